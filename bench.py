@@ -2,7 +2,13 @@
 """bench.py -- forward-scoring throughput (nucleotides/s) of the MI355X-native StripedHyena engine.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
-prints ONE JSON line on rank 0.
+prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, W warm-up steps, the K timed
+steps, the outputs (--dump-outputs DIR) and the line (`metric`, `value`, `unit`, `ms_per_step`, ...).  --full adds
+everything else below (box probes, per-kernel timings and rooflines, the in-process A/B legs, the CPU baseline, the
+131k context, generation and the decode pool; the --skip-* options leave parts of it out).
+--dump-outputs DIR: the last timed step's per-token log-probs as DIR/logprobs.npy (float32 [B, nt]) and the
+per-sequence mean scores as DIR/scores.npy (float64 [B]); N > 1: every rank writes its own, suffixed _rank<r>.
+The inputs (ids and weights) are seeded: the same arguments give the same inputs in every run.
 
 Workloads (BASELINE.json):
   primary  `value`    : configs[1]  evo-1-8k-base scoring, batch 8 x 8,192 nt (T = 8,193 with BOS), bf16, per GPU.
@@ -55,6 +61,28 @@ def scoring_step(model, ids):
     (32 blocks, final norm, fused unembed + log-softmax + gather)."""
     from evo_amd.scoring import score_logprobs_device
     return score_logprobs_device(model, ids)[0]
+
+
+DUMP_BYTES = 64 << 20                                     # --dump-outputs: at most this much in all (over the ranks)
+
+
+def dump_outputs(out_dir, lp, rank=0, world=1):
+    """--dump-outputs: what the timed path returned in its last step, as float .npy files in `out_dir`.  A log-prob matrix larger
+    than this rank's share of DUMP_BYTES is written as a fixed, seeded sample of its elements, with their flat indices beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    lp = lp.float().cpu().numpy()
+    arrays = {"scores": lp.astype(np.float64).mean(-1)}
+    budget = DUMP_BYTES // world - arrays["scores"].nbytes - 3 * 4096          # (room for the .npy headers)
+    if lp.nbytes <= budget:
+        arrays["logprobs"] = lp
+    else:
+        n = budget // (4 + 8)                             # a float32 value and its float64 index per sampled element
+        idx = np.sort(np.random.default_rng(0).choice(lp.size, size=n, replace=False))
+        arrays["logprobs_sample"] = lp.reshape(-1)[idx]
+        arrays["logprobs_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
 
 
 def timed(fn, steps, warmup, dist_on, stats=None):
@@ -537,6 +565,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--nt", type=int, default=8192)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: box probes, per-kernel timings and rooflines, A/B legs, "
+                                                       "CPU baseline, 131k context, generation and pool (the --skip-* options below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--skip-131k", action="store_true")
     ap.add_argument("--skip-ab", action="store_true", help="skip the in-process A/B legs (library_gemm_l3, mlp_gate_unfused, norm_unfused, attention_round4_kernel): "
                                                           "the profile runs want the headline step's kernels only")
@@ -587,15 +618,49 @@ def main():
     T = nt + 1
     step_stats = {}
     box = {}
-    if not args.skip_box:
+    if args.full and not args.skip_box:
         try:
             box = box_probes(ops, device, local)
         except Exception as e:  # noqa: BLE001
             box = {"error": f"{type(e).__name__}: {e}"}
+    last = {}
+
+    def step():
+        last["lp"] = scoring_step(model, ids)
     with torch.inference_mode():
-        with TelemetrySampler(local) as tel_head:
-            dt = timed(lambda: scoring_step(model, ids), args.steps, args.warmup, dist_on, step_stats)
-        box["headline_telemetry"] = tel_head.summary()
+        if args.full:
+            with TelemetrySampler(local) as tel_head:
+                dt = timed(step, args.steps, args.warmup, dist_on, step_stats)
+            box["headline_telemetry"] = tel_head.summary()
+        else:
+            dt = timed(step, args.steps, args.warmup, dist_on, step_stats)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.pop("lp"), rank, world)
+    last.clear()
+    ms_per_step = dt / args.steps * 1e3
+    value = n_gpus * B * nt / (dt / args.steps)
+    out = {
+        "metric": "nucleotides/sec forward scoring, evo-1 7B", "value": value, "unit": "nt/s", "n_gpus": n_gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic ACGT, synthetic weights",
+        "n_ranks": dist.get_world_size() if dist_on else 1,
+        "collectives": (None if not dist_on else "SELF-TEST: gloo, host-staged, all ranks on one GPU (not a measurement)"
+                        if dist.get_backend() == "gloo" else
+                        "RCCL %s (torch.distributed backend nccl)" % ".".join(map(str, torch.cuda.nccl.version()))),
+        "step_timing": step_stats,
+        "config": {"workload": "evo-1-8k-base scoring, batch 8 x 8,192 nt per GPU (BASELINE configs[1])",
+                   "batch_per_gpu": B, "nt": nt, "tokens_per_seq": T,
+                   "parallelism": "independent batches per GPU" if n_gpus > 1 else "single GPU"},
+        "model_tflops": flops_per_token(T) * B * T / (dt / args.steps) / 1e12,
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if dist_on:
+            dist.destroy_process_group()
+        return
+    with torch.inference_mode():
         # per-kernel HIP-event timings over a second, separately instrumented pass of the same steps
         ops.timer = KernelTimer()
         for _ in range(args.steps):
@@ -603,8 +668,6 @@ def main():
         torch.cuda.synchronize()
         ksum = ops.timer.summary()
         ops.timer = None
-    ms_per_step = dt / args.steps * 1e3
-    value = n_gpus * B * nt / (dt / args.steps)
 
     D = 4096
     alg_bytes = B * T * (3 * D * 2 + D * 2)               # z in + y out per launch (32,768 B/token)
@@ -624,26 +687,14 @@ def main():
                       "hand_written_share_of_dense_ms": sum(ksum[k][1] * ksum[k][0] / args.steps for k in ("gemm_mfma", "gemm_gate", "gemm_zt") if k in ksum) / gemm_ms,
                       "note": "2.5 PFLOP/s is the dense peak; the part is power-limited: both kernels run their MFMA pipes 82-86 % busy "
                               "at 1.6-1.7 GHz (profiles/r03_gemm_notes.txt)"}
-    out = {
-        "metric": "nucleotides/sec forward scoring, evo-1 7B", "value": value, "unit": "nt/s", "n_gpus": n_gpus,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic ACGT, synthetic weights",
-        "n_ranks": dist.get_world_size() if dist_on else 1,
-        "collectives": (None if not dist_on else "SELF-TEST: gloo, host-staged, all ranks on one GPU (not a measurement)"
-                        if dist.get_backend() == "gloo" else
-                        "RCCL %s (torch.distributed backend nccl)" % ".".join(map(str, torch.cuda.nccl.version()))),
-        "step_timing": step_stats,
-        "config": {"workload": "evo-1-8k-base scoring, batch 8 x 8,192 nt per GPU (BASELINE configs[1])",
-                   "batch_per_gpu": B, "nt": nt, "tokens_per_seq": T,
-                   "parallelism": "independent batches per GPU" if n_gpus > 1 else "single GPU"},
-        "model_tflops": flops_per_token(T) * B * T / (dt / args.steps) / 1e12,
+    out.update({
         "roofline": roofline, "roofline_dense": roofline_dense, "kernels": kernels, "gemm_ms_per_step": gemm_ms,
         "gemm_library_launches_per_step": kernels.get("gemm", {}).get("launches_per_step", 0),
         "box": box,
         "weights_resident_GB": model.resident_bytes() / 1e9,
         "weights_resident_note": "the scoring model as this run used it (default: originals + norm-folded copies + operand tables); "
                                  "`generation.weights_resident_GB` is the same model on ONE weight set (fold_norms_)",
-    }
+    })
     if "library_gemm_tflops" in box and "hbm_copy_GBs" in box:
         share = min(1.0, gemm_ms / (step_stats.get("hip_event_ms_median") or ms_per_step))
         cal = share * box["library_gemm_tflops"] / REF_GEMM_TFLOPS + (1.0 - share) * box["hbm_copy_GBs"] / REF_COPY_GBS

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything a round is judged on, on one MI355X box:  gpurun --timeout 3000 -- 'bash tools/gpu_check.sh [notests|tests]'
-#   -m gpu tests (with -rs and the parity numbers the tests print), smoke(), bench.py (default flags), the rocprofv3 kernel-trace
+#   -m gpu tests (with -rs and the parity numbers the tests print), smoke(), bench.py --full, the rocprofv3 kernel-trace
 #   summaries of the 8k and the 131k scoring step, the PMC traffic passes of the Hyena operator and its SQ counters, the decode
 #   kernel-trace -- summaries land in gpurun_out/check/ and are copied to profiles/rNN_*.
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
@@ -22,9 +22,9 @@ timeout 300 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum --kernel-tra
 cd $R && (python tools/summarize_prof.py pmc $O/pmc_zrd; python tools/summarize_prof.py pmc $O/pmc_zwr) | grep -E "^kernel|hyena_ct" > $O/hyena_ct_pmc_traffic.txt; rm -rf $O/pmc_zrd $O/pmc_zwr
 cat $O/hyena_ct_pmc_traffic.txt
 python tools/pmc_live.py $O/hyena_ct_pmc_traffic.txt $O/pmc_traffic_live.json "${EVO_COMMIT:-unknown}"
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 400 $O/bench.json
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 400 $O/bench.json
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o b -- python $R/bench.py --skip-131k --skip-cpu --skip-gen --skip-ab --steps 3 --warmup 1 > $R/$O/prof_bench.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o b -- python $R/bench.py --full --skip-131k --skip-cpu --skip-gen --skip-ab --steps 3 --warmup 1 > $R/$O/prof_bench.log 2>&1
 cd $R && python tools/summarize_prof.py stats $O/prof > $O/bench_8k_kernel_stats.txt && rm -rf $O/prof
 head -14 $O/bench_8k_kernel_stats.txt
 cd /tmp
@@ -47,6 +47,6 @@ tail -1 $O/prof_gen.log; head -8 $O/decode_kernel_stats.txt
 if [ "$1" != "tests" ]; then
 bash tools/attn_counters.sh 2 > /dev/null 2>&1; bash tools/attn_counters.sh 1 > /dev/null 2>&1
 cp gpurun_out/attn_sq/form2.txt $O/attn_sq_form2.txt; cp gpurun_out/attn_sq/form1.txt $O/attn_sq_form1.txt
-EVO_AMD_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --skip-cpu --skip-gen > $O/bench_n2_selftest.json 2> $O/bench_n2_selftest.err; echo "n2 self-test rc=$?"
+EVO_AMD_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --full --skip-cpu --skip-gen > $O/bench_n2_selftest.json 2> $O/bench_n2_selftest.err; echo "n2 self-test rc=$?"
 fi
 
