@@ -57,10 +57,11 @@ _SIGNATURES = {
     "evo_logprob_entropy": ([_PTR, _I64, _PTR, _PTR, _PTR, _I64, _I64, _PTR], _c.c_int),
     "evo_unembed_logprob_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_rope_append_decode_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR], _c.c_int),
+    "evo_pool_rows_bf16": ([_PTR, _I64, _I64, _I64, _PTR, _I64, _PTR, _F32, _I64, _I64, _PTR, _PTR, _PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 10         # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 11        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 
 
 class EvoLibraryError(RuntimeError):
@@ -1048,6 +1049,47 @@ class HipOps:
             _check(self.lib.evo_unembed_logprob_bf16(h.data_ptr(), emb.data_ptr(), _ptr(target), _ptr(lp), _ptr(en),
                                                      M, V, K, _stream()), "evo_unembed_logprob_bf16")
         return lp, en
+
+    POOL_MODES = {"mean": 0, "last": 1}
+    POOL_WORKGROUPS = 1024      # strips of all sequences together: 4 per CU (16 waves) -- 1 x 131,073 and 8 x 8,193 both reach it
+
+    def pool_rows(self, x: torch.Tensor, ranges, scale: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                  mode: str = "mean") -> torch.Tensor:
+        """Masked row pooling (csrc/pool.hip): x [M, D] bf16 (row stride >= D), `ranges` = B pairs (first_row, n_rows) as a list or an
+        int64 tensor [B, 2] -> [B, D] fp32: the mean (mode "mean") or the last row (mode "last") of each range, of x itself or -- with
+        `scale` -- of the RMSNorm of its rows (scale * x / (rms(x) + eps), in fp32, no bf16 rounding)."""
+        if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+            raise RuntimeError("pool_rows: x must be a [M, D] bf16 device matrix with unit column stride")
+        if x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(0) < x.shape[1]:
+            raise RuntimeError("pool_rows: x must be 16-byte aligned with a row stride >= D, a multiple of 8")
+        if mode not in self.POOL_MODES:
+            raise ValueError(f"pool_rows: mode must be one of {tuple(self.POOL_MODES)}, got {mode!r}")
+        if scale is not None:
+            self._need(scale, torch.bfloat16, "pool_rows scale")
+            assert scale.numel() == x.shape[1]
+        M, D = x.shape
+        if isinstance(ranges, torch.Tensor):
+            rg = ranges.to(device=x.device, dtype=torch.int64).reshape(-1, 2).contiguous()
+            longest = M
+        else:
+            pairs = [(int(a), int(n)) for a, n in ranges]
+            for a, n in pairs:
+                if a < 0 or n < 1 or a + n > M:
+                    raise ValueError(f"pool_rows: range (first={a}, n={n}) is outside the {M} rows of x")
+            rg = torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2).to(x.device)
+            longest = max(n for _, n in pairs) if pairs else 0
+        B = rg.shape[0]
+        if B < 1:
+            raise ValueError("pool_rows: no ranges")
+        # strips per sequence: POOL_WORKGROUPS over the batch, no strip below 16 rows (a wave then still pools 4 of them)
+        n_strips = 1 if mode == "last" else max(1, min(-(-self.POOL_WORKGROUPS // B), -(-longest // 16)))
+        ws = torch.empty(B * n_strips * D, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, D, dtype=torch.float32, device=x.device)
+        with self._t("pool_rows"):
+            _check(self.lib.evo_pool_rows_bf16(x.data_ptr(), M, D, x.stride(0), rg.data_ptr(), B, _ptr(scale), float(eps),
+                                               self.POOL_MODES[mode], n_strips, ws.data_ptr(), out.data_ptr(), _stream()),
+                   "evo_pool_rows_bf16")
+        return out
 
 
 _DEFAULT_OPS = None

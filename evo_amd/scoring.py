@@ -65,6 +65,8 @@ def logits_to_logprobs(logits: torch.Tensor, input_ids: torch.Tensor, trim_bos: 
 def _fused_tail_ok(model, input_ids) -> bool:
     """The fused unembed + log-softmax + gather kernel serves the engine's own model class on the GPU."""
     ops = getattr(model, "ops", None) if hasattr(model, "hidden_states") else None
+    if not getattr(model, "has_own_unembed", True) or not isinstance(getattr(getattr(model, "unembed", None), "weight", None), torch.Tensor):
+        return False                    # model.unembed replaced (e.g. by an identity module): model(ids) returns what it makes
     return (ops is not None and getattr(ops, "name", "") == "hip-gfx950" and hasattr(ops, "unembed_logprob")
             and ops.unembed_logprob_ok(model.unembed.weight.new_empty(1, model.hidden_size), model.unembed.weight))
 

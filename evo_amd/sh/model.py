@@ -14,6 +14,7 @@ There is no CPU fallback here: with no `ops` injected and no usable HIP library 
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -82,6 +83,27 @@ class _AttentionBlock(nn.Module):
         self.mlp = _MLP(D, inner)
 
 
+class _Unembed(nn.Module):
+    """The tied unembedding (`weight` is embedding_layer.weight).  `unembed(u)` [..., D] -> logits [..., V], the API of upstream's
+    VocabParallelEmbedding.unembed -- so a caller can reach the logits of a hidden state, and the identity-unembed recipe (replace
+    `model.unembed` by a module whose unembed() returns its input) finds the method it overrides."""
+
+    def __init__(self, owner, weight):
+        super().__init__()
+        self.weight = weight
+        object.__setattr__(self, "_owner", weakref.ref(owner))     # (not a submodule: no cycle in the module tree)
+
+    def unembed(self, u: torch.Tensor) -> torch.Tensor:
+        owner = self._owner()
+        if owner is not None:
+            ops = owner.ops
+        else:
+            from ..ops import default_ops
+            ops = default_ops()
+        D = u.shape[-1]
+        return ops.linear(u.reshape(-1, D).contiguous(), self.weight, None).view(*u.shape[:-1], self.weight.shape[0])
+
+
 class StripedHyena(nn.Module):
     def __init__(self, config, ops=None):
         super().__init__()
@@ -115,8 +137,7 @@ class StripedHyena(nn.Module):
         bf = torch.bfloat16
         self.embedding_layer = _Params(weight=((self.vocab_size, D), bf))
         self.norm = _Params(scale=((D,), bf)) if bool(_cfg(c, "final_norm", True)) else None
-        self.unembed = nn.Module()
-        self.unembed.weight = self.embedding_layer.weight          # tied [REF evo/models.py:132-137]
+        self.unembed = _Unembed(self, self.embedding_layer.weight)  # tied [REF evo/models.py:132-137]
         blocks = []
         for i in range(self.num_layers):
             if i in self.attn_layer_idxs:
@@ -782,26 +803,103 @@ class StripedHyena(nn.Module):
         dyn = T == 1 and mha_c is not None and getattr(mha_c, "pos_tensor", None) is not None
         if dyn and not hasattr(ops, "rope_append_decode"):   # (fallback path) one rotary table per decode step for all layers
             mha_c._rot_dyn = self._rotary_dyn(mha_c.pos_tensor)
-        rs = None
-        taps = getattr(self, "block_taps", None)     # debugging / parity hook: residual stream entering every block
-        tap_idxs = getattr(self, "block_tap_idxs", None)   # ... or only the listed ones (index num_layers = the final stream)
         try:
-            for i, blk in enumerate(self.blocks):
-                if taps is not None and (tap_idxs is None or i in tap_idxs):
-                    taps.append(h.clone())
-                # rs: 1 / (rms + eps) of every row of h, from the epilogue of the dense layer that wrote it (None: the block norms h itself)
-                if isinstance(blk, _AttentionBlock):
-                    rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs)
-                else:
-                    rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs)
-            if taps is not None and (tap_idxs is None or self.num_layers in tap_idxs):
-                taps.append(h.clone())
+            self._run_blocks(h, B, T, mha_c, hy_c, mask)
         finally:
             if dyn:
                 mha_c._rot_dyn = None
         if self.norm is not None:
             h = ops.rmsnorm(h, None, self.norm.scale, self.eps)
         return h
+
+    def _run_blocks(self, h: torch.Tensor, B: int, T: int, mha_c, hy_c, mask, stop: Optional[int] = None, after_block=None) -> None:
+        """Blocks 0 .. stop - 1 (default: all) on the residual stream h [B T, D], in place.  `after_block(i, h)` is called as soon as
+        block i has finished (StripedHyena.embeddings pools the streams it asked for there)."""
+        stop = self.num_layers if stop is None else stop
+        rs = None
+        taps = getattr(self, "block_taps", None)     # debugging / parity hook: residual stream entering every block
+        tap_idxs = getattr(self, "block_tap_idxs", None)   # ... or only the listed ones (index num_layers = the final stream)
+        for i in range(stop):
+            blk = self.blocks[i]
+            if taps is not None and (tap_idxs is None or i in tap_idxs):
+                taps.append(h.clone())
+            # rs: 1 / (rms + eps) of every row of h, from the epilogue of the dense layer that wrote it (None: the block norms h itself)
+            if isinstance(blk, _AttentionBlock):
+                rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs)
+            else:
+                rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs)
+            if after_block is not None:
+                after_block(i, h)
+        if stop == self.num_layers and taps is not None and (tap_idxs is None or self.num_layers in tap_idxs):
+            taps.append(h.clone())
+
+    @torch.no_grad()
+    def embeddings(self, input_ids: torch.Tensor, layers, pooling: str = "mean", start: int = 1, lengths=None,
+                   padding_mask=None, inference_params_dict=None) -> Dict:
+        """Sequence embeddings of ids [B, T] in ONE partial forward: {layer: tensor} for every requested layer.
+
+        layers:  block indices k in [0, num_layers) -- the residual stream LEAVING block k (what block_taps records as the input of
+                 block k + 1) -- and / or "final", the final-norm output (hidden_states()' result).  The blocks run up to the deepest
+                 one requested and stop there; the unembedding never runs.
+        pooling: "mean" / "last" over positions [start, start + lengths[b]) of row b (default start = 1: the BOS of prepare_batch is
+                 skipped; lengths default to T - start; pads beyond a row's length are never pooled) -> [B, D] fp32, pooled by the
+                 pooling kernel (csrc/pool.hip) as soon as the layer's block finishes; for "final" with the RMSNorm fused in (the normed
+                 [B T, D] is never written).  "none": the per-position rows, [B, T, D] bf16 (for "final" bit for bit hidden_states()).
+        Batches beyond max_rows_per_pass run in row groups (_row_groups), as hidden_states does.  Not supported: a padding mask, an
+        inference cache, a model whose weights are not on the GPU."""
+        from ..embeddings import check_pooling, normalize_layers
+        if padding_mask is not None:
+            raise ValueError("embeddings: padding_mask is not supported (pass the true lengths instead: pads are never pooled)")
+        if inference_params_dict is not None:
+            raise ValueError("embeddings: an inference cache is not supported (embeddings are a stateless forward)")
+        if not self.embedding_layer.weight.is_cuda:
+            raise RuntimeError(f"embeddings: the model's weights are on {self.embedding_layer.weight.device}; move the model to the GPU")
+        layers = normalize_layers(layers, self.num_layers)
+        check_pooling(pooling)
+        if input_ids.dim() != 2:
+            raise ValueError("input_ids must be [batch, length]")
+        B, T = input_ids.shape
+        if lengths is None:
+            lengths = [T - start] * B
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != B:
+            raise ValueError(f"embeddings: {len(lengths)} lengths for a batch of {B}")
+        if start < 0 or any(n < 1 or start + n > T for n in lengths):
+            raise ValueError(f"embeddings: every row needs 1 <= length and start + length <= T = {T} (start {start}, lengths {lengths})")
+        if not self._packed:
+            self._pack()
+        ops = self.ops
+        D = self.hidden_size
+        dev = self.device
+        blocks = [l for l in layers if l != "final"]
+        stop = self.num_layers if "final" in layers else max(blocks) + 1
+        out = {l: (torch.empty(B, T, D, dtype=torch.bfloat16, device=dev) if pooling == "none"
+                   else torch.empty(B, D, dtype=torch.float32, device=dev)) for l in layers}
+        b0 = 0
+        for nb in self._row_groups(B, T):
+            ranges = [(b * T + start, lengths[b0 + b]) for b in range(nb)]
+
+            def take(l, hh, scale=None, b0=b0, nb=nb, ranges=ranges):
+                if pooling == "none":
+                    out[l][b0:b0 + nb] = hh.view(nb, T, D)
+                else:
+                    out[l][b0:b0 + nb] = ops.pool_rows(hh, ranges, scale=scale, eps=self.eps, mode=pooling)
+
+            def after_block(i, hh):
+                if i in blocks:
+                    take(i, hh)
+
+            h = ops.embed(input_ids[b0:b0 + nb].to(dev), self.embedding_layer.weight)
+            self._run_blocks(h, nb, T, None, None, None, stop=stop, after_block=after_block)
+            if "final" in layers:
+                if self.norm is None:
+                    take("final", h)
+                elif pooling == "none":
+                    take("final", ops.rmsnorm(h, None, self.norm.scale, self.eps))
+                else:
+                    take("final", h, scale=self.norm.scale)
+            b0 += nb
+        return out
 
     @torch.no_grad()
     def forward(self, x, inference_params_dict=None, padding_mask=None):
@@ -818,14 +916,25 @@ class StripedHyena(nn.Module):
             padding_mask = None
         if padding_mask is not None:
             h = self.hidden_states(x, inference_params_dict, padding_mask)
-            return self.ops.linear(h, self.unembed.weight, None).view(B, T, self.vocab_size), inference_params_dict
+            return self._unembed_output(h, B, T), inference_params_dict
         if T == 1 and inference_params_dict is not None and self._graph_eligible(inference_params_dict):
             logits = self._graph_decode_step(x, inference_params_dict)
             if logits is not None:
                 return logits, inference_params_dict
         h = self.hidden_states(x, inference_params_dict)
-        logits = self.ops.linear(h, self.unembed.weight, None).view(B, T, self.vocab_size)
-        return logits, inference_params_dict
+        return self._unembed_output(h, B, T), inference_params_dict
+
+    @property
+    def has_own_unembed(self) -> bool:
+        """False once `model.unembed` has been replaced by another module (the identity-unembed embedding recipe)."""
+        return isinstance(self.unembed, _Unembed)
+
+    def _unembed_output(self, h: torch.Tensor, B: int, T: int) -> torch.Tensor:
+        """What forward returns for the final-norm hidden states h [B T, D]: the logits [B, T, V], or -- with `model.unembed` replaced --
+        whatever the replacement's unembed() makes of h [B, T, D] (upstream users swap in an identity module to get embeddings)."""
+        if not self.has_own_unembed:
+            return self.unembed.unembed(h.view(B, T, self.hidden_size))
+        return self.ops.linear(h, self.unembed.weight, None).view(B, T, self.vocab_size)
 
     # ------------------------------------------------------------------ hipGraph-captured decode step
     # One decode step is ~270 short launches (the reference pays that per token too); at batch 1 the step is
@@ -838,6 +947,8 @@ class StripedHyena(nn.Module):
         if not self.decode_graph or os.environ.get("EVO_AMD_DECODE_GRAPH", "1") == "0":
             return False
         if getattr(self.ops, "name", "") != "hip-gfx950" or getattr(self.ops, "timer", None) is not None:
+            return False
+        if not self.has_own_unembed:          # the captured step bakes in the engine's unembedding weight
             return False
         hy, mha = ipd["hyena"], ipd["mha"]
         # every layer must already hold state (i.e. a prefill happened), on this device

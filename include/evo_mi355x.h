@@ -48,8 +48,9 @@ extern "C" {
  *      evo_rope_qk_bf16 and evo_rope_append_decode_bf16 gained `q_scale`, evo_attn_fwd_causal_bf16 / evo_attn_decode_bf16 accept
  *      softmax_scale <= 0 = "queries pre-scaled" (the prefill attention kernel without its per-score multiply); evo_linear_small_m_bf16
  *      takes up to 64 rows and an optional workspace (`ws`, `ws_bytes`: split over K across workgroups for the narrow layers); evo_hyena_ct gained `y_row_pitch` (rows of y between two batch rows: the scoring path runs the 512 k main tokens
- *      of every row through the operator and the one token behind them through the single-token launch, see below). */
-#define EVO_ABI_VERSION 10
+ *      of every row through the operator and the one token behind them through the single-token launch, see below).
+ *  11: evo_pool_rows_bf16 added (sequence embeddings: masked row pooling with the final RMSNorm optionally fused in); no signature changed. */
+#define EVO_ABI_VERSION 11
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -349,6 +350,24 @@ int evo_logprob_entropy(const void* logits, int64_t logits_f32, const int64_t* t
  * and the softmax statistics are taken in fp32 on the rounded values.  V must be 512, K % 32 == 0. */
 int evo_unembed_logprob_bf16(const void* hidden, const void* emb, const int64_t* target,
                              float* logprob, float* entropy, int64_t M, int64_t V, int64_t K, void* stream);
+
+/* ---- sequence embeddings: masked row pooling (+ fused RMSNorm) --------------------------------------------
+ * replaces the torch mean over positions of the hidden states that evo users take as embeddings (no reference kernel: upstream
+ * users swap in an identity unembedding and reduce [B, T, D] in eager torch)
+ *   x      [M, D] bf16 rows with a pitch of `ld` elements (ld >= D, ld % 8 == 0, x 16-byte aligned): the residual stream
+ *   ranges [B, 2] device int64: sequence b pools rows first_b .. first_b + n_b - 1 of x (a range with first_b < 0, n_b < 1 or
+ *          first_b + n_b > M pools nothing and gets a NaN row)
+ *   scale  [D] bf16 or NULL: with it f(x) = scale * x / (||x||_2 D^-1/2 + eps) (the engine's RMSNorm, eps outside the root) taken
+ *          in fp32 from the bf16 rows, no rounding in between; NULL: f(x) = x.  The scale is applied once, after the sum.
+ *   mode   0 = mean:  out[b] = (1 / n_b) * sum_t f(x_t);  1 = last:  out[b] = f(x_{first_b + n_b - 1})
+ *   ws     fp32 workspace of B * n_strips * D floats (B * n_strips * D * 4 bytes): one partial slab per (sequence, strip); a
+ *          sequence's rows are split into n_strips nearly equal strips, one workgroup each (1 <= n_strips <= 65535)
+ *   out    [B, D] fp32
+ * Two launches (strip partials, then a fixed-order sum of each sequence's slabs), no float atomics: bit-identical from run to run.
+ * D <= 4096 (the register plan: D / 64 fp32 column sums per lane), D % 8 == 0, 1 <= B <= 65535.  Returns -1 for a null pointer
+ * (x, ranges, ws, out), a bad D / ld / M, B < 1, n_strips out of range or an unknown mode. */
+int evo_pool_rows_bf16(const void* x, int64_t M, int64_t D, int64_t ld, const int64_t* ranges, int64_t B,
+                       const void* scale, float eps, int64_t mode, int64_t n_strips, float* ws, float* out, void* stream);
 
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:
