@@ -1,0 +1,209 @@
+// Seeded sampling of one token per row of [S, 512] logits, entirely on the device (the written
+// specification is evo_amd/sh/sample.py: sample_seeded).  One launch, no host reads, no allocation: capturable in a hipGraph.
+// One 64-lane wave per row.  The row's 512 (logit, id) pairs are packed into 64-bit keys -- the logit as an order-preserving
+// 32-bit pattern in the high word, 511 - id in the low word -- and sorted DESCENDING by a bitonic network through 4 KB of LDS,
+// which gives the order "logit descending, ties by ascending id".  Everything else falls out of that one order, 8 consecutive
+// positions per lane: the k-th value (top-k keeps its ties), the top-p cut (the reference's ascending cumulative softmax is the
+// suffix sum here, so the survivors are a prefix) and the CDF walk.  Sums are fp32 in a FIXED order (8 sequential terms per lane,
+// then a Hillis-Steele scan / butterfly over the lanes), so a row's token is bit-identical from run to run.  No float atomics.
+// The random number of a row is Philox4x32-10 keyed by the seed, counter = (stream id, draw count): a function of the sample and
+// the draw, not of the slot or the step.  Entry point and contract: include/evo_mi355x.h.
+#include "common.h"
+#include "../../include/evo_mi355x.h"
+
+#define EVO_SAMPLE_V 512
+
+__device__ __forceinline__ uint32_t philox4x32_10_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// float <-> a 32-bit pattern whose unsigned order is the float order (-inf lowest, +inf highest)
+__device__ __forceinline__ uint32_t sample_ord(float x) {
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sample_unord(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+__device__ __forceinline__ int sample_wave_sum_i(int v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(64) void sample_rows_kernel(const void* __restrict__ logits, int logits_f32, int64_t ld,
+                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                         const float* __restrict__ temperature, const uint8_t* __restrict__ allow,
+                                                         uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ stream_id,
+                                                         int64_t* count, const uint8_t* __restrict__ active, int64_t* ids_out,
+                                                         float* logprob_out, int64_t* hist_ids, float* hist_logits, int64_t hist_len) {
+    __shared__ uint64_t keys[EVO_SAMPLE_V];
+    __shared__ float raw[EVO_SAMPLE_V];
+    const int lane = threadIdx.x;
+    const int64_t s = blockIdx.x;
+    if (active && !active[s]) return;                                 // (the whole wave: before any barrier)
+
+    // ---- the row: ids lane * 8 .. lane * 8 + 7
+    float x[8];
+    if (logits_f32) {
+        const f32x4_t* p = (const f32x4_t*)((const float*)logits + s * ld) + 2 * lane;
+        const f32x4_t a = p[0], b = p[1];
+        x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3];
+        x[4] = b[0]; x[5] = b[1]; x[6] = b[2]; x[7] = b[3];
+    } else {
+        const uint4 v = ((const uint4*)((const uint16_t*)logits + s * ld))[lane];
+        x[0] = bf_lo(v.x); x[1] = bf_hi(v.x); x[2] = bf_lo(v.y); x[3] = bf_hi(v.y);
+        x[4] = bf_lo(v.z); x[5] = bf_hi(v.z); x[6] = bf_lo(v.w); x[7] = bf_hi(v.w);
+    }
+    const int64_t cnt = count ? count[s] : 0;
+    const int64_t sid = stream_id ? stream_id[s] : s;
+    const bool hist_ok = cnt >= 0 && cnt < hist_len;                  // (hist_len = 0 without history)
+    if (hist_logits && hist_ok) {
+        f32x4_t* h = (f32x4_t*)(hist_logits + (s * hist_len + cnt) * EVO_SAMPLE_V) + 2 * lane;
+        h[0] = f32x4_t{x[0], x[1], x[2], x[3]};
+        h[1] = f32x4_t{x[4], x[5], x[6], x[7]};
+    }
+
+    // ---- log-sum-exp of the UNFILTERED row (fp32)
+    float mx = x[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) mx = fmaxf(mx, x[j]);
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) se += expf(x[j] - mx);
+    se = wave_sum(se);
+    const float lse = mx + logf(se);
+
+    // ---- keys: allow mask, then (logit, id) -> LDS
+    const uint32_t abits = allow ? allow[lane] : 0xffu;             // bit j of byte b: token 8 b + j
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int id = lane * 8 + j;
+        raw[id] = x[j];
+        float v = ((abits >> j) & 1u) ? x[j] : -INFINITY;
+        if (v == 0.f) v = 0.f;                                        // -0 and +0 are one value
+        keys[id] = ((uint64_t)sample_ord(v) << 32) | (uint32_t)(EVO_SAMPLE_V - 1 - id);
+    }
+    __syncthreads();
+
+    // ---- bitonic sort, descending: 45 steps of 256 compare-exchanges (4 per lane); every index stays below 512
+    for (int k = 2; k <= EVO_SAMPLE_V; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int t = lane; t < EVO_SAMPLE_V / 2; t += 64) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // bit j clear
+                const int p = i | j;
+                const uint64_t a = keys[i], b = keys[p];
+                const bool down = (i & k) == 0;
+                if ((a < b) == down) { keys[i] = b; keys[p] = a; }
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- sorted positions lane * 8 .. lane * 8 + 7
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = sample_unord((uint32_t)(keys[lane * 8 + j] >> 32));
+    const float v0 = sample_unord((uint32_t)(keys[0] >> 32));
+    const int k = top_k[s];
+    int pos = 0;                                                      // top_k == 1: the arg-max, lowest id on ties
+    if (k != 1) {
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c += v[j] > -INFINITY ? 1 : 0;
+        int n_keep = sample_wave_sum_i(c);                            // finite logits
+        if (k > 1 && k < EVO_SAMPLE_V) {
+            const float kth = sample_unord((uint32_t)(keys[k - 1] >> 32));
+            c = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) c += v[j] >= kth ? 1 : 0;     // ties with the k-th value stay
+            n_keep = min(n_keep, sample_wave_sum_i(c));
+        }
+        const float T = temperature[s];
+        const bool use_t = T != 1.0f && T > 0.f;
+        // e = exp(logit - max) of the kept prefix, inclusive prefix sums P in position order
+        float P[8];
+        float run = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float d = use_t ? (v[j] - v0) / T : v[j] - v0;
+            run += (lane * 8 + j < n_keep) ? expf(d) : 0.f;
+            P[j] = run;
+        }
+        float scan = run;                                             // inclusive scan of the lane totals, fixed order
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float up = __shfl_up(scan, d, 64);
+            if (lane >= d) scan += up;
+        }
+        const float prev = __shfl_up(scan, 1, 64);
+        const float base = lane == 0 ? 0.f : prev;                    // sum of every earlier lane's terms
+#pragma unroll
+        for (int j = 0; j < 8; ++j) P[j] += base;
+        const float Z = __shfl(scan, 63, 64);
+        const float p = top_p[s];
+        if (p > 0.f && p < 1.f) {
+            // the reference drops, in ASCENDING order, while the cumulative softmax is <= 1 - top_p: that cumulative value is the
+            // suffix sum Z - (exclusive prefix) here
+            const float thr = (1.0f - p) * Z;
+            c = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float excl = j == 0 ? base : P[j - 1];
+                c += (lane * 8 + j < n_keep && Z - excl > thr) ? 1 : 0;
+            }
+            n_keep = sample_wave_sum_i(c);
+        }
+        n_keep = max(n_keep, 1);
+        float zk = 0.f;                                               // P at position n_keep - 1 (P never decreases)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) zk = fmaxf(zk, lane * 8 + j < n_keep ? P[j] : 0.f);
+        zk = wave_max(zk);
+        const uint32_t r = philox4x32_10_x0((uint32_t)sid, (uint32_t)((uint64_t)sid >> 32), (uint32_t)cnt,
+                                            (uint32_t)((uint64_t)cnt >> 32), seed_lo, seed_hi);
+        const double u = ((double)(r >> 8) + 0.5) * 0x1p-24;
+        const float target = (float)(u * (double)zk);
+        c = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) c += (lane * 8 + j < n_keep && P[j] <= target) ? 1 : 0;
+        pos = min(sample_wave_sum_i(c), n_keep - 1);                  // first position whose inclusive CDF exceeds u
+    }
+    const int tok = EVO_SAMPLE_V - 1 - (int)(uint32_t)keys[pos];      // 0 <= pos < 512, 0 <= tok < 512
+    if (lane == 0) {
+        ids_out[s] = tok;
+        logprob_out[s] = raw[tok] - lse;
+        if (hist_ids && hist_ok) hist_ids[s * hist_len + cnt] = tok;
+        if (count) count[s] = cnt + 1;
+    }
+}
+
+extern "C" int evo_sample_rows_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,
+                                   const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
+                                   const uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
+                                   int64_t hist_len, int64_t S, int64_t V, void* stream) {
+    if (!logits || !top_k || !top_p || !temperature || !ids_out || !logprob_out) return -1;
+    if (S < 1 || S > 0x7fffffff || V != EVO_SAMPLE_V || ld < V || ld % 8 != 0) return -1;
+    if (((uintptr_t)logits & 15) || ((uintptr_t)hist_logits & 15)) return -1;
+    if ((hist_ids || hist_logits) && (!count || hist_len < 1)) return -1;
+    if (!hist_ids && !hist_logits) hist_len = 0;
+    hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, logits, (int)(logits_f32 != 0), ld, top_k,
+                       top_p, temperature, (const uint8_t*)allow, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, count, active,
+                       ids_out, logprob_out, hist_ids, hist_logits, hist_len);
+    return evo_launch_status();
+}

@@ -23,19 +23,26 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
-from .sh.sample import sample
+from .sh.sample import allowed_mask, sample
 from .tokenizer import CharLevelTokenizer
 
 
 class Generator:
     def __init__(self, model, tokenizer: CharLevelTokenizer, top_k: int = 50, top_p: float = 0.7,
-                 temperature: float = 1.0):
+                 temperature: float = 1.0, seed: int = None, allowed_tokens=None):
+        """`seed` / `allowed_tokens` (additions to the reference's interface, off by default): with either, tokens are drawn by
+        the device sampler `evo_sample_rows_f32` -- row b of a batch draws from random stream `stream_offset + b`, reproducibly
+        under `seed`, and only from `allowed_tokens` (e.g. "ACGT") when given."""
         self.model = model
         self.tokenizer = tokenizer
         self.top_k = top_k
         self.top_p = top_p
         self.temperature = temperature
         self.untils = ["\n\n"]
+        self.device_sampler = seed is not None or allowed_tokens is not None
+        self.seed = 0 if seed is None else int(seed)
+        self.allow_mask = None if allowed_tokens is None else allowed_mask(tokenizer, allowed_tokens)
+        self.stream_offset = 0                               # first random stream of the next batch (advanced by `generate`)
 
     def _rehome_cache(self, cache: dict, device) -> None:
         """Cached tensors follow the input's device [REF evo/generation.py:105-114]."""
@@ -87,6 +94,16 @@ class Generator:
             print("Starting generation...")
             print("Prompt: " + input_string if input_string is not None else f"Prompt ids: {input_ids} {input_ids.shape}")
 
+        if self.device_sampler:                              # per-row settings and stream ids of the device sampler, made once
+            ops = self.model.ops
+            s_top_k = torch.full((B,), int(self.top_k), dtype=torch.int32, device=x.device)
+            s_top_p = torch.full((B,), float(self.top_p), dtype=torch.float32, device=x.device)
+            s_temp = torch.full((B,), float(self.temperature), dtype=torch.float32, device=x.device)
+            s_stream = torch.arange(B, dtype=torch.int64, device=x.device) + self.stream_offset
+            s_count = torch.zeros(B, dtype=torch.int64, device=x.device)     # the kernel advances it: draw j has count j
+            s_allow = None if self.allow_mask is None else ops.pack_allow_mask(self.allow_mask, x.device)
+            self.stream_offset += B
+
         total_steps = n_forced + num_tokens
         i = -1
         for i in range(total_steps):
@@ -107,7 +124,11 @@ class Generator:
             if i < n_forced:
                 new_idx = x_force[:, i]                               # teacher forcing of the prompt tail
             else:
-                new_idx = sample(last_logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
+                if self.device_sampler:
+                    new_idx = ops.sample_rows(last_logits, s_top_k, s_top_p, s_temp, self.seed, stream=s_stream, count=s_count,
+                                              allow=s_allow)[0]
+                else:
+                    new_idx = sample(last_logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
                 j = i - n_forced
                 scores[:, j] = last_logits
                 generation[:, j] = new_idx
@@ -134,12 +155,14 @@ class Generator:
 def generate(prompt_seqs: List[str], model, tokenizer: CharLevelTokenizer, n_tokens: int = 100,
              temperature: float = 0.0, top_k: int = 1, top_p: float = 1.0, batched: bool = True,
              prepend_bos: bool = False, cached_generation: bool = False, force_prompt_threshold: int = None,
-             verbose: int = 1, device: str = "cuda:0", **kwargs) -> Tuple[List[str], List[float]]:
+             verbose: int = 1, device: str = "cuda:0", seed: int = None, allowed_tokens=None,
+             **kwargs) -> Tuple[List[str], List[float]]:
     """Generate `n_tokens` after each prompt.  Equal-length prompts run as one batch when `batched`.
-    Returns (generated strings, mean log-likelihood score per generation)."""
+    Returns (generated strings, mean log-likelihood score per generation).  `seed`: the same call gives the same strings
+    (prompt number i draws from random stream i); `allowed_tokens`: the characters that may be generated, e.g. "ACGT"."""
     if hasattr(model, "eval"):
         model.eval()
-    g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature)
+    g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, allowed_tokens=allowed_tokens)
 
     same_len = all(len(s) == len(prompt_seqs[0]) for s in prompt_seqs)
     if batched and same_len:

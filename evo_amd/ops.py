@@ -58,10 +58,11 @@ _SIGNATURES = {
     "evo_unembed_logprob_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_rope_append_decode_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR], _c.c_int),
     "evo_pool_rows_bf16": ([_PTR, _I64, _I64, _I64, _PTR, _I64, _PTR, _F32, _I64, _I64, _PTR, _PTR, _PTR], _c.c_int),
+    "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 11        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 12        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 
 
 class EvoLibraryError(RuntimeError):
@@ -1090,6 +1091,63 @@ class HipOps:
                                                self.POOL_MODES[mode], n_strips, ws.data_ptr(), out.data_ptr(), _stream()),
                    "evo_pool_rows_bf16")
         return out
+
+
+    @staticmethod
+    def pack_allow_mask(mask: torch.Tensor, device) -> torch.Tensor:
+        """bool [512] -> the 64 device bytes `sample_rows` takes (bit j of byte b = token 8 b + j)."""
+        m = torch.as_tensor(mask, dtype=torch.bool).reshape(-1).cpu()
+        if m.numel() != 512 or not bool(m.any()):
+            raise ValueError("allow mask: expected 512 flags with at least one set")
+        w = (m.view(64, 8).to(torch.int32) << torch.arange(8, dtype=torch.int32)[None, :]).sum(-1)
+        return w.to(torch.uint8).to(device)
+
+    def sample_rows(self, logits: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, temperature: torch.Tensor, seed: int,
+                    stream: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                    active: Optional[torch.Tensor] = None, ids_out: Optional[torch.Tensor] = None,
+                    logprob_out: Optional[torch.Tensor] = None, hist_ids: Optional[torch.Tensor] = None,
+                    hist_logits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Seeded sampling on the device (csrc/sample.hip; specification: sh/sample.py sample_seeded): logits [S, 512] bf16 | f32 ->
+        (ids [S] int64, logprob [S] f32 under the unfiltered log-softmax).  top_k int32 / top_p f32 / temperature f32 / stream int64 /
+        count int64 / active bool are device tensors [S]; `allow` the 64 bytes of `pack_allow_mask`; `count` advances by one for
+        every active row; with hist_ids [S, L] int64 / hist_logits [S, L, 512] f32 the token and the f32 row land at [s, count[s]].
+        One launch on the current stream, nothing read back: capturable."""
+        if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2 or not logits.is_cuda:
+            raise RuntimeError("sample_rows: logits must be a [S, 512] bf16 or f32 device matrix")
+        S, V = logits.shape
+        if logits.stride(1) != 1 or logits.stride(0) % 8 or logits.stride(0) < V or logits.data_ptr() % 16:
+            logits = logits.contiguous()
+        dev = logits.device
+
+        def need(t, dtype, shape, what):
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+                raise RuntimeError(f"sample_rows: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        need(top_k, torch.int32, (S,), "top_k")
+        need(top_p, torch.float32, (S,), "top_p")
+        need(temperature, torch.float32, (S,), "temperature")
+        need(stream, torch.int64, (S,), "stream")
+        need(count, torch.int64, (S,), "count")
+        need(active, torch.bool, (S,), "active")
+        need(allow, torch.uint8, (64,), "allow")
+        if ids_out is None:
+            ids_out = torch.empty(S, dtype=torch.int64, device=dev)
+        if logprob_out is None:
+            logprob_out = torch.empty(S, dtype=torch.float32, device=dev)
+        need(ids_out.view(-1), torch.int64, (S,), "ids_out")
+        need(logprob_out, torch.float32, (S,), "logprob_out")
+        hist_len = 0
+        if hist_ids is not None or hist_logits is not None:
+            if count is None:
+                raise RuntimeError("sample_rows: a history needs the per-row count")
+            hist_len = int(hist_ids.shape[1] if hist_ids is not None else hist_logits.shape[1])
+            need(hist_ids, torch.int64, (S, hist_len), "hist_ids")
+            need(hist_logits, torch.float32, (S, hist_len, V), "hist_logits")
+        with self._t("sample_rows"):
+            _check(self.lib.evo_sample_rows_f32(logits.data_ptr(), int(logits.dtype == torch.float32), logits.stride(0), top_k.data_ptr(),
+                                                top_p.data_ptr(), temperature.data_ptr(), _ptr(allow), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                _ptr(stream), _ptr(count), _ptr(active), ids_out.data_ptr(), logprob_out.data_ptr(),
+                                                _ptr(hist_ids), _ptr(hist_logits), hist_len, S, V, _stream()), "evo_sample_rows_f32")
+        return ids_out, logprob_out
 
 
 _DEFAULT_OPS = None

@@ -15,6 +15,12 @@ exact modal state); the `n_sample_per_prompt` copies of a prompt share ONE prefi
 into their slots.  Sampling and scoring follow the reference wrapper verbatim (same `sample`, same shifted
 logits/token pairing [REF evo/generation.py:162-167,287]), so with greedy sampling a pool run reproduces per-prompt
 `generate` token for token (tests/test_pool.py).
+
+With `seed` and / or `allowed_tokens` the sampler is the device kernel `evo_sample_rows_f32`: it is the
+last node of the step (captured with it), writes the next ids where the next step reads them and appends tokens and logits to
+a device-resident history, so the host reads nothing back per step -- a job's rows are copied out once, when its slot finishes.
+Every job draws from its own random stream (its output index), so a sample does not depend on the slot it ran in, on the step
+it was admitted at, or on the other prompts of the job -- for a fixed `n_slots` (the logits themselves depend on the row count).
 """
 from __future__ import annotations
 
@@ -25,12 +31,13 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
-from .sh.sample import sample
+from .sh.sample import allowed_mask, sample
 
 
 class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
-                 temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None):
+                 temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
+                 seed: Optional[int] = None, allowed_tokens=None):
         self.model = model
         self.tok = tokenizer
         self.n_slots = int(n_slots)
@@ -42,6 +49,11 @@ class DecodePool:
         self.capacity = 0
         self._graph = None
         self.stats = {"steps": 0, "prefills": 0, "tokens": 0}
+        # seeded / restricted sampling runs on the device; with neither the host sampler of the reference stays (the default)
+        self.device_sampler = seed is not None or allowed_tokens is not None
+        self.seed = 0 if seed is None else int(seed)
+        self.allow_mask = None if allowed_tokens is None else allowed_mask(tokenizer, allowed_tokens)
+        self.hist_ids = self.hist_logits = None
 
     # ------------------------------------------------------------------ cache rows
     def _allocate(self, capacity: int) -> None:
@@ -73,6 +85,25 @@ class DecodePool:
         self._graph = None
         self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
         self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+        if self.device_sampler:                                      # per-slot sampler state, all of it read by the captured launch
+            self.s_top_k = torch.full((S,), int(self.top_k), dtype=torch.int32, device=dev)
+            self.s_top_p = torch.full((S,), float(self.top_p), dtype=torch.float32, device=dev)
+            self.s_temperature = torch.full((S,), float(self.temperature), dtype=torch.float32, device=dev)
+            self.s_stream = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.s_count = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.s_active = torch.zeros(S, dtype=torch.bool, device=dev)
+            self.s_logprob = torch.zeros(S, dtype=torch.float32, device=dev)
+            self.s_allow = None if self.allow_mask is None else m.ops.pack_allow_mask(self.allow_mask, dev)
+            self.hist_ids = self.hist_logits = None
+
+    def _allocate_history(self, n_tokens: int) -> None:
+        """Device-resident record of every slot's current job: tokens [S, L] and the f32 logits that produced them [S, L, V]."""
+        if self.hist_ids is not None and self.hist_ids.shape[1] >= n_tokens:
+            return
+        S, dev = self.n_slots, self.device
+        self.hist_ids = torch.zeros(S, n_tokens, dtype=torch.int64, device=dev)
+        self.hist_logits = torch.zeros(S, n_tokens, self.model.vocab_size, dtype=torch.float32, device=dev)
+        self._graph = None
 
     def _prefill(self, ids: torch.Tensor):
         """ids [1, P] -> (last-position logits [V] f32, the B = 1 caches of the prompt)."""
@@ -124,11 +155,44 @@ class DecodePool:
             g.replay()
             return out.float()
 
+    # ------------------------------------------------------------------ the same step with the sampler as its last node
+    def _sample_rows(self, logits: torch.Tensor, rows: slice, active) -> None:
+        self.model.ops.sample_rows(logits, self.s_top_k[rows], self.s_top_p[rows], self.s_temperature[rows], self.seed,
+                                   stream=self.s_stream[rows], count=self.s_count[rows], allow=self.s_allow, active=active,
+                                   ids_out=self.ids[rows], logprob_out=self.s_logprob[rows], hist_ids=self.hist_ids[rows],
+                                   hist_logits=self.hist_logits[rows])
+
+    def _step_sample_eager(self) -> None:
+        self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
+        self.pos.add_(1)                                              # (idle slots drift harmlessly; fill() resets them)
+        self.pos.clamp_(max=self.capacity - 1)
+
+    def _step_sampled(self) -> None:
+        """One token for every active slot, nothing returned to the host: ids, counters and history advance on the device."""
+        self.stats["steps"] += 1
+        with torch.inference_mode():
+            if not self.use_graph:
+                return self._step_sample_eager()
+            if self._graph is None:
+                self._step_sample_eager()                             # the first step runs eagerly and IS the step (see _step)
+                torch.cuda.synchronize(self.device)
+                self.model._row_index(self.n_slots, self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._step_sample_eager()
+                self._graph = (g, None)
+                return None
+            self._graph[0].replay()
+
     # ------------------------------------------------------------------ the job
     def generate(self, prompts: Sequence[str], n_tokens: int = 1000, n_sample_per_prompt: int = 1,
-                 prepend_bos: bool = False) -> Tuple[List[str], List[float], List[int]]:
+                 prepend_bos: bool = False, sampling: Optional[Sequence[Optional[dict]]] = None,
+                 streams: Optional[Sequence[int]] = None) \
+            -> Tuple[List[str], List[float], List[int]]:
         """Returns (generated strings, mean log-likelihood scores, index of the prompt each came from), in job
-        order: prompt 0's samples first."""
+        order: prompt 0's samples first.  `sampling` (device sampler only): one dict of `top_k` / `top_p` / `temperature`
+        per prompt (or None) overriding the pool's own settings for that prompt's samples; `streams`: the random-stream id of
+        every output (default: its index, `prompt index * n_sample_per_prompt + copy`), for a job that is a re-ordered part of another."""
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         if hasattr(m, "eval"):
             m.eval()
@@ -141,7 +205,17 @@ class DecodePool:
         if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
             raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
         encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
+        if sampling is not None:
+            if not self.device_sampler:
+                raise ValueError("per-prompt sampling settings need the device sampler (give the pool a seed)")
+            sampling = list(sampling)
+            if len(sampling) != len(prompts) or any(d is not None and set(d) - {"top_k", "top_p", "temperature"} for d in sampling):
+                raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
+        if streams is not None and (not self.device_sampler or len(streams) != len(prompts) * int(n_sample_per_prompt)):
+            raise ValueError("streams: one id per output, and only with the device sampler")
         self._allocate(max(e.shape[1] for e in encoded) + n_tokens)
+        if self.device_sampler:
+            self._allocate_history(n_tokens)
         # job = (output index, prompt index); the copies of one prompt are adjacent so that they share a prefill
         jobs = deque((pi * n_sample_per_prompt + c, pi) for pi in range(len(prompts)) for c in range(n_sample_per_prompt))
         n_jobs = len(jobs)
@@ -159,6 +233,20 @@ class DecodePool:
             last_logits, tmp = cached_prefill[pi]
             P = encoded[pi].shape[1]
             self._install(slot, tmp, P)
+            if self.device_sampler:
+                # the job's settings and its own random stream (its output index); the first token is draw 0 of that stream,
+                # taken by the same kernel from the prefill's last logits
+                cfg = (sampling[pi] if sampling is not None else None) or {}
+                self.s_top_k[slot] = int(cfg.get("top_k", self.top_k))
+                self.s_top_p[slot] = float(cfg.get("top_p", self.top_p))
+                self.s_temperature[slot] = float(cfg.get("temperature", self.temperature))
+                self.s_stream[slot] = j if streams is None else int(streams[j])
+                self.s_count[slot] = 0
+                self.s_active[slot] = True
+                self._sample_rows(last_logits[None], slice(slot, slot + 1), None)
+                self.pos[slot] = P
+                slot_job[slot], slot_n[slot] = j, 1
+                return
             first = sample(last_logits[None], top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
             out_ids[j, 0] = int(first[0])
             out_logits[j, 0] = last_logits.cpu()
@@ -166,16 +254,37 @@ class DecodePool:
             self.pos[slot] = P                                        # the sampled token sits at position P
             slot_job[slot], slot_n[slot] = j, 1
 
+        def fetch(slots: List[int]) -> None:
+            """Finished slots: their history rows leave the device (the only read-back of the device sampler), the slots go idle."""
+            idx = torch.tensor(slots, dtype=torch.int64, device=dev)
+            self.s_active[idx] = False
+            ids_cpu, lg_cpu = self.hist_ids[idx, :n_tokens].cpu(), self.hist_logits[idx, :n_tokens].cpu()
+            for r, s in enumerate(slots):
+                out_ids[slot_job[s]], out_logits[slot_job[s]] = ids_cpu[r], lg_cpu[r]
+                slot_job[s] = None
+
         done = 0
         while done < n_jobs:
             for s in range(S):
                 if slot_job[s] is None and jobs:
                     fill(s)
                     if n_tokens == 1:
+                        if self.device_sampler:
+                            fetch([s])
                         slot_job[s] = None
                         done += 1
             active = [s for s in range(S) if slot_job[s] is not None]
             if not active:
+                continue
+            if self.device_sampler:
+                self._step_sampled()
+                for s in active:
+                    slot_n[s] += 1
+                self.stats["tokens"] += len(active)
+                finished = [s for s in active if slot_n[s] == n_tokens]   # a job's length is fixed: the host knows without reading
+                if finished:
+                    fetch(finished)
+                    done += len(finished)
                 continue
             logits = self._step()                                     # [S, V]
             nxt = sample(logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
@@ -203,10 +312,12 @@ class DecodePool:
 
 def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, temp: float = 0.7, top_k: int = 4,
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
-                device: Optional[str] = None):
+                device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
-    sample, generated sequences, scores)."""
-    pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device)
+    sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
+    (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device."""
+    pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
+                      allowed_tokens=allowed_tokens)
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos)
     return [prompts[i] for i in owner], seqs, scores

@@ -34,3 +34,119 @@ def sample(logits: torch.Tensor, top_k: int = 1, top_p: float = 0.0, temperature
         logits /= temperature
     modify_logits_for_top_p_filtering(logits, top_p)
     return torch.multinomial(torch.softmax(logits, dim=-1), num_samples=1).squeeze(dim=-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Seeded sampling: the written specification of `evo_sample_rows_f32` (csrc/sample.hip).  Pure
+# torch / numpy on the CPU, fp64 inside.  A sample's n-th random number is a function of (seed, stream, n) alone.
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+VOCAB_BITS = 512
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32 with 10 rounds (Salmon et al., SC'11): counter = 4 and key = 2 words of 32 bits -> 4 words.
+    The words are Python ints or numpy uint64 arrays holding 32-bit values (arrays give arrays, element by element)."""
+    import numpy as np
+    vec = any(isinstance(w, np.ndarray) for w in tuple(counter) + tuple(key))
+    cast = (lambda w: np.asarray(w, dtype=np.uint64)) if vec else int
+    c0, c1, c2, c3 = (cast(w) & cast(_M32) for w in counter)
+    k0, k1 = (cast(w) & cast(_M32) for w in key)
+    m32, s32 = cast(_M32), cast(32)
+    for _ in range(10):
+        p0, p1 = cast(_PHILOX_M0) * c0, cast(_PHILOX_M1) * c2          # 32 x 32 -> 64 bits: fits a uint64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + cast(_PHILOX_W0)) & m32, (k1 + cast(_PHILOX_W1)) & m32
+    return c0, c1, c2, c3
+
+
+def seeded_uniform(seed, stream, count):
+    """u in (0, 1) of draw number `count` of sample `stream` under `seed`: key = (seed low, seed high), counter =
+    (stream low, stream high, count low, count high) as 64-bit two's complement, u = ((x0 >> 8) + 0.5) * 2^-24.
+    `stream` / `count` may be ints (-> float) or integer arrays (-> float64 array)."""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if isinstance(stream, (int, np.integer)) and isinstance(count, (int, np.integer)):
+        st, ct = int(stream) & 0xFFFFFFFFFFFFFFFF, int(count) & 0xFFFFFFFFFFFFFFFF
+        x0 = philox4x32_10((st & _M32, st >> 32, ct & _M32, ct >> 32), (seed & _M32, seed >> 32))[0]
+        return ((x0 >> 8) + 0.5) * 2.0 ** -24
+    st, ct = np.broadcast_arrays(np.asarray(stream, dtype=np.int64).astype(np.uint64),
+                                 np.asarray(count, dtype=np.int64).astype(np.uint64))
+    m32, s32 = np.uint64(_M32), np.uint64(32)
+    x0 = philox4x32_10((st & m32, st >> s32, ct & m32, ct >> s32),
+                       (np.full(st.shape, seed & _M32, dtype=np.uint64), np.full(st.shape, seed >> 32, dtype=np.uint64)))[0]
+    return ((x0 >> np.uint64(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+
+
+def allowed_mask(tokenizer, allowed) -> torch.Tensor:
+    """The 512-bit allow mask as a bool tensor [512]: `allowed` is a string (its characters, through `tokenizer`) or
+    an iterable of token ids.  An empty set, or an id outside [0, 512), is a ValueError."""
+    if isinstance(allowed, torch.Tensor):
+        allowed = allowed.tolist()
+    ids = [int(t) for t in tokenizer.tokenize(allowed)] if isinstance(allowed, str) else [int(t) for t in allowed]
+    if not ids:
+        raise ValueError("allowed_tokens: the set of allowed tokens is empty")
+    mask = torch.zeros(VOCAB_BITS, dtype=torch.bool)
+    for t in ids:
+        if not 0 <= t < VOCAB_BITS:
+            raise ValueError(f"allowed_tokens: token id {t} is outside [0, {VOCAB_BITS})")
+        mask[t] = True
+    return mask
+
+
+def seeded_distribution(logits: torch.Tensor, top_k: int, top_p: float, temperature: float, allowed=None):
+    """What a seeded draw is taken from.  logits [B, V] -> (order [B, V] int64, cdf [B, V] fp64, n_kept [B]):
+    `order` lists each row's tokens by descending (masked) logit, ties by ascending token id; the kept tokens are its
+    first `n_kept`; `cdf` is the inclusive cumulative softmax of the kept tokens in that order (1 beyond them).
+
+    The kept set is the one the filters above keep -- they are called here, on the fp64 rows.  One thing they leave
+    open is pinned: when the top-p cut falls inside a group of EQUAL logits, which members go depends on the tie
+    order of a non-stable `torch.sort`; here (and in the kernel) the group loses its highest token ids first, i.e. the
+    cut is taken in the exact reverse of `order`.  The number of tokens kept of every value is the filters' own."""
+    raw = logits.detach().to("cpu", torch.float64)
+    if raw.dim() != 2:
+        raise ValueError("logits must be [B, V]")
+    if allowed is not None:
+        raw = raw.masked_fill(~torch.as_tensor(allowed, dtype=torch.bool)[None, :], float("-inf"))
+    order = torch.sort(raw, dim=-1, descending=True, stable=True)[1]
+    col = torch.arange(raw.shape[1])[None, :]
+    if top_k == 1:                                                    # greedy: no filter, no temperature
+        n_kept = torch.ones(raw.shape[0], dtype=torch.long)
+        xs = raw
+    else:
+        x = raw.clone()
+        if top_p > 0.0:
+            assert top_p <= 1.0, "top-p should be in (0, 1]."
+        if top_k > 0:
+            modify_logits_for_top_k_filtering(x, min(top_k, x.size(-1)))
+        if temperature != 1.0 and temperature > 0.0:
+            x /= temperature
+        modify_logits_for_top_p_filtering(x, top_p)
+        n_kept = (x > float("-inf")).sum(-1)
+        xs = raw / temperature if (temperature != 1.0 and temperature > 0.0) else raw
+    xs = xs.gather(-1, order).masked_fill(col >= n_kept[:, None], float("-inf"))
+    cdf = xs.softmax(-1).cumsum(-1)
+    cdf = torch.where(col >= (n_kept[:, None] - 1), torch.ones_like(cdf), cdf)
+    return order, cdf, n_kept
+
+
+def sample_seeded(logits: torch.Tensor, top_k: int, top_p: float, temperature: float, seed: int, stream, count,
+                  allowed=None) -> torch.Tensor:
+    """[B, V] (or [V]) logits -> [B] (or scalar) int64 token ids: the filters of `sample`, then ONE draw per row by
+    inverting the CDF of the kept tokens taken in descending-logit order, ties by ascending token id -- the first
+    position whose inclusive CDF exceeds u = seeded_uniform(seed, stream[b], count[b]).  top_k == 1 is the arg-max
+    (lowest id on ties).  `stream` / `count`: an int for every row or one per row.  `allowed`: bool mask [V] or None."""
+    import numpy as np
+    single = logits.dim() == 1
+    lg = logits[None] if single else logits
+    order, cdf, n_kept = seeded_distribution(lg, top_k, top_p, temperature, allowed)
+    B = lg.shape[0]
+    st = np.broadcast_to(np.asarray(stream, dtype=np.int64), (B,))
+    ct = np.broadcast_to(np.asarray(count, dtype=np.int64), (B,))
+    u = torch.from_numpy(np.ascontiguousarray(seeded_uniform(seed, st, ct)))
+    pos = (cdf <= u[:, None]).sum(-1).clamp_(max=lg.shape[1] - 1)
+    pos = torch.minimum(pos, n_kept - 1) if top_k != 1 else torch.zeros_like(pos)
+    tok = order.gather(-1, pos[:, None])[:, 0]
+    return tok[0] if single else tok

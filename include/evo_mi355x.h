@@ -50,7 +50,7 @@ extern "C" {
  *      takes up to 64 rows and an optional workspace (`ws`, `ws_bytes`: split over K across workgroups for the narrow layers); evo_hyena_ct gained `y_row_pitch` (rows of y between two batch rows: the scoring path runs the 512 k main tokens
  *      of every row through the operator and the one token behind them through the single-token launch, see below).
  *  11: evo_pool_rows_bf16 added (sequence embeddings: masked row pooling with the final RMSNorm optionally fused in); no signature changed. */
-#define EVO_ABI_VERSION 11
+#define EVO_ABI_VERSION 12
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -368,6 +368,30 @@ int evo_unembed_logprob_bf16(const void* hidden, const void* emb, const int64_t*
  * (x, ranges, ws, out), a bad D / ld / M, B < 1, n_strips out of range or an unknown mode. */
 int evo_pool_rows_bf16(const void* x, int64_t M, int64_t D, int64_t ld, const int64_t* ranges, int64_t B,
                        const void* scale, float eps, int64_t mode, int64_t n_strips, float* ws, float* out, void* stream);
+
+/* ---- seeded sampling: one token per row of [S, 512] logits, on the device -------------------------------------
+ * replaces stripedhyena.sample (topk / sort / softmax / cumsum / scatter / masked_fill_ / multinomial in eager torch, the logits
+ * and the sampled ids read back by the host every step)     [REF evo/generation.py:7,162-167; semantic_design/semantic_design.py:121-179]
+ * One launch, no host reads, no allocation: capturable in a hipGraph.  Written specification: evo_amd/sh/sample.py sample_seeded.
+ *   logits      [S, V = 512] bf16 (logits_f32 = 0) or f32 (logits_f32 = 1), row pitch `ld` elements (ld >= 512, ld % 8 == 0, 16-byte aligned)
+ *   top_k       [S] device int32: 1 = arg-max (lowest id on ties); > 1: keep logits >= the k-th largest (ties kept); <= 0: keep all
+ *   top_p       [S] device f32: with 0 < top_p < 1 drop, in ascending order, while the cumulative softmax is <= 1 - top_p
+ *   temperature [S] device f32: the kept logits are divided by it unless it is 1 or <= 0
+ *   allow       64 device bytes or NULL: bit j of byte b set = token 8 b + j may be drawn (others count as -inf); NULL = all
+ *   seed, stream_id [S] int64 (NULL: the row index), count [S] int64 (NULL: 0): the row's random number is word 0 of Philox4x32-10 with
+ *               key (seed low, seed high) and counter (stream low, stream high, count low, count high), u = ((x0 >> 8) + 0.5) 2^-24;
+ *               the token is the first one, by descending logit and ascending id, whose inclusive CDF over the kept set exceeds u
+ *   active      [S] device bytes or NULL: a row whose byte is 0 writes nothing and does not advance
+ *   ids_out     [S] int64;  logprob_out [S] f32: log-probability of the token under the fp32 log-softmax of the UNFILTERED row
+ *   hist_ids    [S, hist_len] int64 or NULL, hist_logits [S, hist_len, 512] f32 or NULL (16-byte aligned): with 0 <= count[s] < hist_len,
+ *               hist_ids[s, count[s]] = token and hist_logits[s, count[s], :] = the row in f32 (outside that range nothing is recorded)
+ *   then count[s] += 1 (when count is given).
+ * fp32 sums in a fixed order, no float atomics: bit-identical from run to run.  Returns -1 for a null logits / top_k / top_p /
+ * temperature / ids_out / logprob_out, S < 1, V != 512, a bad ld or alignment, or history without count or with hist_len < 1. */
+int evo_sample_rows_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,
+                        const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
+                        const uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
+                        int64_t hist_len, int64_t S, int64_t V, void* stream);
 
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:

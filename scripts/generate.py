@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--verbose", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: sample i draws from its own random stream i")
+    ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
     args = ap.parse_args()
 
     import evo_amd
@@ -38,7 +40,8 @@ def main():
     seqs, scores = evo_amd.generate([args.prompt] * args.n_samples, m.model, m.tokenizer, n_tokens=args.n_tokens,
                                     temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                     cached_generation=args.cached_generation, batched=args.batched,
-                                    prepend_bos=args.prepend_bos, device=args.device, verbose=args.verbose)
+                                    prepend_bos=args.prepend_bos, device=args.device, verbose=args.verbose, seed=args.seed,
+                                    allowed_tokens=args.allowed_tokens)
     print("Generated sequences:")
     for s in seqs:
         print(s)

@@ -38,6 +38,9 @@ def main(argv=None):
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--n-slots", type=int, default=16, help="decode streams advanced together per step")
     ap.add_argument("--prepend-bos", action="store_true")
+    ap.add_argument("--seed", type=int, default=None, help="reproducible run (for a fixed --n-slots): every sample draws from its own "
+                                                           "random stream; the sampler then runs on the device")
+    ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -49,7 +52,7 @@ def main(argv=None):
         raise SystemExit(f"no prompts in {args.prompts}")
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
-                      temperature=args.temperature, device=args.device)
+                      temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens)
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
                                         prepend_bos=args.prepend_bos)
     rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] for s, sc, o in zip(seqs, scores, owner)
