@@ -207,6 +207,20 @@ class HipOps:
         return self.timer.span(name) if self.timer is not None else _NOSPAN
 
     # ---- plumbing -------------------------------------------------------------------------------
+    PTR_ALIGN = 16      # bytes: the alignment include/evo_mi355x.h ("Conventions") asks of bf16 / f32 / c64 tensor data (16-byte vector loads / stores)
+
+    @staticmethod
+    def _align_of(dtype) -> int:
+        """Bytes of alignment the header asks of an operand of this dtype: 16 for floating-point data, the element's own size for the
+        integer vectors (ids, targets, positions, ranges: read one element at a time -- the model passes slices such as ids[b0:b0 + nb])."""
+        return HipOps.PTR_ALIGN if (dtype.is_floating_point or dtype.is_complex) else torch.empty(0, dtype=dtype).element_size()
+
+    @staticmethod
+    def _check_address(addr: int, what: str, align: int = 16) -> None:
+        """Raises when a device address breaks the header's alignment rule: a misaligned view fails here instead of reaching a kernel."""
+        if addr % align:
+            raise RuntimeError(f"{what}: address 0x{addr:x} is not {align}-byte aligned (include/evo_mi355x.h, Conventions)")
+
     @staticmethod
     def _need(t: torch.Tensor, dtype, what: str):
         if not t.is_cuda:
@@ -215,6 +229,7 @@ class HipOps:
             raise RuntimeError(f"{what}: expected {dtype}, got {t.dtype}")
         if not t.is_contiguous():
             raise RuntimeError(f"{what}: tensor must be contiguous")
+        HipOps._check_address(t.data_ptr(), what, HipOps._align_of(dtype))
 
     # ---- dense layers (hipBLASLt via torch) --------------------------------------------------------
     @staticmethod
@@ -848,8 +863,10 @@ class HipOps:
         B, T, three, H, hd = qkv.shape
         if T != 1 or three != 3 or kv.dtype != torch.bfloat16 or not kv.is_cuda or kv.stride(-1) != 1 or kv.shape[0] < B:
             raise RuntimeError("rope_append_decode: expects qkv [B,1,3,H,hd] and a bf16 KV cache [>=B,cap,2,H,hd]")
+        self._check_address(kv.data_ptr(), "rope_append_decode kv")
         if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() != B or not pos.is_contiguous():
             raise RuntimeError("rope_append_decode pos: need a contiguous device int64 tensor with B entries")
+        self._check_address(pos.data_ptr(), "rope_append_decode pos", 8)
         self._need(inv_freq, torch.float32, "rope_append_decode inv_freq")
         _check(self.lib.evo_rope_append_decode_bf16(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(),
                                                     float(scaling), B, H, hd, kv.stride(0), kv.stride(1), kv.stride(2),
@@ -861,6 +878,7 @@ class HipOps:
         for t, nm in ((q, "q"), (k, "k"), (v, "v")):
             if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
                 raise RuntimeError(f"attention {nm}: need a ROCm bf16 tensor with a dense last dim")
+            self._check_address(t.data_ptr(), f"attention {nm}")
         B, Tq, H, hd = q.shape
         Tk = k.shape[1]
         if hd != 128:
@@ -885,11 +903,13 @@ class HipOps:
             if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() not in (1, B):
                 raise RuntimeError("attention_decode pos: need a device int64 tensor with 1 or B entries")
             pos = (pos.reshape(1).expand(B) if pos.numel() == 1 and B > 1 else pos.reshape(-1)).contiguous()
+            self._check_address(pos.data_ptr(), "attention_decode pos", 8)
         if Tq != 1 or hd != 128:
             raise RuntimeError("attention_decode: expects [B,1,H,128] queries")
         for t, nm in ((q, "q"), (k, "k"), (v, "v")):
             if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
                 raise RuntimeError(f"attention_decode {nm}: need a ROCm bf16 tensor with a dense last dim")
+            self._check_address(t.data_ptr(), f"attention_decode {nm}")
         Tk = k.shape[1]
         if n_splits is None:                     # one split per WAVE of the streaming kernel, whole workgroups of four, at most
             # one per 64-key block.  Measured on MI355X (tools/experiments/attn_decode_bench.py, round 6: the kernel keeps the next 32-key
@@ -1061,8 +1081,9 @@ class HipOps:
         `scale` -- of the RMSNorm of its rows (scale * x / (rms(x) + eps), in fp32, no bf16 rounding)."""
         if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
             raise RuntimeError("pool_rows: x must be a [M, D] bf16 device matrix with unit column stride")
-        if x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(0) < x.shape[1]:
-            raise RuntimeError("pool_rows: x must be 16-byte aligned with a row stride >= D, a multiple of 8")
+        self._check_address(x.data_ptr(), "pool_rows x")
+        if x.stride(0) % 8 or x.stride(0) < x.shape[1]:
+            raise RuntimeError("pool_rows: x must have a row stride >= D that is a multiple of 8")
         if mode not in self.POOL_MODES:
             raise ValueError(f"pool_rows: mode must be one of {tuple(self.POOL_MODES)}, got {mode!r}")
         if scale is not None:
@@ -1071,6 +1092,7 @@ class HipOps:
         M, D = x.shape
         if isinstance(ranges, torch.Tensor):
             rg = ranges.to(device=x.device, dtype=torch.int64).reshape(-1, 2).contiguous()
+            self._check_address(rg.data_ptr(), "pool_rows ranges", 8)
             longest = M
         else:
             pairs = [(int(a), int(n)) for a, n in ranges]

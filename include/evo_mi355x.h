@@ -13,7 +13,19 @@
  *   - no allocation, no host sync, no global state: safe to capture in a hipGraph; workspace is
  *     passed in by the caller;
  *   - return value is a hipError_t cast to int (0 = hipSuccess); -1 = bad argument.  The Python
- *     binding raises on non-zero.
+ *     binding raises on non-zero;
+ *   - alignment: every pointer to bf16 / f32 / c64 tensor data (activations, weights, states, tables, workspaces) is
+ *     16-byte aligned unless a function says otherwise (the kernels load and store 16 bytes per lane), and NO MORE
+ *     is ever needed: a row slice of a bf16 matrix whose rows are whole multiples of 16 bytes, one third of a
+ *     packed qkv, a block of z^T are all legal operands.  Integer vectors (ids, target, pos / dyn_pos, ranges,
+ *     mask, bad_flag) are read one element at a time and need only that element's own alignment -- the callers
+ *     pass row slices of int64 id matrices; so do the per-row vectors of evo_sample_rows_f32 (see there).  The
+ *     binding checks the addresses it passes (HipOps._check_address);
+ *   - extents: a launch reads and writes nothing outside the extents its arguments describe -- no load and no
+ *     store before the first or behind the last element of an operand (a ragged last tile is masked, not
+ *     clamped into a neighbour), workspaces included; operands passed as const are never written.  Elements
+ *     INSIDE an extent that a function calls pad / scratch / "may hold anything" may be read and, where the
+ *     function says so, written.  tests/test_gpu_arena.py runs every entry point between poisoned guard bands.
  */
 #ifndef EVO_MI355X_H
 #define EVO_MI355X_H
@@ -386,6 +398,9 @@ int evo_pool_rows_bf16(const void* x, int64_t M, int64_t D, int64_t ld, const in
  *   hist_ids    [S, hist_len] int64 or NULL, hist_logits [S, hist_len, 512] f32 or NULL (16-byte aligned): with 0 <= count[s] < hist_len,
  *               hist_ids[s, count[s]] = token and hist_logits[s, count[s], :] = the row in f32 (outside that range nothing is recorded)
  *   then count[s] += 1 (when count is given).
+ *   Alignment: logits and hist_logits 16 bytes (above); the per-row vectors (top_k, top_p, temperature, stream_id, count, active,
+ *   ids_out, logprob_out, hist_ids) are read and written one element per row and need only that element's own alignment -- the
+ *   decode pool samples ONE slot by passing one-element slices of its per-slot vectors.
  * fp32 sums in a fixed order, no float atomics: bit-identical from run to run.  Returns -1 for a null logits / top_k / top_p /
  * temperature / ids_out / logprob_out, S < 1, V != 512, a bad ld or alignment, or history without count or with hist_len < 1. */
 int evo_sample_rows_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,

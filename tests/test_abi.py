@@ -74,6 +74,25 @@ def test_argument_validation_needs_no_gpu():
     assert lib.evo_attn_fwd_causal_bf16(None, None, None, None, 1, 1, 4, 4, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1.0, None, None) == -1
 
 
+def test_binding_refuses_misaligned_addresses():
+    """include/evo_mi355x.h, Conventions: bf16 / f32 / c64 data 16-byte aligned and no more, integer vectors at their element's alignment.  HipOps._need and the hand-rolled checks of
+    attention / attention_decode / rope_append_decode / pool_rows go through this one helper, which takes an address: no GPU needed."""
+    chk = evo_ops.HipOps._check_address
+    for addr in (0, 16, 0x7f0000000010, 0x7f0000000200, 48):                                    # 16 (mod 32) is legal: nothing more is asked
+        chk(addr, "x")
+    for addr in (8, 2, 0x7f0000000008, 0x7f0000000204, 17):
+        with pytest.raises(RuntimeError, match="not 16-byte aligned"):
+            chk(addr, "x")
+    with pytest.raises(RuntimeError, match="rmsnorm x: address 0x40 is not 128-byte aligned"):
+        chk(64, "rmsnorm x", align=128)
+    assert evo_ops.HipOps.PTR_ALIGN == 16
+    al = evo_ops.HipOps._align_of                                                                # floating-point data: 16; integer vectors: the element
+    assert [al(d) for d in (torch.bfloat16, torch.float32, torch.complex64, torch.int64, torch.int32, torch.uint8)] == [16, 16, 16, 8, 4, 1]
+    import inspect
+    for name in ("_need", "attention", "attention_decode", "rope_append_decode", "pool_rows"):   # the check is wired into every place the issue names
+        assert "_check_address(" in inspect.getsource(getattr(evo_ops.HipOps, name)), name
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")
 def test_no_cpu_fallback():
     from evo_amd.sh.model import StripedHyena

@@ -117,7 +117,8 @@ def test_logprob_entropy(ops, dtype):
     assert lp[3].item() == 0.0
 
 
-@pytest.mark.parametrize("M,K", [(1, 256), (63, 4096), (64, 4096), (513, 4096), (8193, 4096)])
+@pytest.mark.parametrize("M,K", [(1, 256), (63, 4096), (64, 4096), (513, 4096), (8193, 4096),
+                                 (70, 32), (70, 288)])       # (unembed_logprob_ok admits any K % 32 == 0: one k-step, and K % 256 != 0)
 def test_fused_unembed_logprob_matches_two_kernel_path_and_oracle(ops, M, K):
     """evo_unembed_logprob_bf16 (unembed + log-softmax + gather + entropy in one kernel, logits never in HBM) vs
     (a) the fp64 oracle on bf16-rounded logits and (b) the two-kernel path it replaces [REF evo/scoring.py:47-57]."""
