@@ -376,6 +376,22 @@ def _attn(ops, q, k, v, off, pre):
     return ops.attention(qp.to(DEV), k.to(DEV), v.to(DEV), off, prescaled=True), R.op_attention(qp.double() / c, k, v, off)
 
 
+def _attn_routed(ops, w64, q, k, v, off, pre):
+    """_attn with the prefill routing chosen: `ops.attn_w64` True = the 64-rows-per-wave kernel (csrc/attn_w64.hip, the default for query
+    ranges > 128), False = the 8-wave pipelined kernel (attn_fwd_pipe_kernel, csrc/attn.hip)."""
+    was = ops.attn_w64
+    ops.attn_w64 = w64
+    try:
+        return _attn(ops, q, k, v, off, pre)
+    finally:
+        ops.attn_w64 = was
+
+
+def _with_routing(values):
+    """Parameter sets (value, w64): the ids of the default routing stay what they were, the 8-wave kernel's cases are `<id>-pipe`."""
+    return [pytest.param(v, w64, id=f"{v}" + ("" if w64 else "-pipe")) for w64 in (True, False) for v in values]
+
+
 @pytest.mark.parametrize("pre", [False, True])
 @pytest.mark.parametrize("B,H,Tq,Tk,off", [
     (2, 2, 37, 37, 0),            # one ragged tile
@@ -406,8 +422,8 @@ def test_attention_packed_qkv_views_and_kv_cache_layout(ops):
     assert torch.equal(o2, o)
 
 
-@pytest.mark.parametrize("pre", [False, True])
-def test_attention_outlier_scores(ops, pre):
+@pytest.mark.parametrize("pre,w64", _with_routing([False, True]))
+def test_attention_outlier_scores(ops, pre, w64):
     """Large score outliers late in the key range force big running-max jumps (the rescale path)."""
     B, H, T = 1, 1, 384
     q = bf(torch.randn(B, T, H, 128, generator=gen(24)))
@@ -415,12 +431,12 @@ def test_attention_outlier_scores(ops, pre):
     v = bf(torch.randn(B, T, H, 128, generator=gen(26)))
     k[0, 200, 0] = q[0, 300, 0] * 3       # key 200 dominates query 300 (and nearby rows see a huge score)
     k[0, 70, 0] = q[0, 90, 0] * 2
-    o, ref = _attn(ops, q, k, v, 0, pre)
+    o, ref = _attn_routed(ops, w64, q, k, v, 0, pre)
     assert_close_bf16(o, ref, rl2=4e-3, atol=2e-2)
 
 
-@pytest.mark.parametrize("pre", [False, True])
-def test_attention_reference_point_moves_several_times_in_one_row(ops, pre):
+@pytest.mark.parametrize("pre,w64", _with_routing([False, True]))
+def test_attention_reference_point_moves_several_times_in_one_row(ops, pre, w64):
     """The 64-rows-per-wave kernel keeps a row's reference point until a tile's largest exponent exceeds it by W_THR = 32 log2 units
     (csrc/attn_w64.hip); a staircase of spikes 1.5 x, 3 x, 5 x, 8 x |q|^2 (steps of 24-49 units, one per key tile and later) walks the
     rescale path four times in the same row, a -5 x spike on the row's FIRST key starts it 81 units below, and the neighbours in the
@@ -434,14 +450,14 @@ def test_attention_reference_point_moves_several_times_in_one_row(ops, pre):
         k[0, key, 0] = q[0, 850, 0] * mul
     k[0, 0, 1] = q[0, 640, 1] * -5.0
     k[0, 600, 1] = q[0, 640, 1] * 4.0
-    o, ref = _attn(ops, q, k, v, 0, pre)
+    o, ref = _attn_routed(ops, w64, q, k, v, 0, pre)
     assert_close_bf16(o, ref, rl2=4e-3, atol=2e-2)
     assert_close_bf16(o[:, 850], ref[:, 850], rl2=4e-3, atol=2e-2)                  # the staircase row itself
     assert_close_bf16(o[:, 640], ref[:, 640], rl2=4e-3, atol=2e-2)
 
 
-@pytest.mark.parametrize("pre", [False, True])
-def test_attention_wide_scores_like_the_models_block_8(ops, pre):
+@pytest.mark.parametrize("pre,w64", _with_routing([False, True]))
+def test_attention_wide_scores_like_the_models_block_8(ops, pre, w64):
     """Scores with a standard deviation of ~9 log2 units (q, k of rms 2.5: what the synthetic 7B model hands block 8,
     tools/attn_instep_ab.py --model): softmax rows are dominated by a handful of keys, the running maximum climbs ~20 units along a
     row.  Every output row against the fp64 oracle."""
@@ -449,12 +465,12 @@ def test_attention_wide_scores_like_the_models_block_8(ops, pre):
     q = bf(torch.randn(B, T, H, 128, generator=gen(127)) * 2.5)
     k = bf(torch.randn(B, T, H, 128, generator=gen(128)) * 2.5)
     v = bf(torch.randn(B, T, H, 128, generator=gen(129)))
-    o, ref = _attn(ops, q, k, v, 0, pre)
+    o, ref = _attn_routed(ops, w64, q, k, v, 0, pre)
     assert_close_bf16(o, ref, rl2=4e-3, atol=2e-2)
 
 
-@pytest.mark.parametrize("shift", [-5.0, -1.2, 3.5])
-def test_attention_prescaled_reference_point_leaves_zero_on_the_first_tile(ops, shift):
+@pytest.mark.parametrize("shift,w64", _with_routing([-5.0, -1.2, 3.5]))
+def test_attention_prescaled_reference_point_leaves_zero_on_the_first_tile(ops, shift, w64):
     """PRE form only: every score of a head sits `shift` x |u|^2 (x softmax_scale log2 e: -81 / -19.6 / +57 log2 units) away from 0 -- all
     queries ~ u, all keys ~ shift u.  At -81 a row's FIRST visible tile pulls its reference point down (nothing accumulated yet: no
     rescale); at -19.6 and +57 the reference stays at 0 and P = 2^s runs at 2^-20 / 2^57 through the bf16 P and the fp32 sums."""
@@ -464,7 +480,7 @@ def test_attention_prescaled_reference_point_leaves_zero_on_the_first_tile(ops, 
     q = bf(u[None, None, None, :] + 0.05 * torch.randn(B, T, H, 128, generator=gen(131)))
     k = bf(shift * u[None, None, None, :] + 0.3 * torch.randn(B, T, H, 128, generator=gen(132)))
     v = bf(torch.randn(B, T, H, 128, generator=gen(133)))
-    o, ref = _attn(ops, q, k, v, 0, True)
+    o, ref = _attn_routed(ops, w64, q, k, v, 0, True)
     assert torch.isfinite(o.float()).all()
     assert_close_bf16(o, ref, rl2=4e-3, atol=2e-2)
 
