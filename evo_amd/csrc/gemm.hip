@@ -928,58 +928,82 @@ extern "C" int evo_linear_mfma_bf16(const void* x, const void* w, const void* bi
     return evo_linear_mfma_nf_bf16(x, w, bias, residual, y, nullptr, nullptr, 0, M, N, K, stream);
 }
 
+// ---- host side: one CU count, one GemmArgs fill, one dispatch over the persistent kernel's template parameters ----------------------------------
+
+// workgroups of a persistent launch: one per CU, a whole number per XCD
+static int persistent_cu_count() {
+    static const int n_cu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        n &= ~7;
+        return n < 8 ? 8 : n;
+    }();
+    return n_cu;
+}
+
+// what the persistent kernel asks beyond whole tiles: two k steps for its pipeline, both operands below 4 GiB (32-bit DMA offsets)
+static bool persistent_shape_ok(int64_t M, int64_t N, int64_t K) {
+    return K >= 2 * GBK && M * K * 2 < 0xffffffffll && N * K * 2 < 0xffffffffll;
+}
+
+// GemmArgs of y [M, N] = x [M, K] . w [N, K]^T (+ bias) (+ res): operands, tile counts, raster width.  false: N or the tile count leaves 31 bits.
+// Raster width: the ~32 tiles an XCD runs at once cover group_m X panels x 32 / group_m W panels.  Measured on the four layer
+// shapes at M = 65,536 (tools/gemm_ab.py lib.so@G): N = 12,288 / 22,016: 8 is best (98.1 / 98.2 % of hipBLASLt against 97.6 /
+// 96.6 at 4, 88 at 16, 60 at 32); N = 4,096 (16 column tiles): 1-4 tie, 8 loses 1.5-2.5 %.  `raster_by_m` (MODE 3, operands swapped:
+// group_m counts column tiles per raster group there, see tile_origin): the rule looks at the row tiles instead.
+static bool gemm_fill(GemmArgs& a, const void* x, const void* w, const void* bias, const void* res, void* y, int64_t M, int64_t N, int64_t K,
+                      bool raster_by_m = false) {
+    if (N > 0x7fffffff / 2) return false;
+    a.x = (const unsigned char*)x; a.w = (const unsigned char*)w; a.bias = (const uint16_t*)bias;
+    a.res = (const uint16_t*)res; a.y = (uint16_t*)y;
+    a.M = M; a.N = (int)N; a.K = (int)K;
+    const int64_t tiles_m = (M + GBM - 1) / GBM, tiles_n = N / GBN;
+    if (tiles_m * tiles_n > 0x7fffffff) return false;
+    a.tiles_m = (int)tiles_m; a.tiles_n = (int)tiles_n; a.n_tiles = (int)(tiles_m * tiles_n);
+    a.group_m = (raster_by_m ? tiles_m : tiles_n) >= 32 ? 8 : 4;
+    return true;
+}
+
+template <bool BIAS, bool RES, int MODE, bool XB, int NF>
+static int launch_persistent_as(const GemmArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((gemmr_bf16_kernel<BIAS, RES, MODE, XB, NF>), dim3((unsigned)persistent_cu_count()), dim3(256), 0, st, a);
+    return evo_launch_status();
+}
+
+template <bool BIAS, int MODE, bool XB, int NF>
+static int launch_persistent_res(const GemmArgs& a, hipStream_t st) {
+    if constexpr (NF == 1) return launch_persistent_as<BIAS, true, MODE, XB, NF>(a, st);       // STATS: the layer that writes the stream adds into it
+    else if constexpr (MODE == 0 && NF == 0)
+        return a.res ? launch_persistent_as<BIAS, true, MODE, XB, NF>(a, st) : launch_persistent_as<BIAS, false, MODE, XB, NF>(a, st);
+    else return launch_persistent_as<BIAS, false, MODE, XB, NF>(a, st);                        // SCALE, gated, transposed: no residual
+}
+
+// The persistent kernel for <MODE, XB, NF>, its BIAS / RES parameters from a.bias / a.res (the gated layer, MODE 1, has no bias)
+template <int MODE, bool XB, int NF>
+static int launch_persistent(const GemmArgs& a, void* stream) {
+    if constexpr (MODE != 1)
+        if (a.bias) return launch_persistent_res<true, MODE, XB, NF>(a, (hipStream_t)stream);
+    return launch_persistent_res<false, MODE, XB, NF>(a, (hipStream_t)stream);
+}
+
 // The same dense layer with the RMSNorm around it folded in (gemmr_bf16_kernel, NF): `row_scale` [ceil(M / 256) * 256] fp32 multiplies the
 // accumulators of row m before the bias (the consumer of a normalised stream: w is then W diag(g), no residual); `sumsq`
 // [N / 128][ss_ld] fp32 (ss_ld >= ceil(M / 256) * 256) receives the sums of squares of the stored rows per 128-column strip (the
 // producer of the stream: residual required).  Both need the persistent form's shape contract (K >= 128, operands < 4 GiB).
 extern "C" int evo_linear_mfma_nf_bf16(const void* x, const void* w, const void* bias, const void* residual, void* y,
                                        const float* row_scale, float* sumsq, int64_t ss_ld, int64_t M, int64_t N, int64_t K, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0 || N > 0x7fffffff / 2) return -1;
+    if (M <= 0 || N <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0) return -1;
     if ((row_scale && (residual || sumsq)) || (sumsq && (!residual || ss_ld < (M + GBM - 1) / GBM * GBM))) return -1;
-    if ((row_scale || sumsq) && !(K >= 2 * GBK && M * K * 2 < 0xffffffffll && N * K * 2 < 0xffffffffll)) return -1;
-    GemmArgs a;
-    a.rs = row_scale; a.ss = sumsq; a.ss_ld = ss_ld;
-    a.x = (const unsigned char*)x; a.w = (const unsigned char*)w; a.bias = (const uint16_t*)bias;
-    a.res = (const uint16_t*)residual; a.y = (uint16_t*)y;
-    a.M = M; a.N = (int)N; a.K = (int)K;
-    a.tiles_n = (int)(N / GBN);
-    a.tiles_m = (int)((M + GBM - 1) / GBM);
-    // raster width: the ~32 tiles an XCD runs at once cover group_m X panels x 32 / group_m W panels.  Measured on the four layer
-    // shapes at M = 65,536 (tools/gemm_ab.py lib.so@G): N = 12,288 / 22,016: 8 is best (98.1 / 98.2 % of hipBLASLt against 97.6 /
-    // 96.6 at 4, 88 at 16, 60 at 32); N = 4,096 (16 column tiles): 1-4 tie, 8 loses 1.5-2.5 %.
-    const int group_m = (a.tiles_n >= 32 ? 8 : 4);
-    a.group_m = group_m;
-    const int64_t tiles = ((M + GBM - 1) / GBM) * a.tiles_n;
-    if (tiles > 0x7fffffff) return -1;
-    a.n_tiles = (int)tiles;
-    const dim3 grid((unsigned)tiles), block(512);
-    hipStream_t st = (hipStream_t)stream;
     static const int form = [] { const char* e = getenv("EVO_GEMM_FORM"); return e ? atoi(e) : 1; }();   // 1: persistent, 0: tile per workgroup
-    if ((row_scale || sumsq) && form != 1) return -1;           // the folded norm exists in the persistent kernel only: never fall through to a launch that ignores it
-    if (form == 1 && K >= 2 * GBK && M * K * 2 < 0xffffffffll && N * K * 2 < 0xffffffffll) {
-        static const int n_cu = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            n &= ~7;
-            return n < 8 ? 8 : n;
-        }();
-        const dim3 gridp((unsigned)n_cu), block4(256);
-        if (row_scale) {
-            if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, false, 0, false, 2>), gridp, block4, 0, st, a);
-            else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 0, false, 2>), gridp, block4, 0, st, a);
-            return evo_launch_status();
-        }
-        if (sumsq) {
-            if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, true, 0, false, 1>), gridp, block4, 0, st, a);
-            else hipLaunchKernelGGL((gemmr_bf16_kernel<false, true, 0, false, 1>), gridp, block4, 0, st, a);
-            return evo_launch_status();
-        }
-        if (bias && residual) hipLaunchKernelGGL((gemmr_bf16_kernel<true, true, 0>), gridp, block4, 0, st, a);
-        else if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, false, 0>), gridp, block4, 0, st, a);
-        else if (residual) hipLaunchKernelGGL((gemmr_bf16_kernel<false, true, 0>), gridp, block4, 0, st, a);
-        else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 0>), gridp, block4, 0, st, a);
-        return evo_launch_status();
-    }
+    const bool persistent = form == 1 && persistent_shape_ok(M, N, K);
+    if ((row_scale || sumsq) && !persistent) return -1;         // the folded norm exists in the persistent kernel only: never fall through to a launch that ignores it
+    GemmArgs a;
+    if (!gemm_fill(a, x, w, bias, residual, y, M, N, K)) return -1;
+    a.rs = row_scale; a.ss = sumsq; a.ss_ld = ss_ld;
+    if (persistent) return row_scale ? launch_persistent<0, false, 2>(a, stream) : sumsq ? launch_persistent<0, false, 1>(a, stream)
+                                                                                         : launch_persistent<0, false, 0>(a, stream);
+    const dim3 grid((unsigned)a.n_tiles), block(512);
+    hipStream_t st = (hipStream_t)stream;
     if (bias && residual) hipLaunchKernelGGL((gemm_bf16_kernel<true, true>), grid, block, 0, st, a);
     else if (bias) hipLaunchKernelGGL((gemm_bf16_kernel<true, false>), grid, block, 0, st, a);
     else if (residual) hipLaunchKernelGGL((gemm_bf16_kernel<false, true>), grid, block, 0, st, a);
@@ -999,36 +1023,11 @@ extern "C" int evo_linear_xblk_mfma_bf16(const void* x_blk, const void* w, const
 extern "C" int evo_linear_xblk_mfma_nf_bf16(const void* x_blk, const void* w, const void* bias, const void* residual, void* y,
                                             float* sumsq, int64_t ss_ld, int64_t M, int64_t N, int64_t K, void* stream) {
     if (sumsq && (!residual || ss_ld < M)) return -1;
-    if (M <= 0 || M % GBM != 0 || N <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0 || K < 2 * GBK || N > 0x7fffffff / 2) return -1;
-    if (M * K * 2 >= 0xffffffffll || N * K * 2 >= 0xffffffffll) return -1;
+    if (M <= 0 || M % GBM != 0 || N <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0 || !persistent_shape_ok(M, N, K)) return -1;
     GemmArgs a;
-    a.x = (const unsigned char*)x_blk; a.w = (const unsigned char*)w; a.bias = (const uint16_t*)bias;
-    a.res = (const uint16_t*)residual; a.y = (uint16_t*)y;
+    if (!gemm_fill(a, x_blk, w, bias, residual, y, M, N, K)) return -1;
     a.ss = sumsq; a.ss_ld = ss_ld;
-    a.M = M; a.N = (int)N; a.K = (int)K;
-    a.tiles_n = (int)(N / GBN);
-    a.tiles_m = (int)(M / GBM);
-    a.group_m = a.tiles_n >= 32 ? 8 : 4;
-    const int64_t tiles = (M / GBM) * a.tiles_n;
-    if (tiles > 0x7fffffff) return -1;
-    a.n_tiles = (int)tiles;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        n &= ~7;
-        return n < 8 ? 8 : n;
-    }();
-    const dim3 gridp((unsigned)n_cu), block4(256);
-    if (sumsq) {
-        if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, true, 0, true, 1>), gridp, block4, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((gemmr_bf16_kernel<false, true, 0, true, 1>), gridp, block4, 0, (hipStream_t)stream, a);
-        return evo_launch_status();
-    }
-    if (bias && residual) hipLaunchKernelGGL((gemmr_bf16_kernel<true, true, 0, true>), gridp, block4, 0, (hipStream_t)stream, a);
-    else if (residual) hipLaunchKernelGGL((gemmr_bf16_kernel<false, true, 0, true>), gridp, block4, 0, (hipStream_t)stream, a);
-    else if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, false, 0, true>), gridp, block4, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 0, true>), gridp, block4, 0, (hipStream_t)stream, a);
-    return evo_launch_status();
+    return sumsq ? launch_persistent<0, true, 1>(a, stream) : launch_persistent<0, true, 0>(a, stream);
 }
 
 // Gated MLP, first half: a[M, I] = gelu(x W1^T) * (x W2^T) in ONE launch of the persistent kernel -- the [M, 2 I] intermediate
@@ -1043,27 +1042,11 @@ extern "C" int evo_mlp_gate_mfma_bf16(const void* x, const void* w12g, void* a_o
 extern "C" int evo_mlp_gate_mfma_nf_bf16(const void* x, const float* row_scale, const void* w12g, void* a_out, int64_t M, int64_t I, int64_t K,
                                          void* stream) {
     const int64_t N = 2 * I;
-    if (M <= 0 || I <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0 || K < 2 * GBK || N > 0x7fffffff / 2) return -1;
-    if (M * K * 2 >= 0xffffffffll || N * K * 2 >= 0xffffffffll) return -1;
+    if (M <= 0 || I <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0 || !persistent_shape_ok(M, N, K)) return -1;
     GemmArgs a;
-    a.x = (const unsigned char*)x; a.w = (const unsigned char*)w12g; a.bias = nullptr; a.res = nullptr; a.y = (uint16_t*)a_out;
+    if (!gemm_fill(a, x, w12g, nullptr, nullptr, a_out, M, N, K)) return -1;
     a.rs = row_scale;
-    a.M = M; a.N = (int)N; a.K = (int)K;
-    a.tiles_n = (int)(N / GBN);
-    a.tiles_m = (int)((M + GBM - 1) / GBM);
-    a.group_m = (a.tiles_n >= 32 ? 8 : 4);
-    const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-    if (tiles > 0x7fffffff) return -1;
-    a.n_tiles = (int)tiles;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        n &= ~7;
-        return n < 8 ? 8 : n;
-    }();
-    if (row_scale) hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 1, false, 2>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 1>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-    return evo_launch_status();
+    return row_scale ? launch_persistent<1, false, 2>(a, stream) : launch_persistent<1, false, 0>(a, stream);
 }
 
 // z^T = (x [Mp, K] . w [N, K]^T + bias [N])^T, stored in blocks of 256 positions, zt [Mp / 256][N][256] (element (feature c, position p) at
@@ -1088,30 +1071,9 @@ extern "C" int evo_linear_t_mfma_nf_bf16(const void* x, const float* row_scale, 
         if (Tm <= 0 || Tm % GBN != 0 || Mp % Tm != 0 || row_skip < 0 || row_skip > 0x7fff || x_rows < Mp + (Mp / Tm - 1) * row_skip
             || x_rows * K * 2 >= 0xffffffffll) return -1;
     } else if (x_rows != Mp || Tm != Mp || row_skip != 0) return -1;
-    if (Mp <= 0 || N <= 0 || K <= 0 || Mp % GBN != 0 || N % GBM != 0 || K % GBK != 0 || K < 2 * GBK || Mp > 0x7fffffff / 2) return -1;
-    if (Mp * K * 2 >= 0xffffffffll || N * K * 2 >= 0xffffffffll) return -1;
+    if (Mp <= 0 || N <= 0 || K <= 0 || Mp % GBN != 0 || N % GBM != 0 || K % GBK != 0 || !persistent_shape_ok(Mp, N, K)) return -1;
     GemmArgs a;
-    a.x = (const unsigned char*)w; a.w = (const unsigned char*)x; a.bias = (const uint16_t*)bias; a.res = nullptr; a.y = (uint16_t*)zt;
-    a.M = N; a.N = (int)Mp; a.K = (int)K;
+    if (!gemm_fill(a, w, x, bias, nullptr, zt, N, Mp, K, true)) return -1;      // (operands swapped: the kernel's M = N, its N = Mp)
     a.rs = row_scale; a.w_rows = x_rows; a.tm_tiles = (int)(Tm / GBN); a.row_skip = (int)row_skip;
-    a.tiles_n = (int)(Mp / GBN);
-    a.tiles_m = (int)(N / GBM);
-    a.group_m = (a.tiles_m >= 32 ? 8 : 4);      // (column tiles per raster group: see tile_origin, MODE 3)
-    const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-    if (tiles > 0x7fffffff) return -1;
-    a.n_tiles = (int)tiles;
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        n &= ~7;
-        return n < 8 ? 8 : n;
-    }();
-    if (row_scale) {
-        if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, false, 3, false, 2>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 3, false, 2>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-        return evo_launch_status();
-    }
-    if (bias) hipLaunchKernelGGL((gemmr_bf16_kernel<true, false, 3>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemmr_bf16_kernel<false, false, 3>), dim3((unsigned)n_cu), dim3(256), 0, (hipStream_t)stream, a);
-    return evo_launch_status();
+    return row_scale ? launch_persistent<3, false, 2>(a, stream) : launch_persistent<3, false, 0>(a, stream);
 }

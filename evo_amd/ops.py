@@ -231,6 +231,50 @@ class HipOps:
             raise RuntimeError(f"{what}: tensor must be contiguous")
         HipOps._check_address(t.data_ptr(), what, HipOps._align_of(dtype))
 
+    def _launch(self, span: str, name: str, *args) -> None:
+        """One launch of entry point `name` on the current stream, under the timer span `span`."""
+        with self._t(span):
+            _check(getattr(self.lib, name)(*args, _stream()), name)
+
+    # ---- the dense layers' routing rules, each stated once ------------------------------------------
+    TILE_ROWS = 256         # rows per tile of the persistent dense layer (csrc/gemm.hip GBM)
+    SLIVER_ROWS = 16        # the most rows behind the last whole tile that count as a BOS sliver (the weight-streaming kernel's MFMA form: one m tile)
+    TAIL_ROWS_FROM = 4096   # _tail_rows peels a sliver from this many rows on (below, one more row of tiles costs less than a second launch)
+    DECODE_ROWS = 8         # batches this small take the fused single-token launches (csrc/gemv.hip; 5-8 rows at a width of 4096 only)
+
+    @staticmethod
+    def _bf16_ok(*tensors, scale=None) -> bool:
+        """Every tensor is a contiguous bf16 device tensor -- what the hand-written launches ask of an operand -- and `scale` (a norm's
+        scale vector), when given, contiguous bf16."""
+        return (all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in tensors)
+                and (scale is None or (scale.dtype == torch.bfloat16 and scale.is_contiguous())))
+
+    @staticmethod
+    def _gemm_shape_ok(M: int, N: int, K: int, persistent: bool = True) -> bool:
+        """The shape contract of csrc/gemm.hip for x [M, K] @ w [N, K]^T: whole 256-column tiles and 64-wide k steps; the PERSISTENT kernel
+        also wants two k steps for its pipeline and both operands below 4 GiB (32-bit DMA offsets; outputs are addressed per tile)."""
+        return (N % 256 == 0 and K % 64 == 0
+                and (not persistent or (K >= 128 and M * K * 2 < 0xffffffff and N * K * 2 < 0xffffffff)))
+
+    @staticmethod
+    def _sliver_rows(M: int, limit: int = SLIVER_ROWS, floor: int = 0) -> int:
+        """Rows of an M-row dense layer that go to the weight-streaming kernel: the 1 .. `limit` rows behind the last whole 256-row tile
+        (none when there are more, or fewer than `floor` rows in all)."""
+        r = M % HipOps.TILE_ROWS
+        return r if M >= floor and 1 <= r <= limit else 0
+
+    @staticmethod
+    def fused_rows_ok(M: int, K: int) -> bool:
+        """This many rows of width K fit the fused single-token launches (csrc/gemv.hip: norm + dense layer (+ gate / Hyena step) in one)."""
+        return 1 <= M <= 4 or (M <= HipOps.DECODE_ROWS and K == 4096)
+
+    def _main_then_sliver(self, M: int, r: int, main, sliver) -> None:
+        """The two launches of a dense layer of M rows whose last r are a sliver: `main(Mm)` for rows [0, Mm = M - r) -- whole tiles on the
+        persistent kernel --, then `sliver(Mm)` for the rows behind them (r = 0: no second launch).  Dense layers are row-independent."""
+        main(M - r)
+        if r:
+            sliver(M - r)
+
     # ---- dense layers (hipBLASLt via torch) --------------------------------------------------------
     @staticmethod
     def _tail_rows(x, w) -> int:
@@ -239,11 +283,7 @@ class HipOps:
         M = 65,544, +0.5 ... +3.7 % at 131,073).  Dense layers are row-independent, so the sliver goes through the
         weight-streaming kernel instead."""
         M, K = x.shape
-        r = M % 256
-        if M >= 4096 and 1 <= r <= 16 and K % 32 == 0 and x.is_cuda and x.dtype == torch.bfloat16 \
-                and w.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous():
-            return r
-        return 0
+        return HipOps._sliver_rows(M, floor=HipOps.TAIL_ROWS_FROM) if K % 32 == 0 and HipOps._bf16_ok(x, w) else 0
 
     def linear(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, mfma: bool = False) -> torch.Tensor:
         """x [M,K] @ w[N,K]^T (+ b) -> [M,N] bf16.  M <= 16 (decode) takes the weight-streaming kernels; `mfma=True`
@@ -251,34 +291,32 @@ class HipOps:
         (`attn_gemm_mfma` / `all_gemm_mfma` False route to hipBLASLt: bench.py's A/B legs)."""
         if self._use_small_m(x, w):
             return self._linear_small_m(x, w, b, None)
-        r = self._tail_rows(x, w)
-        if r:
-            M = x.shape[0]
-            y = torch.empty(M, w.shape[0], dtype=torch.bfloat16, device=x.device)
-            self._linear_into(y[: M - r], x[: M - r], w, b, mfma)
-            self._linear_small_m(x[M - r:], w, b, None, out=y[M - r:])
-            return y
-        if self._take_mfma(mfma) and self.mfma_linear_ok(x, w):
-            return self.linear_mfma(x, w, b)
-        with self._t("gemm"):
-            if b is not None:
-                return torch.addmm(b, x, w.t())
-            return torch.mm(x, w.t())
+        y = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+        self._linear_into(y, x, w, b, mfma)
+        return y
 
     def _take_mfma(self, mfma: bool) -> bool:
         return self.all_gemm_mfma or (mfma and self.attn_gemm_mfma)
 
-    def _linear_into(self, y, x, w, b, mfma):
-        if self._take_mfma(mfma) and self.mfma_linear_ok(x, w):
-            with self._t("gemm_mfma"):
-                _check(self.lib.evo_linear_mfma_bf16(x.data_ptr(), w.data_ptr(), _ptr(b), None, y.data_ptr(),
-                                                     x.shape[0], w.shape[0], x.shape[1], _stream()), "evo_linear_mfma_bf16")
-            return
-        with self._t("gemm"):
-            if b is not None:
-                torch.addmm(b, x, w.t(), out=y)
-            else:
-                torch.mm(x, w.t(), out=y)
+    def _linear_into(self, y, x, w, b, mfma, residual: bool = False) -> None:
+        """y = x @ w^T (+ b) (+ y itself with `residual`; fp32 accumulate, one rounding): the main rows on the persistent kernel when
+        routing and shape allow (hipBLASLt otherwise), the BOS sliver on the weight-streaming kernel."""
+        def main(Mm):
+            xm, ym = x[:Mm], y[:Mm]
+            if self._take_mfma(mfma) and self.mfma_linear_ok(xm, w) and ym.is_contiguous():
+                self.linear_mfma(xm, w, b, ym if residual else None, out=ym)     # (bias and residual in the dense layer's epilogue: one rounding)
+                return
+            with self._t("gemm"):
+                if residual:
+                    ym.addmm_(xm, w.t())
+                elif b is not None:
+                    torch.addmm(b, xm, w.t(), out=ym)
+                else:
+                    torch.mm(xm, w.t(), out=ym)
+            if residual and b is not None:
+                ym.add_(b)
+        self._main_then_sliver(x.shape[0], self._tail_rows(x, w) if y.is_contiguous() else 0, main,
+                               lambda Mm: self._linear_small_m(x[Mm:], w, b, y[Mm:] if residual else None, out=y[Mm:]))
 
     def linear_residual_(self, res: torch.Tensor, x: torch.Tensor, w: torch.Tensor, mfma: bool = False,
                          bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -286,17 +324,8 @@ class HipOps:
         weight-streaming kernel adds it in the same pass."""
         if self._use_small_m(x, w) and res.is_contiguous():
             return self._linear_small_m(x, w, bias, res)
-        r = self._tail_rows(x, w) if res.is_contiguous() else 0
-        if r:
-            M = x.shape[0]
-            self.linear_residual_(res[: M - r], x[: M - r], w, mfma, bias=bias)
-            self._linear_small_m(x[M - r:], w, bias, res[M - r:])
-            return res
-        if self._take_mfma(mfma) and self.mfma_linear_ok(x, w) and res.is_contiguous():
-            return self.linear_mfma(x, w, bias, res)          # (bias and residual in the dense layer's epilogue: one rounding)
-        with self._t("gemm"):
-            res.addmm_(x, w.t())
-        return res if bias is None else res.add_(bias)
+        self._linear_into(res, x, w, bias, mfma, residual=True)
+        return res
 
     @staticmethod
     def _use_small_m(x, w):
@@ -309,8 +338,7 @@ class HipOps:
             return False
         if K % 32 != 0 and not (M <= 4 or (M <= 8 and w.shape[0] <= 4096)):
             return False
-        return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous()
-                and w.is_contiguous() and K % 8 == 0)
+        return HipOps._bf16_ok(x, w) and K % 8 == 0
 
     def _linear_small_m(self, x, w, b, res, out=None):
         M, K = x.shape
@@ -318,29 +346,27 @@ class HipOps:
         y = res if res is not None else (out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device))
         # 17-64 rows on a narrow layer (N < 8192): a workspace for the partial sums of the split over K (csrc/gemv.hip skinny_nw_kernel SPLITK)
         ws = torch.empty(8 * M * N, dtype=torch.float32, device=x.device) if (M > 16 and N < 8192 and K % 256 == 0 and N % 64 == 0) else None
-        with self._t("gemv"):
-            _check(self.lib.evo_linear_small_m_bf16(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(),
-                                                    M, N, K, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()), "evo_linear_small_m_bf16")
+        self._launch("gemv", "evo_linear_small_m_bf16", x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(), M, N, K, _ptr(ws),
+                     0 if ws is None else ws.numel() * 4)
         return y
 
     @staticmethod
     def mfma_linear_ok(x, w):
-        return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous()
-                and w.is_contiguous() and w.shape[0] % 256 == 0 and x.shape[1] % 64 == 0 and x.shape[0] > 8)
+        # not the persistent contract: evo_linear_mfma_bf16 serves K = 64 and operands beyond 4 GiB with its tile-per-workgroup kernel
+        # (csrc/gemm.hip); 8 rows or fewer belong to the weight-streaming kernels whatever the operands
+        return HipOps._bf16_ok(x, w) and HipOps._gemm_shape_ok(x.shape[0], w.shape[0], x.shape[1], persistent=False) and x.shape[0] > 8
 
     def linear_mfma(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
-                    residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Hand-written MFMA dense layer (csrc/gemm.hip): x [M,K] @ w[N,K]^T (+ b) (+ residual, in place) -> [M,N]."""
+                    residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Hand-written MFMA dense layer (csrc/gemm.hip): x [M,K] @ w[N,K]^T (+ b) (+ residual, in place) -> [M,N] (`out`, when given)."""
         self._need(x, torch.bfloat16, "linear_mfma x")
         self._need(w, torch.bfloat16, "linear_mfma w")
         M, K = x.shape
         N = w.shape[0]
         if residual is not None:
             self._need(residual, torch.bfloat16, "linear_mfma residual")
-        y = residual if residual is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-        with self._t("gemm_mfma"):
-            _check(self.lib.evo_linear_mfma_bf16(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(residual), y.data_ptr(),
-                                                 M, N, K, _stream()), "evo_linear_mfma_bf16")
+        y = residual if residual is not None else (out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device))
+        self._launch("gemm_mfma", "evo_linear_mfma_bf16", x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(residual), y.data_ptr(), M, N, K)
         return y
 
     # ---- kernels -------------------------------------------------------------------------------------
@@ -413,8 +439,7 @@ class HipOps:
     def zt_shape_ok(self, B: int, T: int, N: int, K: int) -> bool:
         _, _, Mp, r = self.zt_layout(B, T)
         P = Mp + (256 if r else 0)
-        return (self.hyena_ct_flag and B * T >= 256 and N % 256 == 0 and N % 384 == 0 and K % 64 == 0 and K >= 128
-                and Mp * K * 2 < 0xffffffff and N * K * 2 < 0xffffffff and P * N * 2 < 0xfffffff0)
+        return self.hyena_ct_flag and B * T >= 256 and N % 384 == 0 and self._gemm_shape_ok(Mp, N, K) and P * N * 2 < 0xfffffff0
 
     def _xpad_buffer(self, B: int, T: int, D: int, device) -> torch.Tensor:
         """The cached [Mp + 16, D] bf16 workspace of rmsnorm_rows: ONE layout at a time (a scoring run keeps its shape; another (B, T)
@@ -463,14 +488,17 @@ class HipOps:
         N = w.shape[0]
         assert xp.shape[0] >= Mp + B * r
         zt = torch.empty(Mp // 256 + (1 if r and tail else 0), N, 256, dtype=torch.bfloat16, device=xp.device)
-        with self._t("gemm_zt"):
-            _check(self.lib.evo_linear_t_mfma_bf16(xp.data_ptr(), w.data_ptr(), _ptr(b), zt.data_ptr(), Mp, N, K, _stream()),
-                   "evo_linear_t_mfma_bf16")
+        self._launch("gemm_zt", "evo_linear_t_mfma_bf16", xp.data_ptr(), w.data_ptr(), _ptr(b), zt.data_ptr(), Mp, N, K)
         if r and tail:
-            zt[-1].zero_()                                                                # (6 MB: the tail block's unused positions hold zeros, not whatever the allocator left)
-            z_tail = self._linear_small_m(xp[Mp:Mp + B * r], w, b, None)                # [B r, N]
-            zt[-1].view(N, 32, 8)[:, :B, :r] = z_tail.view(B, r, N).permute(2, 0, 1)      # position Mp + 8 b + j
+            self._zt_tail_fill(zt, self._linear_small_m(xp[Mp:Mp + B * r], w, b, None), B, r)
         return zt
+
+    @staticmethod
+    def _zt_tail_fill(zt: torch.Tensor, z_tail: torch.Tensor, B: int, r: int) -> None:
+        """The tail block of z^T (zt_layout) from the tail tokens' projections z_tail [B r, N]: token j of batch row b at position Mp + 8 b + j."""
+        N = zt.shape[1]
+        zt[-1].zero_()                                                                    # (6 MB: the tail block's unused positions hold zeros, not whatever the allocator left)
+        zt[-1].view(N, 32, 8)[:, :B, :r] = z_tail.view(B, r, N).permute(2, 0, 1)
 
     @staticmethod
     def zt_rows(zt: torch.Tensor, B: int, T: int, t0: int, n: int) -> torch.Tensor:
@@ -582,28 +610,32 @@ class HipOps:
         if s0 is not None:
             s0r = torch.view_as_real(s0.to(torch.complex64).contiguous())
             assert s0r.shape == (B, D, 8, 2)
-        C = seg_len or self.seg_len_override or pick_segment_length(B, T, n_heads)
-        n_seg = (T + C - 1) // C
-        agg = torch.empty(B, n_seg, D, 8, 2, dtype=torch.float32, device=z.device)
-        y = torch.empty(B, T, D, dtype=torch.bfloat16, device=z.device)
+        agg, C = self._hyena_seg_state(z, z_halo, fir_w, fir_b, poles, mask, n_heads, seg_len)
         s_final = torch.empty(B, D, 8, 2, dtype=torch.float32, device=z.device) if want_state else None
-        st = _stream()
-        with self._t("hyena_seg_state"):
-            _check(self.lib.evo_hyena_seg_state(z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(),
-                                                poles.data_ptr(), agg.data_ptr(), _ptr(mask), B, T, D, n_heads, C, st),
-                   "evo_hyena_seg_state")
-        with self._t("hyena_carry_scan"):
-            _check(self.lib.evo_hyena_carry_scan(agg.data_ptr(), poles.data_ptr(), _ptr(s0r), _ptr(s_final), B, T, D,
-                                                 C, st), "evo_hyena_carry_scan")
-        with self._t("hyena_apply"):
-            _check(self.lib.evo_hyena_apply(z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(),
-                                            poles.data_ptr(), residues.data_ptr(), dskip.data_ptr(), agg.data_ptr(),
-                                            y.data_ptr(), _ptr(mask), B, T, D, n_heads, C, st), "evo_hyena_apply")
+        self._launch("hyena_carry_scan", "evo_hyena_carry_scan", agg.data_ptr(), poles.data_ptr(), _ptr(s0r), _ptr(s_final), B, T, D, C)
+        y = self._hyena_apply(z, z_halo, fir_w, fir_b, poles, residues, dskip, agg, mask, n_heads, C)
         state = torch.view_as_complex(s_final) if want_state else None
         # bytes of the tensors each launch touched (bench.py prints them beside the algorithmic figure)
         self.last_hyena_io = {"seg_state": z.numel() * 2 * 2 // 3 + agg.numel() * 4,
                               "apply": z.numel() * 2 + y.numel() * 2 + agg.numel() * 4}
         return y, state
+
+    def _hyena_seg_state(self, z, z_halo, fir_w, fir_b, poles, mask, n_heads, seg_len):
+        """Launch 1 of the modal form: the segments' end states from a zero carry-in -> (agg [B, segments, D, 8, 2] fp32, segment length)."""
+        B, T, D3 = z.shape
+        C = seg_len or self.seg_len_override or pick_segment_length(B, T, n_heads)
+        agg = torch.empty(B, (T + C - 1) // C, D3 // 3, 8, 2, dtype=torch.float32, device=z.device)
+        self._launch("hyena_seg_state", "evo_hyena_seg_state", z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(),
+                     agg.data_ptr(), _ptr(mask), B, T, D3 // 3, n_heads, C)
+        return agg, C
+
+    def _hyena_apply(self, z, z_halo, fir_w, fir_b, poles, residues, dskip, agg, mask, n_heads, C):
+        """Launch 3 of the modal form: y [B, T, D] from z and the segments' carried-in states `agg`."""
+        B, T, D3 = z.shape
+        y = torch.empty(B, T, D3 // 3, dtype=torch.bfloat16, device=z.device)
+        self._launch("hyena_apply", "evo_hyena_apply", z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(),
+                     residues.data_ptr(), dskip.data_ptr(), agg.data_ptr(), y.data_ptr(), _ptr(mask), B, T, D3 // 3, n_heads, C)
+        return y
 
     YBLK = 128          # rows per block of the blocked y layout (csrc/hyena_ct.hip)
 
@@ -625,20 +657,18 @@ class HipOps:
         M, N = res.shape
         K = w.shape[1]
         assert y_blk.shape[0] * self.YBLK >= M and y_blk.shape[1] * 16 == K and res.is_contiguous()
-        Mf = M // 256 * 256
-        ok = (Mf > 0 and N % 256 == 0 and K % 64 == 0 and K >= 128 and Mf * K * 2 < 0xffffffff and N * K * 2 < 0xffffffff
-              and w.dtype == torch.bfloat16 and w.is_contiguous())
-        if not ok:
+        r = self._sliver_rows(M, limit=255)                  # (the blocked launch takes whole tiles only)
+        if not (M > r and self._gemm_shape_ok(M - r, N, K) and self._bf16_ok(w)):
             return self.linear_residual_(res, self.yblk_to_rows(y_blk, M).contiguous(), w, bias=bias)
-        with self._t("gemm_mfma"):
-            _check(self.lib.evo_linear_xblk_mfma_bf16(y_blk.data_ptr(), w.data_ptr(), _ptr(bias), res.data_ptr(), res.data_ptr(), Mf, N, K,
-                                                      _stream()), "evo_linear_xblk_mfma_bf16")
-        if M > Mf:                                           # (<= 255 rows: rows Mf .. M - 1 of the matrix, gathered row-major)
-            r = M - Mf
-            nb0 = Mf // self.YBLK
-            tail = y_blk[nb0:].permute(0, 2, 1, 3).reshape(-1, K)[:r].contiguous()
-            self.linear_residual_(res[Mf:], tail, w, bias=bias)
+        self._main_then_sliver(M, r,
+                               lambda Mf: self._launch("gemm_mfma", "evo_linear_xblk_mfma_bf16", y_blk.data_ptr(), w.data_ptr(), _ptr(bias),
+                                                       res.data_ptr(), res.data_ptr(), Mf, N, K),
+                               lambda Mf: self.linear_residual_(res[Mf:], self._yblk_tail_rows(y_blk, Mf, M), w, bias=bias))
         return res
+
+    def _yblk_tail_rows(self, y_blk: torch.Tensor, Mf: int, M: int) -> torch.Tensor:
+        """Rows Mf .. M - 1 (Mf a multiple of 256, at most 255 rows) of the matrix a blocked y stands for, gathered row-major."""
+        return y_blk[Mf // self.YBLK:].permute(0, 2, 1, 3).reshape(-1, y_blk.shape[1] * 16)[:M - Mf].contiguous()
 
     # ---- RMSNorm folded into the dense layers around it (csrc/gemm.hip NF; include/evo_mi355x.h "RMSNorm folded ...") -----------------
     @staticmethod
@@ -648,24 +678,19 @@ class HipOps:
 
     def nf_shape_ok(self, M: int, N: int, K: int) -> bool:
         """Shapes whose main rows the persistent dense layer takes with the norm folded in (sliver rows <= 16 or none)."""
-        r = M % 256
-        Mm = M - r if 1 <= r <= 16 else M
         # (below 1,024 rows a forward is launch-bound -- four row tiles on 256 CUs -- and the fold would trade 63 small norm launches for 64 finalize launches)
-        return (self.fuse_norm and self.all_gemm_mfma and M >= 1024 and N % 256 == 0 and K % 64 == 0 and K >= 128
-                and Mm * K * 2 < 0xffffffff and N * K * 2 < 0xffffffff)      # (operands below 4 GiB: the kernel's 32-bit DMA offsets; outputs are addressed per tile)
+        return self.fuse_norm and self.all_gemm_mfma and M >= 1024 and self._gemm_shape_ok(self._nf_main_rows(M), N, K)
 
     def _nf_main_rows(self, M: int) -> int:
-        r = M % 256
-        return M - r if 1 <= r <= 16 else M
+        return M - self._sliver_rows(M)                      # (no floor of its own: nf_shape_ok asks for 1,024 rows)
 
     def rms_finalize(self, ss: Optional[torch.Tensor], x: torch.Tensor, M_main: int, eps: float) -> torch.Tensor:
         """rstd [M rounded up to 256] fp32 = 1 / (rms(x_m) + eps): rows < M_main from the dense layer's partial sums `ss`
         [strips, ld], the others from x itself (evo_rms_finalize_f32)."""
         M, D = x.shape
         rstd = torch.empty((M + 255) // 256 * 256, dtype=torch.float32, device=x.device)
-        with self._t("rms_finalize"):
-            _check(self.lib.evo_rms_finalize_f32(_ptr(ss), 0 if ss is None else ss.shape[0], 0 if ss is None else ss.shape[1], x.data_ptr(),
-                                                 M_main, M, D, float(eps), rstd.data_ptr(), _stream()), "evo_rms_finalize_f32")
+        self._launch("rms_finalize", "evo_rms_finalize_f32", _ptr(ss), 0 if ss is None else ss.shape[0], 0 if ss is None else ss.shape[1],
+                     x.data_ptr(), M_main, M, D, float(eps), rstd.data_ptr())
         return rstd
 
     def linear_residual_stats_(self, res: torch.Tensor, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], eps: float):
@@ -675,27 +700,23 @@ class HipOps:
         K = w.shape[1]
         Mm = self._nf_main_rows(M)
         ss = torch.empty(N // 128, (Mm + 255) // 256 * 256, dtype=torch.float32, device=res.device)
-        with self._t("gemm_mfma"):
-            _check(self.lib.evo_linear_mfma_nf_bf16(x.data_ptr(), w.data_ptr(), _ptr(bias), res.data_ptr(), res.data_ptr(), None, ss.data_ptr(),
-                                                    ss.shape[1], Mm, N, K, _stream()), "evo_linear_mfma_nf_bf16")
-        if M > Mm:
-            self._linear_small_m(x[Mm:], w, bias, res[Mm:])
+        self._main_then_sliver(M, M - Mm,
+                               lambda Mm: self._launch("gemm_mfma", "evo_linear_mfma_nf_bf16", x.data_ptr(), w.data_ptr(), _ptr(bias), res.data_ptr(),
+                                                       res.data_ptr(), None, ss.data_ptr(), ss.shape[1], Mm, N, K),
+                               lambda Mm: self._linear_small_m(x[Mm:], w, bias, res[Mm:]))
         return self.rms_finalize(ss, res, Mm, eps)
 
     def linear_residual_yblk_stats_(self, res: torch.Tensor, y_blk: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], eps: float):
         """linear_residual_yblk_ + the RMSNorm factor of every updated row (see linear_residual_stats_)."""
         M, N = res.shape
         K = w.shape[1]
-        Mf = M // 256 * 256
-        ss = torch.empty(N // 128, Mf, dtype=torch.float32, device=res.device)
-        with self._t("gemm_mfma"):
-            _check(self.lib.evo_linear_xblk_mfma_nf_bf16(y_blk.data_ptr(), w.data_ptr(), _ptr(bias), res.data_ptr(), res.data_ptr(), ss.data_ptr(),
-                                                         Mf, Mf, N, K, _stream()), "evo_linear_xblk_mfma_nf_bf16")
-        if M > Mf:
-            r = M - Mf
-            tail = y_blk[Mf // self.YBLK:].permute(0, 2, 1, 3).reshape(-1, K)[:r].contiguous()
-            self.linear_residual_(res[Mf:], tail, w, bias=bias)
-        return self.rms_finalize(ss, res, Mf, eps)
+        r = self._sliver_rows(M, limit=255)
+        ss = torch.empty(N // 128, M - r, dtype=torch.float32, device=res.device)
+        self._main_then_sliver(M, r,
+                               lambda Mf: self._launch("gemm_mfma", "evo_linear_xblk_mfma_nf_bf16", y_blk.data_ptr(), w.data_ptr(), _ptr(bias),
+                                                       res.data_ptr(), res.data_ptr(), ss.data_ptr(), Mf, Mf, N, K),
+                               lambda Mf: self.linear_residual_(res[Mf:], self._yblk_tail_rows(y_blk, Mf, M), w, bias=bias))
+        return self.rms_finalize(ss, res, M - r, eps)
 
     def linear_rs(self, x: torch.Tensor, rstd: torch.Tensor, w_folded: torch.Tensor, b: Optional[torch.Tensor], w: torch.Tensor,
                   scale: torch.Tensor, eps: float) -> torch.Tensor:
@@ -705,11 +726,13 @@ class HipOps:
         N = w.shape[0]
         Mm = self._nf_main_rows(M)
         y = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-        with self._t("gemm_mfma"):
-            _check(self.lib.evo_linear_mfma_nf_bf16(x.data_ptr(), w_folded.data_ptr(), _ptr(b), None, y.data_ptr(), rstd.data_ptr(), None, 0,
-                                                    Mm, N, K, _stream()), "evo_linear_mfma_nf_bf16")
-        if M > Mm:
+
+        def sliver(Mm):
             y[Mm:] = self.norm_linear(x[Mm:], scale, eps, w, b)
+        self._main_then_sliver(M, M - Mm,
+                               lambda Mm: self._launch("gemm_mfma", "evo_linear_mfma_nf_bf16", x.data_ptr(), w_folded.data_ptr(), _ptr(b), None,
+                                                       y.data_ptr(), rstd.data_ptr(), None, 0, Mm, N, K),
+                               sliver)
         return y
 
     def mlp_gate_rs(self, x: torch.Tensor, rstd: torch.Tensor, w12g_folded: torch.Tensor, w12: torch.Tensor, scale: torch.Tensor,
@@ -720,11 +743,13 @@ class HipOps:
         I = w12g_folded.shape[0] // 2
         Mm = self._nf_main_rows(M)
         a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-        with self._t("gemm_gate"):
-            _check(self.lib.evo_mlp_gate_mfma_nf_bf16(x.data_ptr(), rstd.data_ptr(), w12g_folded.data_ptr(), a.data_ptr(), Mm, I, K, _stream()),
-                   "evo_mlp_gate_mfma_nf_bf16")
-        if M > Mm:
+
+        def sliver(Mm):
             a[Mm:] = self.mlp_gate(x[Mm:], w12, scale, eps, w12g=None if w12 is not None else w12g_folded)
+        self._main_then_sliver(M, M - Mm,
+                               lambda Mm: self._launch("gemm_gate", "evo_mlp_gate_mfma_nf_bf16", x.data_ptr(), rstd.data_ptr(), w12g_folded.data_ptr(),
+                                                       a.data_ptr(), Mm, I, K),
+                               sliver)
         return a
 
     def zt_stream_rows_ok(self, B: int, T: int) -> bool:
@@ -747,20 +772,15 @@ class HipOps:
         N = w.shape[0]
         if r == 0:                                    # plain form without a single pad position: z^T position p IS row p of the stream
             zt = torch.empty(Mp // 256, N, 256, dtype=torch.bfloat16, device=x.device)
-            with self._t("gemm_zt"):
-                _check(self.lib.evo_linear_t_mfma_nf_bf16(x.data_ptr(), rstd.data_ptr(), w_folded.data_ptr(), _ptr(b), zt.data_ptr(), Mp, N, K,
-                                                          Mp, Mp, 0, _stream()), "evo_linear_t_mfma_nf_bf16")
+            self._launch("gemm_zt", "evo_linear_t_mfma_nf_bf16", x.data_ptr(), rstd.data_ptr(), w_folded.data_ptr(), _ptr(b), zt.data_ptr(),
+                         Mp, N, K, Mp, Mp, 0)
             return zt
         zt = torch.empty(Mp // 256 + (1 if tail else 0), N, 256, dtype=torch.bfloat16, device=x.device)
-        with self._t("gemm_zt"):
-            _check(self.lib.evo_linear_t_mfma_nf_bf16(x.data_ptr(), rstd.data_ptr(), w_folded.data_ptr(), _ptr(b), zt.data_ptr(), Mp, N, K,
-                                                      B * T, Tm, r, _stream()), "evo_linear_t_mfma_nf_bf16")
-        if not tail:                                  # (the caller runs the tail tokens through the single-token launch: hyena_ct(main_only=True))
-            return zt
-        zt[-1].zero_()
-        x_tail = x.view(B, T, K)[:, Tm:].reshape(B * r, K).contiguous()                           # (a copy of B r <= 16 rows)
-        z_tail = self.norm_linear(x_tail, scale, eps, w, b)                             # [B r, N]
-        zt[-1].view(N, 32, 8)[:, :B, :r] = z_tail.view(B, r, N).permute(2, 0, 1)        # position Mp + 8 b + j
+        self._launch("gemm_zt", "evo_linear_t_mfma_nf_bf16", x.data_ptr(), rstd.data_ptr(), w_folded.data_ptr(), _ptr(b), zt.data_ptr(),
+                     Mp, N, K, B * T, Tm, r)
+        if tail:                                      # (else the caller runs the tail tokens through the single-token launch: hyena_ct(main_only=True))
+            x_tail = x.view(B, T, K)[:, Tm:].reshape(B * r, K).contiguous()                       # (a copy of B r <= 16 rows)
+            self._zt_tail_fill(zt, self.norm_linear(x_tail, scale, eps, w, b), B, r)
         return zt
 
     # The same operator in two stages, for sequence parallelism: stage 1 (launches 1+2) yields the shard's end
@@ -769,36 +789,19 @@ class HipOps:
         self._need(z, torch.bfloat16, "hyena z")
         B, T, D3 = z.shape
         D = D3 // 3
-        C = seg_len or self.seg_len_override or pick_segment_length(B, T, n_heads)
-        n_seg = (T + C - 1) // C
-        agg = torch.empty(B, n_seg, D, 8, 2, dtype=torch.float32, device=z.device)
+        agg, C = self._hyena_seg_state(z, z_halo, fir_w, fir_b, poles, None, n_heads, seg_len)
         s_end = torch.empty(B, D, 8, 2, dtype=torch.float32, device=z.device)
-        st = _stream()
-        with self._t("hyena_seg_state"):
-            _check(self.lib.evo_hyena_seg_state(z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(),
-                                                poles.data_ptr(), agg.data_ptr(), None, B, T, D, n_heads, C, st),
-                   "evo_hyena_seg_state")
-        with self._t("hyena_carry_scan"):
-            _check(self.lib.evo_hyena_carry_scan(agg.data_ptr(), poles.data_ptr(), None, s_end.data_ptr(), B, T, D, C,
-                                                 st), "evo_hyena_carry_scan")
+        self._launch("hyena_carry_scan", "evo_hyena_carry_scan", agg.data_ptr(), poles.data_ptr(), None, s_end.data_ptr(), B, T, D, C)
         return (agg, C), torch.view_as_complex(s_end)
 
     def hyena_stage2(self, z, fir_w, fir_b, poles, residues, dskip, n_heads, stage1, z_halo=None, s0=None):
         agg, C = stage1
         B, T, D3 = z.shape
         D = D3 // 3
-        st = _stream()
         if s0 is not None:
             s0r = torch.view_as_real(s0.to(torch.complex64).contiguous())
-            with self._t("hyena_carry_add"):
-                _check(self.lib.evo_hyena_carry_add(agg.data_ptr(), poles.data_ptr(), s0r.data_ptr(), B, T, D, C, st),
-                       "evo_hyena_carry_add")
-        y = torch.empty(B, T, D, dtype=torch.bfloat16, device=z.device)
-        with self._t("hyena_apply"):
-            _check(self.lib.evo_hyena_apply(z.data_ptr(), _ptr(z_halo), fir_w.data_ptr(), fir_b.data_ptr(),
-                                            poles.data_ptr(), residues.data_ptr(), dskip.data_ptr(), agg.data_ptr(),
-                                            y.data_ptr(), None, B, T, D, n_heads, C, st), "evo_hyena_apply")
-        return y
+            self._launch("hyena_carry_add", "evo_hyena_carry_add", agg.data_ptr(), poles.data_ptr(), s0r.data_ptr(), B, T, D, C)
+        return self._hyena_apply(z, z_halo, fir_w, fir_b, poles, residues, dskip, agg, None, n_heads, C)
 
     def hyena_step(self, z_t: torch.Tensor, fir_state: torch.Tensor, iir_state: torch.Tensor, fir_w, fir_b, poles,
                    residues, dskip, n_heads: int) -> torch.Tensor:
@@ -821,8 +824,7 @@ class HipOps:
         """One decode token through pre-norm + projections + FIR/modal step + gate in ONE launch (M = batch <= 4, or <= 8 at D = 4096);
         states are updated in place.  Falls back to the two kernels otherwise."""
         M, D = x.shape
-        ok = ((1 <= M <= 4 or (M <= 8 and D == 4096)) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and proj_w.is_contiguous()
-              and proj_w.dtype == torch.bfloat16 and norm_scale.dtype == torch.bfloat16 and proj_b is not None
+        ok = (self.fused_rows_ok(M, D) and self._bf16_ok(x, proj_w, scale=norm_scale) and proj_b is not None
               and fir_state.dtype == torch.bfloat16 and fir_state.is_contiguous() and fir_state.shape[0] == M
               and iir_state.dtype == torch.complex64 and iir_state.is_contiguous() and iir_state.shape[0] == M
               and D == n_heads * 128)
@@ -831,11 +833,9 @@ class HipOps:
             return self.hyena_step(z, fir_state, iir_state, fir_w, fir_b, poles, residues, dskip, n_heads)
         y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
         sr = torch.view_as_real(iir_state)
-        with self._t("gemv_hyena"):
-            _check(self.lib.evo_hyena_decode_fused_small_m(
-                x.data_ptr(), norm_scale.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(), fir_state.data_ptr(),
-                sr.data_ptr(), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(), residues.data_ptr(),
-                dskip.data_ptr(), y.data_ptr(), M, D, n_heads, float(eps), _stream()), "evo_hyena_decode_fused_small_m")
+        self._launch("gemv_hyena", "evo_hyena_decode_fused_small_m", x.data_ptr(), norm_scale.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(),
+                     fir_state.data_ptr(), sr.data_ptr(), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(), residues.data_ptr(),
+                     dskip.data_ptr(), y.data_ptr(), M, D, n_heads, float(eps))
         return y
 
     @staticmethod
@@ -933,14 +933,10 @@ class HipOps:
         """linear(rmsnorm(x) * scale, w, b).  Decode-sized batches (M <= 4) with a wide layer take ONE weight-streaming
         launch that rebuilds the normalised row on the fly; everything else is the two kernels."""
         M, K = x.shape
-        if ((1 <= M <= 4 or (M <= 8 and K == 4096)) and w.shape[0] > 4096 and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-                and scale.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous() and scale.is_contiguous()
-                and K % 8 == 0):
+        if self.fused_rows_ok(M, K) and w.shape[0] > 4096 and self._bf16_ok(x, w, scale=scale) and K % 8 == 0:
             y = torch.empty(M, w.shape[0], dtype=torch.bfloat16, device=x.device)
-            with self._t("gemv_norm"):
-                _check(self.lib.evo_norm_linear_small_m_bf16(x.data_ptr(), scale.data_ptr(), w.data_ptr(), _ptr(b),
-                                                             y.data_ptr(), M, w.shape[0], K, float(eps), _stream()),
-                       "evo_norm_linear_small_m_bf16")
+            self._launch("gemv_norm", "evo_norm_linear_small_m_bf16", x.data_ptr(), scale.data_ptr(), w.data_ptr(), _ptr(b), y.data_ptr(),
+                         M, w.shape[0], K, float(eps))
             return y
         return self.linear(self.rmsnorm(x, None, scale, eps), w, b, mfma=mfma)
 
@@ -959,9 +955,7 @@ class HipOps:
         if w12g is None or not self.mlp_gate_fused:
             return False
         M, K = x.shape
-        return (M >= 256 and w12g.shape[0] % 256 == 0 and K % 64 == 0 and K >= 128 and x.is_cuda and x.dtype == torch.bfloat16
-                and w12g.dtype == torch.bfloat16 and x.is_contiguous() and w12g.is_contiguous()
-                and M * K * 2 < 0xffffffff and w12g.shape[0] * K * 2 < 0xffffffff)
+        return M >= 256 and self._gemm_shape_ok(M, w12g.shape[0], K) and self._bf16_ok(x, w12g)
 
     def mlp_gate(self, x: torch.Tensor, w12: Optional[torch.Tensor], norm_scale: Optional[torch.Tensor] = None,
                  eps: float = 0.0, w12g: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -979,15 +973,14 @@ class HipOps:
             if norm_scale is not None:
                 x = self.rmsnorm(x, None, norm_scale, eps)
             a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-            r = self._tail_rows(x, wsrc)                          # the BOS sliver (M % 256 <= 16) goes through the small-M path
-            with self._t("gemm_gate"):
-                _check(self.lib.evo_mlp_gate_mfma_bf16(x.data_ptr(), w12g.data_ptr(), a.data_ptr(), M - r, I, K, _stream()),
-                       "evo_mlp_gate_mfma_bf16")
-            if r:
-                a[M - r:] = self.mlp_gate(x[M - r:], w12, w12g=w12g if w12 is None else None)
+
+            def sliver(Mm):                                       # the BOS sliver (M % 256 <= 16) goes through the small-M path
+                a[Mm:] = self.mlp_gate(x[Mm:], w12, w12g=w12g if w12 is None else None)
+            self._main_then_sliver(M, self._tail_rows(x, wsrc),
+                                   lambda Mm: self._launch("gemm_gate", "evo_mlp_gate_mfma_bf16", x.data_ptr(), w12g.data_ptr(), a.data_ptr(), Mm, I, K),
+                                   sliver)
             return a
-        ok_mem = (x.is_cuda and x.dtype == torch.bfloat16 and wsrc.dtype == torch.bfloat16 and x.is_contiguous() and wsrc.is_contiguous()
-                  and (norm_scale is None or (norm_scale.dtype == torch.bfloat16 and norm_scale.is_contiguous())))
+        ok_mem = self._bf16_ok(x, wsrc, scale=norm_scale)
         # (5-8 rows WITH a norm keep the dot2 launch that norms for itself: one launch -- the BOS sliver of a scoring batch -- against norm pass + 44 us)
         if self.gate_small_m_mfma and 5 <= M <= 64 and (M > 8 or norm_scale is None) and K % 256 == 0 and I % 32 == 0 and ok_mem:
             # round 6: 5-64 rows on the MFMA weight-streaming form with the gate in its epilogue (csrc/gemv.hip skinny_nw_kernel GATE; 512-byte weight
@@ -995,22 +988,17 @@ class HipOps:
             if norm_scale is not None:
                 x = self.rmsnorm(x, None, norm_scale, eps)
             a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-            with self._t("gemv_gate"):
-                _check(self.lib.evo_mlp_gate_small_m_bf16(x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, grouped, _stream()),
-                       "evo_mlp_gate_small_m_bf16")
+            self._launch("gemv_gate", "evo_mlp_gate_small_m_bf16", x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, grouped)
             return a
-        if ((1 <= M <= 4 or (M <= 8 and K == 4096 and norm_scale is not None)) and x.is_cuda and x.dtype == torch.bfloat16 and wsrc.dtype == torch.bfloat16 and x.is_contiguous()
-                and wsrc.is_contiguous() and K % 8 == 0 and I % 2 == 0 and (not grouped or I % 32 == 0)
-                and (norm_scale is None or (norm_scale.dtype == torch.bfloat16 and norm_scale.is_contiguous()))):
+        # (without a norm the dot2 launch stops at 4 rows: 5-8 rows are the MFMA form's above, or the dense layer's)
+        if ((1 <= M <= 4 or norm_scale is not None) and self.fused_rows_ok(M, K) and ok_mem and K % 8 == 0 and I % 2 == 0
+                and (not grouped or I % 32 == 0)):
             a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-            with self._t("gemv_gate"):
-                if norm_scale is None:
-                    _check(self.lib.evo_mlp_gate_small_m_bf16(x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, grouped,
-                                                              _stream()), "evo_mlp_gate_small_m_bf16")
-                else:
-                    _check(self.lib.evo_norm_mlp_gate_small_m_bf16(x.data_ptr(), norm_scale.data_ptr(), wsrc.data_ptr(),
-                                                                   a.data_ptr(), M, I, K, float(eps), grouped, _stream()),
-                           "evo_norm_mlp_gate_small_m_bf16")
+            if norm_scale is None:
+                self._launch("gemv_gate", "evo_mlp_gate_small_m_bf16", x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, grouped)
+            else:
+                self._launch("gemv_gate", "evo_norm_mlp_gate_small_m_bf16", x.data_ptr(), norm_scale.data_ptr(), wsrc.data_ptr(), a.data_ptr(),
+                             M, I, K, float(eps), grouped)
             return a
         if norm_scale is not None:
             x = self.rmsnorm(x, None, norm_scale, eps)

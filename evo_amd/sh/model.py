@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from ..ops import HipOps                                 # (its static host rules and pure tensor functions; no library is loaded by the import)
 from .cache import InferenceParams, RecurrentInferenceParams
 from .utils import dotdict
 
@@ -295,7 +296,6 @@ class StripedHyena(nn.Module):
         `model.to(device).prepare().fold_norms_()` once after loading."""
         if getattr(self, "_norms_folded", False):
             return self
-        from ..ops import HipOps                                 # (fold_norm_scale / pack_gate_weights are pure tensor functions)
         ops = self.ops
         with torch.inference_mode(False), torch.no_grad():
             if not self._packed:
@@ -448,7 +448,7 @@ class StripedHyena(nn.Module):
                 torch.sin(freqs).to(torch.bfloat16).float().contiguous())
 
     # ------------------------------------------------------------------ blocks
-    DECODE_ROWS = 8          # batches this small take the fused single-token launches (csrc/gemv.hip; 5-8 rows at D = 4096 only)
+    DECODE_ROWS = HipOps.DECODE_ROWS          # batches this small take the fused single-token launches (HipOps.fused_rows_ok)
 
     def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False):
         """x += y @ w^T (the mixer's output projection); returns the bias still to be added (folded into the next
@@ -597,8 +597,8 @@ class StripedHyena(nn.Module):
             # go through the operator as a ragged tile (one valid step at a full tile's issue time: 8 of 136 tile steps at 8 x 8,193) but
             # through the fused single-token launch of the decode path, from the operator's end state (ops.hyena_tail_split)
             Tm, _, _, r_tail = ops.zt_layout(B, T)
-            split = (cache is None and r_tail == 1 and getattr(ops, "hyena_tail_split", False) and B <= self.DECODE_ROWS
-                     and (B <= 4 or D == 4096) and pb is not None)
+            split = (cache is None and r_tail == 1 and getattr(ops, "hyena_tail_split", False) and HipOps.fused_rows_ok(B, D)
+                     and pb is not None)
             if nf and rs is not None and ops.zt_stream_rows_ok(B, T):
                 # pre-norm folded: the projection reads the stream itself (z^T layouts without pad positions inside the main area: no padded copy either)
                 wp_f = self._folded(blk, "_wp_f", blk.projections.weight, blk.pre_norm.scale)
@@ -754,7 +754,8 @@ class StripedHyena(nn.Module):
         cap = max(1, self.max_rows_per_pass // T)
 
         def fits(p):
-            return (p * T) % 256 <= self.DECODE_ROWS
+            r = (p * T) % 256                                # (grouping is decided for the 7B width, where up to DECODE_ROWS rows fit)
+            return r == 0 or HipOps.fused_rows_ok(r, 4096)
 
         if B <= cap and (fits(B) or B * T < 65536):
             return [B]

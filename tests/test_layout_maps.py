@@ -246,3 +246,135 @@ def test_norm_fold_host_maps_and_the_stream_row_remap_of_the_transposed_projecti
         assert int(src.max()) < B * T
     rows = sorted(wm * 128 + 16 * j + l15 for wm in range(2) for j in range(8) for l15 in range(16))
     assert rows == list(range(256))
+
+
+# ---- the routing of the dense layers, tabulated (tests/golden/dense_routing.json) ---------------------------------------------------
+ROUTE_M = (1, 4, 5, 8, 9, 16, 17, 64, 65, 255, 256, 272, 273, 1023, 1024, 2050, 2100, 4095, 4096, 4097, 4112, 4113, 65544, 131073)
+# the 7B layer shapes (Wo / out_filter_dense, Wqkv / projections, l1 | l2, l3, the unembedding) + K % 32 != 0 (and % 8 == 0) + K % 64 != 0
+ROUTE_NK = ((4096, 4096), (12288, 4096), (22016, 4096), (4096, 11008), (512, 4096), (4096, 4120), (4096, 4128))
+ROUTE_BT = ((8, 8193), (1, 131073), (2, 1026), (3, 700), (16, 8193), (1, 8192))
+# the operand flag: "ok" = every operand a contiguous bf16 device tensor; the others break one property of one operand
+ROUTE_OPERANDS = ("ok", "host", "x_f32", "w_f32", "x_strided", "w_strided")
+
+
+class _Operand:
+    """What the routing predicates read of a tensor -- shape / dtype / is_cuda / is_contiguous() -- and nothing to compute with."""
+
+    def __init__(self, shape, dtype=None, is_cuda=True, contiguous=True):
+        import torch
+        self.shape, self.dtype, self.is_cuda, self._contiguous = tuple(shape), dtype or torch.bfloat16, is_cuda, contiguous
+        self.device = "cuda:0" if is_cuda else "cpu"
+
+    def is_contiguous(self):
+        return self._contiguous
+
+    def data_ptr(self):
+        return 0
+
+    def numel(self):
+        n = 1
+        for s in self.shape:
+            n *= s
+        return n
+
+
+def _route_operands(kind, M, N, K):
+    import torch
+    x = _Operand((M, K), torch.float32 if kind == "x_f32" else None, kind != "host", kind != "x_strided")
+    w = _Operand((N, K), torch.float32 if kind == "w_f32" else None, kind != "host", kind != "w_strided")
+    return x, w
+
+
+def dense_routing_table(monkeypatch):
+    """{key: decisions} over ROUTE_M x ROUTE_NK x ROUTE_OPERANDS and ROUTE_BT x ROUTE_NK, from evo_amd.ops as imported.  The pure
+    predicates are called as they are; which launch norm_linear / mlp_gate / hyena_decode_fused pick (the fused single-token launches or
+    not) is read off a recording stand-in for the library, with the launches behind them (rmsnorm, linear, gelu_gate, hyena_step)
+    replaced by markers."""
+    import types
+    import torch
+    import evo_amd.ops as O
+
+    class FakeTorch:                                  # evo_amd.ops' `torch` for the three routed calls: allocations become _Operand
+        def __getattr__(self, name):
+            return getattr(torch, name)
+        empty = staticmethod(lambda *shape, dtype=None, device=None: _Operand(shape, dtype))
+        view_as_real = staticmethod(lambda t: t)
+        cuda = types.SimpleNamespace(current_stream=lambda: types.SimpleNamespace(cuda_stream=0))
+
+    class Lib:
+        def __init__(self):
+            self.calls = []
+
+        def __getattr__(self, name):
+            return lambda *args: self.calls.append(name) or 0
+
+    class Probe(O.HipOps):
+        def __init__(self):
+            self.lib, self.timer = Lib(), None
+            self.fuse_norm = self.all_gemm_mfma = self.hyena_ct_flag = self.mlp_gate_fused = self.gate_small_m_mfma = True
+
+        def rmsnorm(self, x, bias, scale, eps):
+            self.lib.calls.append("rmsnorm")
+            return x
+
+        def linear(self, x, w, b=None, mfma=False):
+            self.lib.calls.append("linear")
+            return _Operand((x.shape[0], w.shape[0]))
+
+        def gelu_gate(self, g):
+            self.lib.calls.append("gelu_gate")
+            return g
+
+        def hyena_step(self, z, *args):
+            self.lib.calls.append("hyena_step")
+            return z
+
+        def launches(self, fn, *args, **kw):
+            self.lib.calls = []
+            fn(*args, **kw)
+            return "+".join(c.replace("evo_", "").replace("_bf16", "") for c in self.lib.calls)
+
+    monkeypatch.setattr(O, "torch", FakeTorch())
+    ops = Probe()
+    table = {}
+    for M, (N, K), kind in itertools.product(ROUTE_M, ROUTE_NK, ROUTE_OPERANDS):
+        x, w = _route_operands(kind, M, N, K)
+        scale = _Operand((K,))
+        row = {
+            "small_m": bool(ops._use_small_m(x, w)),
+            "tail_rows": int(ops._tail_rows(x, w)),
+            "nf_main_rows": int(ops._nf_main_rows(M)),
+            "mfma_linear_ok": bool(ops.mfma_linear_ok(x, w)),
+            "mlp_gate_fused_ok": bool(ops.mlp_gate_fused_ok(x, w)),
+            "nf_shape_ok": bool(ops.nf_shape_ok(M, N, K)),
+            "norm_linear": ops.launches(ops.norm_linear, x, scale, 1e-6, w, None),
+        }
+        if M <= 65 and N % 2 == 0:                     # (above: the unfused route either way; w as [W1; W2], no regrouped copy)
+            row["mlp_gate"] = ops.launches(ops.mlp_gate, x, w)
+            row["norm_mlp_gate"] = ops.launches(ops.mlp_gate, x, w, scale, 1e-6)
+        if M <= 65 and N == K and K % 128 == 0:        # the Hyena block's single-token launch: D = K, projections [3 D, D]
+            pw = _route_operands(kind, M, 3 * K, K)[1]
+            fir, iir = _Operand((M, 3 * K, 2)), _Operand((M, K, 8), torch.complex64)
+            row["hyena_decode_fused"] = ops.launches(ops.hyena_decode_fused, x, scale, 1e-6, pw, _Operand((3 * K,)), fir, iir,
+                                                     *[_Operand((1,))] * 5, K // 128)
+        table[f"M={M} N={N} K={K} {kind}"] = row
+    for (B, T), (N, K) in itertools.product(ROUTE_BT, ROUTE_NK):
+        table[f"B={B} T={T} N={N} K={K}"] = {"zt_layout": [int(v) for v in ops.zt_layout(B, T)],
+                                             "zt_shape_ok": bool(ops.zt_shape_ok(B, T, N, K)),
+                                             "zt_stream_rows_ok": bool(ops.zt_stream_rows_ok(B, T))}
+    return table
+
+
+def test_dense_layer_routing_matches_the_committed_table(monkeypatch):
+    """Which launch serves which shape is decided by a handful of host predicates (evo_amd/ops.py); this pins every one of them over a grid
+    of row counts (decode sizes, the BOS slivers of the scoring batches, the floors at 256 / 1,024 / 4,096 rows), the 7B layer shapes
+    and broken operands against tests/golden/dense_routing.json, so a change to the predicates that moves a shape to another kernel
+    shows as a diff of that table."""
+    import json
+    import os
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dense_routing.json")))
+    got = dense_routing_table(monkeypatch)
+    assert sorted(got) == sorted(want)
+    diff = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not diff, f"{len(diff)} routing decisions moved, e.g. {list(diff.items())[:3]}"
+    assert len(got) == len(ROUTE_M) * len(ROUTE_NK) * len(ROUTE_OPERANDS) + len(ROUTE_BT) * len(ROUTE_NK)
