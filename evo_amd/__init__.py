@@ -13,7 +13,7 @@ import sys as _sys
 from .version import version as __version__
 from .models import Evo
 from .generation import generate
-from .scoring import score_sequences, positional_entropies
+from .scoring import score_sequences, positional_entropies, position_profiles, substitution_scores, PositionProfile
 from .embeddings import embed_sequences
 
 SHIM_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "shim")

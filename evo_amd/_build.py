@@ -22,7 +22,7 @@ EXPORTS = [
     "evo_abi_version", "evo_embed_bf16", "evo_rmsnorm_bf16", "evo_hyena_seg_state", "evo_hyena_carry_scan", "evo_hyena_carry_add",
     "evo_hyena_apply", "evo_hyena_step", "evo_rope_qk_bf16", "evo_attn_fwd_causal_bf16", "evo_attn_decode_bf16",
     "evo_linear_small_m_bf16", "evo_mlp_gate_small_m_bf16", "evo_norm_mlp_gate_small_m_bf16", "evo_norm_linear_small_m_bf16", "evo_hyena_decode_fused_small_m", "evo_linear_mfma_bf16", "evo_mlp_gate_mfma_bf16", "evo_linear_xblk_mfma_bf16", "evo_hyena_ct", "evo_linear_t_mfma_bf16", "evo_rmsnorm_rows_bf16", "evo_gelu_gate_bf16",
-    "evo_logprob_entropy", "evo_unembed_logprob_bf16", "evo_rope_append_decode_bf16",
+    "evo_logprob_entropy", "evo_unembed_logprob_bf16", "evo_unembed_profile_bf16", "evo_rope_append_decode_bf16",
     "evo_linear_mfma_nf_bf16", "evo_linear_xblk_mfma_nf_bf16", "evo_mlp_gate_mfma_nf_bf16", "evo_linear_t_mfma_nf_bf16", "evo_rms_finalize_f32",
     "evo_probe_copy_f4", "evo_probe_mfma_bf16", "evo_pool_rows_bf16", "evo_sample_rows_f32",
 ]

@@ -14,7 +14,9 @@
 // DMA's SOURCE side (the LDS side of a DMA is lane-linear) so the ds_read_b128 fragment reads are conflict-free.
 // Two workgroups per CU (72 KiB each) overlap one's DMA wait with the other's MFMAs; this layer is 0.03 % of the
 // model's FLOPs, so the structure is kept simple (compiler-placed waits, two plain barriers per step).
-// Entry point and reference citation: include/evo_mi355x.h.
+// The body is instantiated twice: unembed_logprob_kernel (the scoring tail) and unembed_profile_kernel, which also writes the
+// log-probs of up to 8 chosen vocabulary ids per row (A, C, G, T: per-position profiles) from a second epilogue -- 2 KiB more LDS.
+// Entry points and reference citation: include/evo_mi355x.h.
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
@@ -26,14 +28,26 @@
 #define ST_STAGE ((ST_ROWS + ST_V) * ST_ROWB)   // 36,864 B = 36 DMA pieces of 1 KiB -> 9 per wave
 #define ST_NP 9
 #define ST_SCRATCH (4 * ST_ROWS * 3 * 4 + ST_ROWS * 4)   // per-wave (max, sum, sum-xd) + target logit
+#define ST_NSEL 8                          // most selected columns of the profile epilogue
+#define ST_SELB (ST_ROWS * ST_NSEL * 4)    // their parked logits: 2 KiB (profile instantiation only -> 79,104 B, still two workgroups per CU)
 
 typedef __attribute__((address_space(3))) void* st_lds_ptr_t;
 typedef __attribute__((address_space(1))) const void* st_glb_ptr_t;
 
-__global__ __launch_bounds__(256, 2) void unembed_logprob_kernel(
+// The selected vocabulary ids of the profile epilogue: read by the HOST at launch, they travel in the kernel arguments (scalar
+// registers: wave-uniform), so the kernel reads no id from memory.
+struct st_sel_t {
+    int n;                                 // 1 .. ST_NSEL
+    int id[ST_NSEL];                       // distinct, each in [0, ST_V)
+};
+
+// The kernel body, instantiated twice: SEL = false is the scoring tail (unembed_logprob_kernel), SEL = true adds the profile
+// epilogue (unembed_profile_kernel): the k-loop, the rounding and the row statistics are this one piece of code.
+template <bool SEL>
+__device__ __forceinline__ void unembed_tail_body(
     const unsigned char* __restrict__ h, const unsigned char* __restrict__ emb, const int64_t* __restrict__ target,
-    float* __restrict__ logprob, float* __restrict__ entropy, int64_t M, int K) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_STAGE + ST_SCRATCH];   // the only LDS object
+    float* __restrict__ logprob, float* __restrict__ entropy, int64_t M, int K, const st_sel_t& sel, float* __restrict__ sel_logprob) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * ST_STAGE + ST_SCRATCH + (SEL ? ST_SELB : 0)];   // the only LDS object
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -140,7 +154,10 @@ __global__ __launch_bounds__(256, 2) void unembed_logprob_kernel(
         const int row = j * 32 + l31;
         const float mx = fmaxf(fmaxf(red[(0 * ST_ROWS + row) * 3], red[(1 * ST_ROWS + row) * 3]),
                                fmaxf(red[(2 * ST_ROWS + row) * 3], red[(3 * ST_ROWS + row) * 3]));
-        const int64_t tg = j ? tg1 : tg0;
+        const int64_t tg64 = j ? tg1 : tg0;
+        // 32-bit compares below (a target outside [0, 512) matches no column): as 64-bit ones the 128 column constants sat in register
+        // pairs across both row tiles and the epilogue spilled
+        const int tg = (tg64 >= 0 && tg64 < ST_V) ? (int)tg64 : -1;
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -160,6 +177,27 @@ __global__ __launch_bounds__(256, 2) void unembed_logprob_kernel(
             red[(wave * ST_ROWS + row) * 3 + 2] = s2;
         }
     }
+    // ---- profile epilogue: column id = 128 w + 32 i + c sits in wave w, column tile i, half (c >> 2) & 1, register
+    //      r = (c & 3) + 4 (c >> 3) -- all wave-uniform, so finding the owner costs scalar compares only.  The owning lanes park the
+    //      rounded logit of their two rows in LDS, as the target's owner does in xt.
+    float* xs = xt + ST_ROWS;                                  // [row][ST_NSEL]
+    if constexpr (SEL) {
+#pragma unroll
+        for (int jj = 0; jj < ST_NSEL; ++jj) {
+            if (jj < sel.n && (sel.id[jj] >> 7) == wave) {
+                const int id = sel.id[jj];
+                const int ti = (id >> 5) & 3, r = (id & 3) + 4 * ((id >> 3) & 3);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    float v = acc[0][j][r];
+                    if (ti == 1) v = acc[1][j][r];
+                    if (ti == 2) v = acc[2][j][r];
+                    if (ti == 3) v = acc[3][j][r];
+                    if (half == ((id >> 2) & 1)) xs[(j * 32 + l31) * ST_NSEL + jj] = v;
+                }
+            }
+        }
+    }
     __syncthreads();
     if (tid < ST_ROWS && m0 + tid < M) {
         const int row = tid;
@@ -176,7 +214,25 @@ __global__ __launch_bounds__(256, 2) void unembed_logprob_kernel(
             const int64_t tg = target ? target[m0 + row] : -1;
             logprob[m0 + row] = (tg >= 0 && tg < ST_V) ? xt[row] - mx - logz : 0.f;
         }
+        if constexpr (SEL) {
+            float* out = sel_logprob + (m0 + row) * sel.n;
+#pragma unroll
+            for (int jj = 0; jj < ST_NSEL; ++jj)
+                if (jj < sel.n) out[jj] = xs[row * ST_NSEL + jj] - mx - logz;
+        }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void unembed_logprob_kernel(
+    const unsigned char* __restrict__ h, const unsigned char* __restrict__ emb, const int64_t* __restrict__ target,
+    float* __restrict__ logprob, float* __restrict__ entropy, int64_t M, int K) {
+    unembed_tail_body<false>(h, emb, target, logprob, entropy, M, K, st_sel_t{}, nullptr);
+}
+
+__global__ __launch_bounds__(256, 2) void unembed_profile_kernel(
+    const unsigned char* __restrict__ h, const unsigned char* __restrict__ emb, const int64_t* __restrict__ target,
+    float* __restrict__ logprob, float* __restrict__ entropy, int64_t M, int K, const st_sel_t sel, float* __restrict__ sel_logprob) {
+    unembed_tail_body<true>(h, emb, target, logprob, entropy, M, K, sel, sel_logprob);
 }
 
 extern "C" int evo_unembed_logprob_bf16(const void* hidden, const void* emb, const int64_t* target, float* logprob,
@@ -187,5 +243,26 @@ extern "C" int evo_unembed_logprob_bf16(const void* hidden, const void* emb, con
     if (tiles > 0x7fffffff) return -1;
     hipLaunchKernelGGL(unembed_logprob_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned char*)hidden, (const unsigned char*)emb, target, logprob, entropy, M, (int)K);
+    return evo_launch_status();
+}
+
+extern "C" int evo_unembed_profile_bf16(const void* hidden, const void* emb, const int64_t* target, const int32_t* sel, int64_t n_sel,
+                                        float* sel_logprob, float* logprob, float* entropy, int64_t M, int64_t V, int64_t K,
+                                        void* stream) {
+    if (M < 0 || V != ST_V || K <= 0 || K % ST_BK != 0 || K > 0x3fffffff) return -1;
+    if (n_sel < 1 || n_sel > ST_NSEL || !sel || !sel_logprob) return -1;
+    st_sel_t s{};
+    s.n = (int)n_sel;
+    for (int j = 0; j < s.n; ++j) {                             // HOST reads: ids in range, no id twice
+        if (sel[j] < 0 || sel[j] >= ST_V) return -1;
+        for (int q = 0; q < j; ++q)
+            if (sel[q] == sel[j]) return -1;
+        s.id[j] = sel[j];
+    }
+    if (M == 0) return 0;
+    const int64_t tiles = (M + ST_ROWS - 1) / ST_ROWS;
+    if (tiles > 0x7fffffff) return -1;
+    hipLaunchKernelGGL(unembed_profile_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)hidden, (const unsigned char*)emb, target, logprob, entropy, M, (int)K, s, sel_logprob);
     return evo_launch_status();
 }

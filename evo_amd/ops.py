@@ -56,13 +56,14 @@ _SIGNATURES = {
     "evo_gelu_gate_bf16": ([_PTR, _PTR, _I64, _I64, _PTR], _c.c_int),
     "evo_logprob_entropy": ([_PTR, _I64, _PTR, _PTR, _PTR, _I64, _I64, _PTR], _c.c_int),
     "evo_unembed_logprob_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR], _c.c_int),
+    "evo_unembed_profile_bf16": ([_PTR] * 3 + [_c.POINTER(_c.c_int32), _I64] + [_PTR] * 3 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_rope_append_decode_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR], _c.c_int),
     "evo_pool_rows_bf16": ([_PTR, _I64, _I64, _I64, _PTR, _I64, _PTR, _F32, _I64, _I64, _PTR, _PTR, _PTR], _c.c_int),
     "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 12        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 13        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 
 
 class EvoLibraryError(RuntimeError):
@@ -1058,6 +1059,54 @@ class HipOps:
             _check(self.lib.evo_unembed_logprob_bf16(h.data_ptr(), emb.data_ptr(), _ptr(target), _ptr(lp), _ptr(en),
                                                      M, V, K, _stream()), "evo_unembed_logprob_bf16")
         return lp, en
+
+    PROFILE_MAX_IDS = 8     # most vocabulary ids one profile launch takes (csrc/score_tail.hip ST_NSEL)
+
+    @staticmethod
+    def check_profile_ids(sel_ids, vocab: int = 512):
+        """The ids of a profile as a list of ints: 1 .. PROFILE_MAX_IDS distinct values in [0, vocab) -- ValueError otherwise (host
+        logic: what evo_unembed_profile_bf16 would answer with -1)."""
+        try:
+            ids = [int(i) for i in sel_ids]
+            exact = all(i == j for i, j in zip(ids, sel_ids))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"profile ids: expected a sequence of integers, got {sel_ids!r}") from e
+        if not exact:
+            raise ValueError(f"profile ids: expected integers, got {list(sel_ids)!r}")
+        if not 1 <= len(ids) <= HipOps.PROFILE_MAX_IDS:
+            raise ValueError(f"profile ids: expected 1 to {HipOps.PROFILE_MAX_IDS} ids, got {len(ids)}")
+        for i in ids:
+            if not 0 <= i < vocab:
+                raise ValueError(f"profile ids: id {i} is outside [0, {vocab})")
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"profile ids: an id is given twice in {ids}")
+        return ids
+
+    def unembed_profile(self, h: torch.Tensor, emb: torch.Tensor, sel_ids, target: Optional[torch.Tensor] = None,
+                        want_logprob=True, want_entropy=True):
+        """Fused scoring tail with a profile: h [M,K] bf16 (final-norm output) x emb[512,K]^T -> (sel_logprob [M, n] f32 = the
+        log-softmax at the n = len(sel_ids) chosen vocabulary ids of every row, logprob [M] f32 | None, entropy [M] f32 | None) in ONE
+        launch, without materialising the [M, 512] logits; logprob / entropy are unembed_logprob's, bit for bit.  `sel_ids`: a host
+        sequence of 1 .. 8 distinct ids in [0, 512) (ValueError otherwise)."""
+        ids = self.check_profile_ids(sel_ids, emb.shape[0])
+        self._need(h, torch.bfloat16, "unembed_profile h")
+        self._need(emb, torch.bfloat16, "unembed_profile emb")
+        if not self.unembed_logprob_ok(h, emb):
+            raise RuntimeError("unembed_profile: the fused tail does not take these operands (unembed_logprob_ok)")
+        M, K = h.shape
+        V = emb.shape[0]
+        sl = torch.empty(M, len(ids), dtype=torch.float32, device=h.device)
+        lp = torch.empty(M, dtype=torch.float32, device=h.device) if want_logprob else None
+        en = torch.empty(M, dtype=torch.float32, device=h.device) if want_entropy else None
+        if target is not None:
+            target = target.reshape(-1).to(torch.int64).contiguous()
+            assert target.numel() == M
+            self._need(target, torch.int64, "unembed_profile target")
+        sel = (_c.c_int32 * len(ids))(*ids)                      # HOST array: read by the entry point at launch
+        with self._t("unembed_profile"):
+            _check(self.lib.evo_unembed_profile_bf16(h.data_ptr(), emb.data_ptr(), _ptr(target), sel, len(ids), sl.data_ptr(),
+                                                     _ptr(lp), _ptr(en), M, V, K, _stream()), "evo_unembed_profile_bf16")
+        return sl, lp, en
 
     POOL_MODES = {"mean": 0, "last": 1}
     POOL_WORKGROUPS = 1024      # strips of all sequences together: 4 per CU (16 waves) -- 1 x 131,073 and 8 x 8,193 both reach it

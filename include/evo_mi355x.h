@@ -61,8 +61,10 @@ extern "C" {
  *      softmax_scale <= 0 = "queries pre-scaled" (the prefill attention kernel without its per-score multiply); evo_linear_small_m_bf16
  *      takes up to 64 rows and an optional workspace (`ws`, `ws_bytes`: split over K across workgroups for the narrow layers); evo_hyena_ct gained `y_row_pitch` (rows of y between two batch rows: the scoring path runs the 512 k main tokens
  *      of every row through the operator and the one token behind them through the single-token launch, see below).
- *  11: evo_pool_rows_bf16 added (sequence embeddings: masked row pooling with the final RMSNorm optionally fused in); no signature changed. */
-#define EVO_ABI_VERSION 12
+ *  11: evo_pool_rows_bf16 added (sequence embeddings: masked row pooling with the final RMSNorm optionally fused in); no signature changed.
+ *  12: evo_sample_rows_f32 added (seeded sampling on the device); no signature changed.
+ *  13: evo_unembed_profile_bf16 added (the fused scoring tail with the log-probs of up to 8 chosen vocabulary ids per row); no signature changed. */
+#define EVO_ABI_VERSION 13
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -362,6 +364,21 @@ int evo_logprob_entropy(const void* logits, int64_t logits_f32, const int64_t* t
  * and the softmax statistics are taken in fp32 on the rounded values.  V must be 512, K % 32 == 0. */
 int evo_unembed_logprob_bf16(const void* hidden, const void* emb, const int64_t* target,
                              float* logprob, float* entropy, int64_t M, int64_t V, int64_t K, void* stream);
+
+/* ---- fused scoring tail with a per-row profile: the log-probs of chosen vocabulary ids --------------------------
+ * replaces  log_softmax(x @ E^T)[:, sel]  next to the gather and the entropy above -- what a user asks of a DNA model at every
+ * position: the log-probability of A, C, G and T (substitution scores, the predicted base)   [REF evo/scoring.py:47-57,119-121]
+ * The same kernel body as evo_unembed_logprob_bf16 (k-loop, one bf16 rounding of every logit, fp32 max / sum-exp) with a second
+ * epilogue; hidden, emb, target, logprob, entropy, M, V, K exactly as there (target may be NULL; a target outside [0, 512) gives
+ * log-prob 0; logprob / entropy may be NULL), bit for bit the values that entry writes.
+ *   sel          n_sel int32 ids in HOST memory, read at launch: they travel in the kernel arguments, so there is no device buffer,
+ *                no device read and no alignment contract.  1 <= n_sel <= 8, every id in [0, 512), no id twice
+ *   sel_logprob  [M, n_sel] f32 row-major (16-byte aligned base; rows of n_sel * 4 bytes):
+ *                sel_logprob[m][j] = logit[m][sel[j]] - max_m - log sum_v exp(logit[m][v] - max_m), written for EVERY row, masked or not
+ * The [M, V] logits are never written to HBM.  Returns -1 before any launch for V != 512, K % 32 != 0, n_sel outside 1 .. 8, a NULL
+ * sel or sel_logprob, an id outside [0, 512) or a repeated id. */
+int evo_unembed_profile_bf16(const void* hidden, const void* emb, const int64_t* target, const int32_t* sel, int64_t n_sel,
+                             float* sel_logprob, float* logprob, float* entropy, int64_t M, int64_t V, int64_t K, void* stream);
 
 /* ---- sequence embeddings: masked row pooling (+ fused RMSNorm) --------------------------------------------
  * replaces the torch mean over positions of the hidden states that evo users take as embeddings (no reference kernel: upstream
