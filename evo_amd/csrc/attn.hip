@@ -17,7 +17,6 @@
 //   Ks [64 keys][128 d] bf16, 16-byte slot XOR-swizzled by (key & 15)      -> ds_read_b128 A fragments
 //   Vt [128 d][64 keys] bf16, 8-byte  slot XOR-swizzled by ((d >> 1) & 15) -> ds_read_b64  A fragments
 // Entry point and reference citation: include/evo_mi355x.h.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
@@ -314,9 +313,7 @@ __global__ __launch_bounds__(256, DECODE ? 1 : 2) void attn_fwd_kernel(AttnArgs 
 #define P_NSTG 4                        // 135,168 B of LDS: one workgroup per CU
 #define P_NDMA_K 17
 #define P_NDMA (17 + 16)
-#ifndef P_VD
 #define P_VD 4                          // V^T fragment prefetch distance, in MFMAs
-#endif
 
 typedef short tr_s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) tr_s16x4* lds_tr_ptr_t;
@@ -655,10 +652,6 @@ __global__ __launch_bounds__(256) void attn_decode_stream_kernel(AttnArgs a) {
     float o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#ifndef ATTN_DECODE_PIPE
-#define ATTN_DECODE_PIPE 1                   // 1 (round 6): 32-key half blocks, the next half's 16 requests in flight while this one is reduced; 0: whole 64-key blocks, load then compute
-#endif
-#if ATTN_DECODE_PIPE
     // A wave's blocks in HALVES of 32 keys (8 steps), double-buffered: the requests of half j + 1 go out before half j is reduced, so a
     // wave keeps 16-32 KiB in flight all the time.  (Whole blocks, loaded then reduced: at 8 k keys and 64 splits a wave has two blocks,
     // i.e. two exposed round trips with the CU's request queue draining while all its waves reduce -- 41 us for 134 MB, 3.3 TB/s.)
@@ -726,53 +719,6 @@ __global__ __launch_bounds__(256) void attn_decode_stream_kernel(AttnArgs a) {
             }
         }
     }
-#else
-    for (int blk = split; blk < nblk; blk += a.n_splits) {
-        const int64_t k0 = (int64_t)blk * 64 + ks;
-        uint4 kr[16], vr[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            int64_t key = k0 + 4 * i;
-            key = key < n_keys ? key : n_keys - 1;           // a ragged last block re-reads the last key (masked below)
-            kr[i] = ld16(kp, (uint32_t)key * kst + dco);
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            int64_t key = k0 + 4 * i;
-            key = key < n_keys ? key : n_keys - 1;
-            vr[i] = ld16(vp, (uint32_t)key * vst + dco);
-        }
-        float sc[16];
-        float mb = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            float d = attn_dot8(kr[i], qv);
-            d += __shfl_xor(d, 1, 64);
-            d += __shfl_xor(d, 2, 64);
-            d += __shfl_xor(d, 4, 64);
-            d += __shfl_xor(d, 8, 64);
-            sc[i] = k0 + 4 * i < n_keys ? d * a.scale_log2 : -INFINITY;
-            mb = fmaxf(mb, sc[i]);
-        }
-        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-        const float m_new = fmaxf(m_run, mb);                // finite: the block holds at least one key
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        l_run *= alpha;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] *= alpha;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float pw = __builtin_amdgcn_exp2f(sc[i] - m_new);
-            l_run += pw;
-            o[0] = fmaf(pw, bf_lo(vr[i].x), o[0]); o[1] = fmaf(pw, bf_hi(vr[i].x), o[1]);
-            o[2] = fmaf(pw, bf_lo(vr[i].y), o[2]); o[3] = fmaf(pw, bf_hi(vr[i].y), o[3]);
-            o[4] = fmaf(pw, bf_lo(vr[i].z), o[4]); o[5] = fmaf(pw, bf_hi(vr[i].z), o[5]);
-            o[6] = fmaf(pw, bf_lo(vr[i].w), o[6]); o[7] = fmaf(pw, bf_hi(vr[i].w), o[7]);
-        }
-        m_run = m_new;
-    }
-#endif
     // the four key groups of the wave meet (every lane of a group carries the same l)
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
@@ -870,13 +816,12 @@ extern "C" int evo_attn_fwd_causal_bf16(const void* q, const void* k, const void
     a.prescaled = softmax_scale <= 0.f ? 1 : 0;
     a.scale_log2 = a.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
     a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1;
-    // query ranges longer than one 128-row block take the 64-rows-per-wave kernel of csrc/attn_w64.hip; EVO_AMD_ATTN_FORM = 1 keeps
-    // them on the 8-wave pipelined kernel of rounds 2-4 (A/B measurements), 0 on the 128-row kernel
-    static const int form = [] { const char* e = getenv("EVO_AMD_ATTN_FORM"); return e ? atoi(e) : 2; }();
+    // query ranges longer than one 128-row block take the 64-rows-per-wave kernel of csrc/attn_w64.hip, or without its V^T workspace
+    // (vt_ws == NULL) the 8-wave pipelined kernel of rounds 2-4; shorter ones the 128-row kernel
     a.nbh = (int)(B * H);
     a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
-    if (form >= 2 && Tq > QB && vt_ws) return evo_attn_w64_launch(a, B, vt_ws, stream);
-    const int use_pipe = form >= 1 && Tq > QB;
+    if (Tq > QB && vt_ws) return evo_attn_w64_launch(a, B, vt_ws, stream);
+    const int use_pipe = Tq > QB;
     const int qblock = use_pipe ? PQB : QB;
     a.n_qblocks = (int)((Tq + qblock - 1) / qblock);
     const int64_t n_wg = (int64_t)a.n_qblocks * a.nbh;
@@ -907,9 +852,8 @@ extern "C" int evo_attn_decode_bf16(const void* q, const void* k, const void* v,
     a.n_qblocks = 1; a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
     a.dyn_pos = dyn_pos; a.part_o = part_o; a.part_ml = part_ml; a.n_splits = (int)n_splits; a.nbh = (int)(B * H);
     hipStream_t s = (hipStream_t)stream;
-    // EVO_ATTN_DECODE_FORM=0 keeps the MFMA split kernel (measurement builds); default: the streaming kernel, one split per wave
-    static const int form = [] { const char* e = getenv("EVO_ATTN_DECODE_FORM"); return e ? atoi(e) : 1; }();
-    if (form != 0 && Tk * k_st * 2 < 0xffffffffll && Tk * v_st * 2 < 0xffffffffll)
+    // the streaming kernel, one split per wave; its 32-bit key offsets need both caches below 4 GiB, beyond that the MFMA split kernel
+    if (Tk * k_st * 2 < 0xffffffffll && Tk * v_st * 2 < 0xffffffffll)
         hipLaunchKernelGGL(attn_decode_stream_kernel, dim3((unsigned)((n_splits + 3) / 4), (unsigned)H, (unsigned)B), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((unsigned)n_splits, (unsigned)H, (unsigned)B), dim3(256), 0, s, a);

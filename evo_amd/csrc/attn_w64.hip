@@ -48,7 +48,6 @@
 // LDS images: K [64 keys][272 B] (padded rows: b128 fragment reads conflict-free, per-lane base + immediates); V^T [128 d][128 B], the
 // 16-byte chunks of a row XOR-swizzled by ((d >> 1) & 7) on the DMA's source side (b128 fragment reads conflict-free, four per-lane
 // bases + immediates).
-#include <stdlib.h>
 #include <utility>
 #include "attn_common.h"
 #include "../../include/evo_mi355x.h"
@@ -67,10 +66,6 @@
 #ifndef W_THRP
 #define W_THRP 64.0f                        // PRE (pre-scaled queries): a row's reference point leaves 0 only beyond +-W_THRP log2 units
 #endif
-#ifndef W_EARLY
-#define W_EARLY 0                           // measurement knob (PRE only): 1 = the exp stream of a tile's FIRST 32 keys (80 of its 160 instructions) runs under the
-                                            // previous trip's P.V MFMAs, speculatively.  MEASURED SLOWER (profiles/r06_attn_notes.txt: 120.1 vs 116.9 ms at 1 x 131,073): see side_early
-#endif
 #ifndef W_PROFILE
 #define W_PROFILE 0                         // 1 (timing build, tools/attn_phase_profile.py): every wave accumulates shader clocks per trip segment and
                                             // writes them over its first output row's bytes: [resc, phase 1, between, phase 2, waits, barrier, trips]
@@ -80,14 +75,7 @@
 #else
 #define W_STAMP(K)
 #endif
-#ifndef W_VD
 #define W_VD 4                              // V^T fragments read ahead of their MFMAs (5+: the register file spills into AGPR copies)
-#endif
-// measurement builds (tools/attn_ablate.sh): W_ABL_NOEXP / NOSIDE / NOLDS / NODMA / NOBAR drop one ingredient of a trip (wrong results)
-#ifndef W_LSUM_MFMA
-#define W_LSUM_MFMA 0                       // 1: softmax denominators on the matrix pipe (8 more MFMAs per trip instead of 64 v_add_f32: measured 4 % SLOWER -- an MFMA costs its 32 pipe cycles, an add ~2.7)
-#endif
-#define W_NG_EARLY 4                        // exp groups (2 x 2 scores x ... = 14 instructions each) done under the previous trip's P.V
 
 typedef int w_srd_t __attribute__((ext_vector_type(4)));
 typedef unsigned int w_u32x4 __attribute__((ext_vector_type(4)));     // asm operands must be native vectors (a HIP uint4 is a struct)
@@ -125,15 +113,9 @@ __device__ __forceinline__ float w_xor32_add(float v) {
 #define W_MFMA_S(S, KF, QF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(S) : "a"(KF), "a"(QF))
 // the LAST k-step of a score tuple: D != C -- the sum accumulated in the work tuple WK lands in the exponent tuple E (a free copy)
 #define W_MFMA_SD(E, WK, KF, QF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %2, %3, %1" : "=v"(E) : "v"(WK), "a"(KF), "a"(QF))
-#define W_MFMA_L(L, ONES, PF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(L) : "v"(ONES), "v"(PF))
 #define W_DSR_K(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(DST) : "v"(ADDR), "n"(OFF))
-#ifdef W_V_AGPR             /* experiment: V^T fragments in AGPRs too */
-#define W_DSR_V(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(DST) : "v"(ADDR), "n"(OFF))
-#define W_MFMA_O(O, VF, PF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(O) : "a"(VF), "v"(PF))
-#else
 #define W_DSR_V(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
 #define W_MFMA_O(O, VF, PF) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(O) : "v"(VF), "v"(PF))
-#endif
 // (hipcc does not capture a local that a generic lambda names ONLY in asm operands: name it once outside of them)
 #define W_USE2(A, B) (void)(A), (void)(B)
 #define W_USE3(A, B, C) (void)(A), (void)(B), (void)(C)
@@ -142,21 +124,6 @@ __device__ __forceinline__ float w_xor32_add(float v) {
 // behind it, which puts it in its gap (an input does not make the recognizer pad anything; an asm OUTPUT read by the next instruction does).
 #define W_PIN(X) asm volatile("" ::"v"(X))
 #define W_LGKM(N) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory")
-#if defined(W_ABL_NOLDS) || defined(W_ABL_NOLDSK)          /* in-trip fragment reads and their waits off (the prologue's stay) */
-#define W_T_DSR_K(DST, ADDR, OFF) (void)0
-#else
-#define W_T_DSR_K W_DSR_K
-#endif
-#if defined(W_ABL_NOLDS) || defined(W_ABL_NOLDSV)
-#define W_T_DSR_V(DST, ADDR, OFF) (void)0
-#else
-#define W_T_DSR_V W_DSR_V
-#endif
-#if defined(W_ABL_NOLDS) || defined(W_ABL_NOLGKM)
-#define W_T_LGKM(N) (void)0
-#else
-#define W_T_LGKM W_LGKM
-#endif
 #define W_NOP24()                                                        \
     do {                                                                 \
         __builtin_amdgcn_sched_barrier(0);                               \
@@ -354,10 +321,9 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     float nm[2] = {0.f, 0.f};                     // -(reference point); 0 until the row has seen a key
     uint32_t seenm[2] = {0u, 0u};                // per lane: all ones once the row has a reference point (non-PRE) / has seen a key (PRE)
     float alpha[2] = {1.f, 1.f};                  // factor the pending tile applies to O and l when `resc`
-    // The softmax denominators ride on the matrix pipe: l^T[.][q] = ones . P^T, one more MFMA per 16-key group and query block (8 of
-    // 72 per trip) with an all-ones A fragment.  Every row of the 32 x 32 result holds the column sums of the bf16 P the numerator
-    // uses.  The wave is bound by instruction ISSUE, not by the pipe (profiles/r05_attn_w64_cycles_by_ablation.txt): 8 MFMA issues
-    // replace 64 v_add_f32 (+ the running-sum bookkeeping).
+    // The softmax denominators are summed in the VALU stream (l_run, psa / psb below).  On the matrix pipe -- l^T = ones . P^T, 8 more MFMAs per trip
+    // instead of 64 v_add_f32 -- they measured 4 % SLOWER: an MFMA costs its 32 pipe cycles, an add ~2.7.  lacc is what that form left behind: 32 AGPRs
+    // that are zeroed here and scaled with O on a rescale, never read; the shipped schedule was tuned with them in the register file (and with the phase-2 lambda capturing them), so they stay.
     f32x16_t lacc[2];                             // AGPRs
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
@@ -365,10 +331,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
         for (int r = 0; r < 16; ++r) lacc[x][r] = 0.f;
         asm volatile("" : "+a"(lacc[x]));
     }
-    const w_u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-#if !W_LSUM_MFMA
     float l_run[2] = {0.f, 0.f}, psa[2] = {0.f, 0.f}, psb[2] = {0.f, 0.f};
-#endif
     bool resc = false;                            // wave-uniform: some row of the wave moved its reference point for the pending tile
     const float c_sc = a.scale_log2;
 
@@ -379,43 +342,22 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     uint32_t pk[2][16];                           // bf16-packed P^T of the current tile [query block][4 * (16-key group) + word]
     w_u32x4 kf[4];                                // K fragments: a ring of four (see w_p1_ops): AGPRs
 
-    // ---- phase-1 stream: P = 2^e and the bf16 pack -- 96 instructions, in the order P.V consumes the words ---------------------------
+    // ---- phase-1 stream: P = 2^e, the row sums and the bf16 pack -- 160 instructions, in the order P.V consumes the words ---------------
     // unit u: 16-key group g = u >> 3, query block x = (u >> 2) & 1, word w = u & 3 (two scores);  group G = units 2G, 2G+1:
-    // 6 instructions: 4 x exp2, 2 x pack
+    // 10 instructions: 4 x exp2, 4 x add, 2 x pack
     float tp[4];
-#if W_LSUM_MFMA
-    auto exp_op = [&](const int G, const int o) __attribute__((always_inline)) {
-        const int which = o < 4 ? (o >> 1) : (o - 4);
-        const int u = 2 * G + which;
-        const int g = u >> 3, x = (u >> 2) & 1, w = u & 3;
-        const int r = 16 * (g >> 1) + 8 * (g & 1) + 2 * w;                     // index into ev[x]: 16 kt + register of the MFMA tile
-#ifdef W_ABL_EXPMUL
-        if (o < 4) { tp[o] = W_EL(x, r + (o & 1)) * c_sc; W_PIN(tp[o]); }
-#else
-        if (o < 4) { tp[o] = __builtin_amdgcn_exp2f(W_EL(x, r + (o & 1))); W_PIN(tp[o]); }
-#endif
-        else { pk[x][4 * g + w] = pack_bf2(tp[2 * which], tp[2 * which + 1]); W_PIN(pk[x][4 * g + w]); }
-    };
-
-#else
-    // (the form with the row sums in the VALU stream: 10 instructions per group -- 4 x exp2, 4 x add, 2 x pack; 160 per trip)
     auto exp_op = [&](const int G, const int o) __attribute__((always_inline)) {
         const int which = o < 8 ? ((o & 3) >> 1) : (o - 8);
         const int u = 2 * G + which;
         const int g = u >> 3, x = (u >> 2) & 1, w = u & 3;
         const int r = 16 * (g >> 1) + 8 * (g & 1) + 2 * w;
-#ifdef W_ABL_EXPMUL
-        if (o < 4) { tp[o] = W_EL(x, r + (o & 1)) * c_sc; W_PIN(tp[o]); }
-#else
         if (o < 4) { tp[o] = __builtin_amdgcn_exp2f(W_EL(x, r + (o & 1))); W_PIN(tp[o]); }
-#endif
         else if (o < 8) {
             const bool first_of_row = w == 0 && g == 0;
             if ((o & 1) == 0) { psa[x] = first_of_row ? tp[o - 4] : psa[x] + tp[o - 4]; W_PIN(psa[x]); }
             else { psb[x] = first_of_row ? tp[o - 4] : psb[x] + tp[o - 4]; W_PIN(psb[x]); }
         } else { pk[x][4 * g + w] = pack_bf2(tp[2 * which], tp[2 * which + 1]); W_PIN(pk[x][4 * g + w]); }
     };
-#endif
 
     // ---- phase-2 side stream on the NEXT tile's scores: exponents, row max, the reference-point bookkeeping --------------------------
     // every instruction is the compiler's own (it pads its hazards; fmaxf of FMA results needs no canonicalising v_max; the file is
@@ -446,7 +388,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     // The per-row decisions are written as 32-bit lane MASKS and bitwise arithmetic, not as bool expressions (round 6): from `a ? b : c` and
     // `a || b` on per-lane bools hipcc built s_and_saveexec / s_or exec regions, and every write of EXEC in the middle of the MFMA stream waits
     // for the matrix pipe to drain -- eight of them per trip cost ~660 of a trip's 3,880 cycles (tools/attn_phase_profile.py with
-    // -DW_ABL_NOBOOK: phase 2 1,715 -> 1,056 cycles; profiles/r06_attn_notes.txt).  Selects on masks are v_cmp + v_cndmask: no EXEC write.
+    // the bookkeeping compiled out: phase 2 1,715 -> 1,056 cycles; profiles/r06_attn_notes.txt).  Selects on masks are v_cmp + v_cndmask: no EXEC write.
     auto book_b = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int x = 0; x < 2; ++x) {
@@ -484,64 +426,28 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     };
     // side work of P.V gap j: 120 instructions spread at <= 4 per gap; the second-half score tuples (last written by the MFMAs of
     // phase-1 gaps 30 / 31) are first read in gap 8
-    // PRE + W_EARLY (an experiment that LOST, kept as a build knob with its number).  Hypothesis: phase 1 is the long pole -- 64 quarter-rate
-    // v_exp_f32 + ~100 other instructions of the exp stream beside 1,024 MFMA cycles, while phase 2 carries ~130 full-rate ones and, with
-    // the queries pre-scaled, not even the 64 fma (removing those alone bought only 0.7 %).  So half of the NEXT tile's exp stream moves
-    // here: its first 32 keys (tuples kt = 0, deposited 16+ gaps ago) are exponentiated under P.V of the current tile, in the P^T words P.V has
-    // already consumed (group g's words are free behind gap 8 g + 7) -- BEFORE the tile's row maximum is known.  That is safe because
-    // the reference point almost never moves (PRE: only beyond +-64 log2 units); when it does (`upd_any`, gap 28) the early words and
-    // row sums are simply formed again from the re-based exponents.  Correct (every attention test green) and 2.7 % SLOWER than W_EARLY 0 in
-    // the same process: the trip is not bound by where the exp stream sits -- see DESIGN 11.3.
-    //   gaps 0..6, 8..16   row max (kt = 0 elements first: the kt = 1 tuple was deposited in phase-1 gaps 30 / 31)
-    //   gaps 8..17         early exp of 16-key group 0  (40 instructions)        gaps 18..27  ... of group 1
-    //   gaps 17..20        the reference-point bookkeeping                          gap 28       rare: re-base + redo the early groups
-    auto side_early = [&](const int j) __attribute__((always_inline)) {
-        if (j < 7) { max_op(2 * j); max_op(2 * j + 1); }
-        else if (j >= 8 && j <= 16) { max_op(2 * (j - 1)); max_op(2 * (j - 1) + 1); }
-        if (j >= 8 && j <= 27) {
-            const int q = 4 * (j - 8);                                          // 80 instructions, four per gap: groups G = 0..7
-            exp_op(q / 10, q % 10); exp_op((q + 1) / 10, (q + 1) % 10); exp_op((q + 2) / 10, (q + 2) % 10); exp_op((q + 3) / 10, (q + 3) % 10);
-        }
-        if (j == 17) book_a();
-        else if (j == 18) book_b();
-        else if (j == 19) book_c();
-        else if (j == 20) book_d();
-        else if (j == 28) {
-            if (upd_any) {                          // rare: re-base the exponents of the rows that moved, then the early groups once more
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) W_EL(x, r) -= dl[x];
-                w_static_for<80>([&](auto qc) __attribute__((always_inline)) { W_USE3(S, pk, tp); exp_op(decltype(qc)::v / 10, decltype(qc)::v % 10); });
-            }
-        }
-    };
+    // (PRE: moving the exp stream of a tile's FIRST 32 keys under the previous trip's P.V MFMAs, speculatively -- before the tile's row maximum is
+    // known, redone when a reference point moves -- was correct and measured 2.7 % SLOWER, 120.1 vs 116.9 ms at 1 x 131,073
+    // (profiles/r06_attn_notes.txt): the trip is not bound by where the exp stream sits -- see DESIGN 11.3)
     auto side = [&](const int j) __attribute__((always_inline)) {
         // (no loops here: a loop that contains a pin is unrolled too late for the register promotion of S / ev)
-        if constexpr (PRE && W_EARLY && !W_LSUM_MFMA) { side_early(j); return; }
         if (j < 8) {                                // exponents of the first-half tuples (written >= 16 MFMAs ago); PRE: the scores ARE the exponents
             if constexpr (!PRE) { fma_op(0, 4 * j); fma_op(0, 4 * j + 1); fma_op(0, 4 * j + 2); fma_op(0, 4 * j + 3); }
         } else if (j < 16) {                        // ... of the second-half tuples
             if constexpr (!PRE) { fma_op(1, 4 * (j - 8)); fma_op(1, 4 * (j - 8) + 1); fma_op(1, 4 * (j - 8) + 2); fma_op(1, 4 * (j - 8) + 3); }
         } else if (j < 24) {                        // row max: 16 steps per query block
-#ifndef W_ABL_NOMAX
             max_op(4 * (j - 16)); max_op(4 * (j - 16) + 1); max_op(4 * (j - 16) + 2); max_op(4 * (j - 16) + 3);
-#endif
-#ifndef W_ABL_NOBOOK
         } else if (j == 24) { book_a();
         } else if (j == 25) { book_b();
         } else if (j == 26) { book_c();
         } else if (j == 27) { book_d();
-#endif
         } else if (j == 28) {
-#ifndef W_ABL_NOBOOK
             if (upd_any) {                          // rare (deferred max): re-base the exponents of the rows that moved
 #pragma unroll
                 for (int x = 0; x < 2; ++x)
 #pragma unroll
                     for (int r = 0; r < 32; ++r) W_EL(x, r) -= dl[x];
             }
-#endif
         }
     };
     auto mask_tile = [&](const int tile) __attribute__((always_inline)) {                                      // diagonal / ragged tiles only: S = -inf beyond the row's limit
@@ -606,24 +512,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
         W_NOP24();                                         // MFMA results -> the VALU below
         if (0 >= mask_from) mask_tile(0);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PRE && W_EARLY && !W_LSUM_MFMA) {
-            // tile 0: row max and bookkeeping first, then (re-based if a row moved) the early half of its exp stream -- nothing speculative here
-            w_static_for<32>([&](auto jc) __attribute__((always_inline)) {
-                constexpr int j = decltype(jc)::v;
-                if (j < 7) { max_op(2 * j); max_op(2 * j + 1); }
-                else if (j >= 8 && j <= 16) { max_op(2 * (j - 1)); max_op(2 * (j - 1) + 1); }
-            });
-            book_a(); book_b(); book_c(); book_d();
-            if (upd_any) {
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) W_EL(x, r) -= dl[x];
-            }
-            w_static_for<80>([&](auto qc) __attribute__((always_inline)) { W_USE3(S, pk, tp); exp_op(decltype(qc)::v / 10, decltype(qc)::v % 10); });
-        } else {
-            w_static_for<32>([&](auto jc) __attribute__((always_inline)) { side(decltype(jc)::v); });
-        }
+        w_static_for<32>([&](auto jc) __attribute__((always_inline)) { side(decltype(jc)::v); });
         resc = false;                                      // (O is still zero)
         const uint32_t kb1 = k_rd + 1 * W_KSTAGE;          // tile 1 -> K slot 1: its first-half fragments
         w_static_for<4>([&](auto jc) __attribute__((always_inline)) { W_USE2(kf, kb1); constexpr int ks = decltype(jc)::v; W_DSR_K(kf[ks], kb1, ks * 32); });
@@ -682,58 +571,34 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
             constexpr int kt = i >> 4, ks = (i >> 1) & 7, x = i & 1;
             constexpr bool dma = (i % 3) == 1 && i < 27;   // gaps 1, 4, ..., 25 -> pieces 0..8 (0-4: K, 5-8: V; K piece 4 exists in wave 0 only)
             constexpr int pc = i / 3;
-#ifndef W_ABL_NODMA
             if (dma) {                                     // m0 at the head of the gap, the load at its end: the MFMA between them is the wait state
                 if (pc < 4) W_M0P(kslot, pc);
                 else if (pc == 4) { if (wave == 0) W_M0P(kslot, pc); }
                 else W_M0P(vslot, pc);
             }
-#endif
             constexpr int f = i >> 1;                     // K fragment of this MFMA
-            if (f >= 4 && x == 0) W_T_LGKM(w_wait_k1(f));
+            if (f >= 4 && x == 0) W_LGKM(w_wait_k1(f));
             if (ks == 0) W_MFMA_S0(WK[x], kf[f & 3], qf[x][ks]);
             else if (ks < 7) W_MFMA_S(WK[x], kf[f & 3], qf[x][ks]);
             else W_MFMA_SD(S[x][kt], WK[x], kf[f & 3], qf[x][ks]);   // deposit: tile t's exponents of half kt were last read in gap 16 kt + 14
-            if (x == 1 && f + 4 < 16) W_T_DSR_K(kf[f & 3], kb, ((f + 4) >> 3) * (32 * W_KROW) + ((f + 4) & 7) * 32);
+            if (x == 1 && f + 4 < 16) W_DSR_K(kf[f & 3], kb, ((f + 4) >> 3) * (32 * W_KROW) + ((f + 4) & 7) * 32);
             if (i >= 32 - 2 * W_VD && (i & 1) == 0) {     // the first W_VD V^T fragments of P.V(tile)
                 constexpr int p = (i - (32 - 2 * W_VD)) >> 1;
-#ifdef W_ABL_VADDRK
-                W_T_DSR_V(vfr[p], kb, (p & 3) * 32);
-#else
-                W_T_DSR_V(vfr[p], vb[p >> 2], (p & 3) * 4096);
-#endif
+                W_DSR_V(vfr[p], vb[p >> 2], (p & 3) * 4096);
             }
-            // three instructions of the exp stream per gap (96 = 32 x 3)
-#ifndef W_ABL_NOEXP
-#if W_LSUM_MFMA
-            exp_op((3 * i) / 6, (3 * i) % 6); exp_op((3 * i + 1) / 6, (3 * i + 1) % 6); exp_op((3 * i + 2) / 6, (3 * i + 2) % 6);
-#else
-            if constexpr (PRE && W_EARLY) {
-                // the tile's LAST 32 keys only (groups G = 8..15: the first 32 went under the previous trip's P.V): 80 instructions, three
-                // per gap -- done by gap 26, the tuples they read are overwritten by the deposits of gaps 30 / 31
-                if constexpr (3 * i < 80) exp_op(8 + (3 * i) / 10, (3 * i) % 10);
-                if constexpr (3 * i + 1 < 80) exp_op(8 + (3 * i + 1) / 10, (3 * i + 1) % 10);
-                if constexpr (3 * i + 2 < 80) exp_op(8 + (3 * i + 2) / 10, (3 * i + 2) % 10);
-            } else {
-                exp_op((5 * i) / 10, (5 * i) % 10); exp_op((5 * i + 1) / 10, (5 * i + 1) % 10); exp_op((5 * i + 2) / 10, (5 * i + 2) % 10);
-                exp_op((5 * i + 3) / 10, (5 * i + 3) % 10); exp_op((5 * i + 4) / 10, (5 * i + 4) % 10);
-            }
-#endif
-#endif
-#ifndef W_ABL_NODMA
+            // five instructions of the exp stream per gap (160 = 32 x 5)
+            exp_op((5 * i) / 10, (5 * i) % 10); exp_op((5 * i + 1) / 10, (5 * i + 1) % 10); exp_op((5 * i + 2) / 10, (5 * i + 2) % 10);
+            exp_op((5 * i + 3) / 10, (5 * i + 3) % 10); exp_op((5 * i + 4) / 10, (5 * i + 4) % 10);
             if (dma) {
                 if (pc < 4) W_LD_K(ksrd, pc);
                 else if (pc == 4) { if (wave == 0) W_LD_K(ksrd, pc); }
                 else W_LD_V(vsrd, pc - 5);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         });
         W_STAMP(1);
-#if !W_LSUM_MFMA
 #pragma unroll
         for (int x = 0; x < 2; ++x) l_run[x] = fmaf(l_run[x], alpha[x], psa[x] + psb[x]);
-#endif
         if (mask_nxt || (PRE && any_nm)) {                 // rare: the diagonal / ragged tile's mask; PRE: rows that left the reference point 0
             W_NOP24();
             if (mask_nxt) mask_tile(tile + 1);
@@ -748,29 +613,20 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
         w_srd_t ksrd_n = ksrd, vsrd_n = vsrd;
         bool mask_nxt_n = false;
         w_static_for<32>([&](auto jc) __attribute__((always_inline)) {
-            W_USE3(kf, oacc, kb2); W_USE3(vb, vfr, pk); W_USE2(S, nm); W_USE2(lacc, ones);
+            W_USE3(kf, oacc, kb2); W_USE3(vb, vfr, pk); W_USE2(S, nm); (void)lacc;
             constexpr int j = decltype(jc)::v;
             constexpr int p = j >> 1, x = j & 1;
             constexpr int g = p >> 2, dt = p & 3;
-            if (x == 0) W_T_LGKM(w_wait_v(p));
+            if (x == 0) W_LGKM(w_wait_v(p));
             w_u32x4 pf;
             pf.x = pk[x][4 * g]; pf.y = pk[x][4 * g + 1]; pf.z = pk[x][4 * g + 2]; pf.w = pk[x][4 * g + 3];
             W_MFMA_O(oacc[x][dt], vfr[p % (W_VD + 1)], pf);
-#if W_LSUM_MFMA && !defined(W_ABL_NOLSUM)
-            if (dt == 3) W_MFMA_L(lacc[x], ones, pf);     // the group's column sums (its P^T fragment is in registers now)
-#endif
             if (x == 0 && p + W_VD < 16) {
                 constexpr int pp = p + W_VD;
-#ifdef W_ABL_VADDRK
-                W_T_DSR_V(vfr[pp % (W_VD + 1)], kb2, (pp & 3) * 32);
-#else
-                W_T_DSR_V(vfr[pp % (W_VD + 1)], vb[pp >> 2], (pp & 3) * 4096);
-#endif
+                W_DSR_V(vfr[pp % (W_VD + 1)], vb[pp >> 2], (pp & 3) * 4096);
             }
-            if (j >= 10 && j <= 22 && ((j - 10) & 3) == 0) W_T_DSR_K(kf[(j - 10) >> 2], kb2, ((j - 10) >> 2) * 32);
-#ifndef W_ABL_NOSIDE
+            if (j >= 10 && j <= 22 && ((j - 10) & 3) == 0) W_DSR_K(kf[(j - 10) >> 2], kb2, ((j - 10) >> 2) * 32);
             side(j);
-#endif
             // the next trip's setup, a few scalar instructions per gap (pinned: they would otherwise collect at the head of the loop)
             if (j == 3) { kb2 = k_rd + (uint32_t)((tile + 2) & (W_NK - 1)) * W_KSTAGE; W_PIN(kb2); }      // = the next trip's kb
             if (j == 5) { v_idx_n = v_idx == W_NV - 1 ? 0 : v_idx + 1; W_PIN_S(v_idx_n); }
@@ -789,14 +645,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
         for (int g = 0; g < 4; ++g) vb[g] = vb_n[g];
         // tile+1's V and tile+3's K must have landed before the next trip (this trip's pieces may stay in flight); every LDS read of
         // this trip has returned (the K fragments of the next trip's first MFMAs among them)
-        W_T_LGKM(0);
-#ifndef W_ABL_NODMA
+        W_LGKM(0);
         W_WAIT(1);
-#endif
         W_STAMP(4);
-#ifndef W_ABL_NOBAR
         W_BARRIER();
-#endif
         W_STAMP(5);
     }
 
@@ -805,11 +657,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     // ---- epilogue: normalise; the two halves of a row trade 8-byte pieces so that every lane stores 16 contiguous bytes -------------------
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
-#if W_LSUM_MFMA
-        const float l_tot = lacc[x][0];                                         // (every row of l^T holds the column's sum over all keys)
-#else
         const float l_tot = w_xor32_add(l_run[x]);
-#endif
         const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
         const bool ok = x == 0 ? row_ok0 : row_ok1;
         uint16_t* orow = a.o + ((int64_t)(bat * a.Tq + (x == 0 ? orow_first : orow_second)) * a.H + head) * DH;

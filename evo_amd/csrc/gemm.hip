@@ -22,7 +22,6 @@
 // Workgroups are numbered so that each XCD (private L2) sweeps a contiguous,
 // group_m-rastered range of output tiles.
 // Entry point and reference citation: include/evo_mi355x.h.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
@@ -315,46 +314,10 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_kernel(GemmArgs a) {
 // Epilogue (round 3): the W rows sit in the LDS slab in a relabelled order that makes a lane's accumulators of an n-tile pair
 // eight consecutive output columns; results go from registers to memory as whole 128-byte lines, no LDS, no barrier
 // (profiles/r03_gemm_notes.txt: 97-99 % of hipBLASLt on the model's four layer shapes).
-#ifndef GR_DGAP
 #define GR_DGAP 8                            // gaps between the DMA pieces of a half step (8 pieces: 8 = spread over all 64 gaps, 4 = first 32)
-#endif
-#ifndef GE_ORDER
-#define GE_ORDER 1                           // epilogue unit order: 1 = the four 64-byte quarters of a row pair back to back (L2 merges them into whole lines)
-#endif
-#ifndef GE_FULL
-#define GE_FULL 1                            // 1: strips stored pairwise as whole 128-byte lines (needs GE_ORDER 1)
-#endif
-static_assert(!GE_FULL || GE_ORDER == 1, "GE_FULL pairs the strips of GE_ORDER 1");
 // epilogue units: 32 per wave tile, unit = (strip b of 32 output columns, m tile j of 16 rows)
-#if GE_ORDER == 0
-#define GE_B(U) ((U) >> 3)                   /* unit U = (strip b = U >> 3, m tile j = U & 7) */
-#define GE_J(U) ((U) & 7)
-#else
-#define GE_B(U) ((U) & 3)                    /* unit U = (m tile j = U >> 2, strip b = U & 3): the four 64-byte quarters of a row pair back to back */
+#define GE_B(U) ((U) & 3)                    /* unit U = (m tile j = U >> 2, strip b = U & 3): the four 64-byte quarters of a row pair back to back (L2 merges them into whole lines) */
 #define GE_J(U) ((U) >> 2)
-#endif
-
-#ifndef GE_STPOL_ID
-#define GE_STPOL_ID 0                        // cache policy of the epilogue's stores: 0 default, 1 nt, 2 sc1, 3 sc0 sc1
-#endif
-#if GE_STPOL_ID == 1
-#define GE_STPOL " nt"
-#elif GE_STPOL_ID == 2
-#define GE_STPOL " sc1"
-#elif GE_STPOL_ID == 3
-#define GE_STPOL " sc0 sc1"
-#else
-#define GE_STPOL ""
-#endif
-#ifndef GR_MIDB
-#define GR_MIDB 1                            // 1: the stage barrier behind the first MFMA of half 1; 0: in front of it
-#endif
-#ifndef GR_PAD
-#define GR_PAD 0
-#endif
-#ifndef GR_ALIGN
-#define GR_ALIGN 0
-#endif
 #ifndef GR_PROFILE
 #define GR_PROFILE 0                         // 1: wave 0 of workgroup 0 accumulates cycles per loop segment, written over y (tools/gemm_stage_profile.py)
 #endif
@@ -500,9 +463,6 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
     // scalar instructions in one gap (the first form of this bookkeeping) idles the matrix pipe for 40-70 cycles.  Past the
     // last tile the cursor re-enters the last origin it knew (harmless re-fetches of valid rows keep the vmcnt counts constant).
 #define GD_M0(V) asm volatile("s_mov_b32 m0, %0" ::"s"(V) : "memory", "m0")
-#ifndef GR_ABL
-#define GR_ABL 0                             // ablation bits (measurement builds only): 1 no in-loop DMA, 2 no in-loop barrier, 8 no in-loop fragment reads, 16 no M0 writes
-#endif
 #define GD_DMAX(JJ) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff[JJ]), "s"(rx), "s"(fxs) : "memory")
 #define GD_DMAW(JJ) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(wvoff[JJ]), "s"(rw), "s"(fws) : "memory")
 
@@ -572,12 +532,12 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
         constexpr int g_ = (G), s_ = g_ & 63;                                                                 \
         /* the stage barrier sits BEHIND the first MFMA of half 1 (its operands are in registers): the matrix pipe works  */ \
         /* through that MFMA while the wave waits for the others                                                          */ \
-        if constexpr (g_ == 64 && GR_MIDB) { G_VMCNT(8); if (!(GR_ABL & 2)) G_BARRIER(); }                    \
-        if constexpr ((s_ & 1) == 0 && s_ < 32 && !(GR_ABL & 8)) { GR_RD1(RXO, RWO, RKH, RBUF, s_ >> 1); }    \
-        if constexpr (g_ < 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == 1 && !(GR_ABL & 16)) GD_M0(fxl + (s_ / GR_DGAP) * 4096);        \
-        if constexpr (g_ < 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == GR_DGAP / 2 + 1 && !(GR_ABL & 1)) GD_DMAX(s_ / GR_DGAP);       \
-        if constexpr (g_ >= 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == 1 && !(GR_ABL & 16)) GD_M0(fwl + (s_ / GR_DGAP) * 4096);       \
-        if constexpr (g_ >= 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == GR_DGAP / 2 + 1 && !(GR_ABL & 1)) GD_DMAW(s_ / GR_DGAP);      \
+        if constexpr (g_ == 64) { G_VMCNT(8); G_BARRIER(); }                                                      \
+        if constexpr ((s_ & 1) == 0 && s_ < 32) { GR_RD1(RXO, RWO, RKH, RBUF, s_ >> 1); }                     \
+        if constexpr (g_ < 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == 1) GD_M0(fxl + (s_ / GR_DGAP) * 4096);                          \
+        if constexpr (g_ < 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == GR_DGAP / 2 + 1) GD_DMAX(s_ / GR_DGAP);                        \
+        if constexpr (g_ >= 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == 1) GD_M0(fwl + (s_ / GR_DGAP) * 4096);                         \
+        if constexpr (g_ >= 64 && s_ < 8 * GR_DGAP && (s_ % GR_DGAP) == GR_DGAP / 2 + 1) GD_DMAW(s_ / GR_DGAP);                       \
         /* scalar bookkeeping of the NEXT k-step, <= 3 instructions per gap, in gaps that carry no memory instruction and no   */ \
         /* M0 write (half 1: this k-step's X pieces are out; the W pieces end at gap 125; slot offsets are dead once read).    */ \
         if constexpr (g_ == 67) { fxp = fxs + XSTEP; fwp = fws + GBK * 2; GS_PIN2(fxp, fwp); }              \
@@ -648,14 +608,6 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
     //        half 1 (k 32..63)  64 MFMAs + the first fragment reads of stage g+1 + DMA W(g+2) -> slot sl (held X(g))
     uint32_t xo = 0, wo = G_SLAB, nxo = 2 * G_SLAB, nwo = 3 * G_SLAB, fxo = 4 * G_SLAB;     // slot byte offsets of stage g: X, W; stage g+1: X, W; free
     uint32_t fxl = lds_dma + 4 * G_SLAB, fwl = lds_dma, r_t0 = 0, r_t1 = 0;
-    // code-placement knobs (measurement builds; MI355X_MICROARCH.md "code-placement sensitivity of hand-written streams"): GR_PAD shifts the
-    // whole stage stream by 4-byte s_nop's, GR_ALIGN pins the head of the tile loop to a 2^GR_ALIGN-byte boundary
-#if GR_PAD
-    asm volatile(".rept %0\n\ts_nop 0\n\t.endr" :: "n"(GR_PAD));
-#endif
-#if GR_ALIGN
-    asm volatile(".p2align %0" :: "n"(GR_ALIGN));
-#endif
     for (int c_i = 0; c_i < n_my; ++c_i) {
 #define GR_KSTEP()                                                                                            \
         {                                                                                                     \
@@ -665,7 +617,6 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
             GR_STAMP(0);                                                                                      \
             GR_LGKM(0, 1);                                       /* the second half's fragments: stage g is fully read */ \
             GR_STAMP(1);                                                                                      \
-            if (!GR_MIDB) { G_VMCNT(8); GR_STAMP(2); if (!(GR_ABL & 2)) G_BARRIER(); }                        \
             GR_STAMP(6);                                                                                      \
             GR_SUB(1, 1, nxo, nwo, 0, 0);                                                                     \
             GR_STAMP(3);                                                                                      \
@@ -744,8 +695,8 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
                         s2[d] = low ? recv : gq[1][d];
                     }
                     const int so = n0 + j * ep_grows16;            // (n0 / 2 gated columns x 2 bytes)
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" GE_STPOL :: "v"(s1), "v"(ep_voff_g), "s"(yd), "s"(so) : "memory");
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" GE_STPOL :: "v"(s2), "v"(ep_voff_g), "s"(yd), "s"(so + ep_grows16 / 2) : "memory");
+                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" :: "v"(s1), "v"(ep_voff_g), "s"(yd), "s"(so) : "memory");
+                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" :: "v"(s2), "v"(ep_voff_g), "s"(yd), "s"(so + ep_grows16 / 2) : "memory");
                     if (j >= 3) { asm volatile("" :: "v"(ost[(2 * j + 2) & 7])); asm volatile("" :: "v"(ost[(2 * j + 3) & 7])); }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -851,7 +802,6 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
                 if constexpr (STATS) {
                     // squares of the ROUNDED values (what the next RMSNorm reads from memory); unit order u = 4 j + b: the four units of
                     // an m tile are consecutive, one running sum is live
-                    static_assert(GE_ORDER == 1, "the statistic closes an m tile at b == 3");
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         const float lo_ = bf_lo(o[d]), hi_ = bf_hi(o[d]);
@@ -869,7 +819,6 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
                         ssq = 0.f;
                     }
                 }
-#if GE_FULL
                 // A store instruction costs the wave ~270 cycles whatever it carries (measured: 16 rows x 64 B and 16 rows x 32 B
                 // alike) -- it is paid per row segment.  So two strips are stored together as WHOLE 128-byte lines, 8 rows per
                 // instruction: lanes l15 < 8 and their partners l15 + 8 swap one quad (DPP row_ror:8), after which instruction 1
@@ -885,17 +834,10 @@ __global__ __launch_bounds__(256, 1) void gemmr_bf16_kernel(GemmArgs a) {
                         s1[d] = low ? o_even[d] : recv;
                         s2[d] = low ? recv : o[d];
                     }
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" GE_STPOL :: "v"(s1), "v"(ep_voff_f), "s"(yd), "s"(GE_SOFF(u - 1)) : "memory");
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" GE_STPOL :: "v"(s2), "v"(ep_voff_f), "s"(yd), "s"(GE_SOFF(u - 1) + ep_rows16 / 2) : "memory");
+                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" :: "v"(s1), "v"(ep_voff_f), "s"(yd), "s"(GE_SOFF(u - 1)) : "memory");
+                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" :: "v"(s2), "v"(ep_voff_f), "s"(yd), "s"(GE_SOFF(u - 1) + ep_rows16 / 2) : "memory");
                     if (u >= 7) { asm volatile("" :: "v"(ost[(u + 1) & 7])); asm volatile("" :: "v"(ost[(u + 2) & 7])); }
                 }
-#else
-                // A store reads its data registers when the memory pipeline gets to it, not at issue: the packed results rotate
-                // through eight register quads (kept allocated by the empty asm)
-                ost[u & 7] = o;
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" GE_STPOL :: "v"(ost[u & 7]), "v"(ep_voff), "s"(yd), "s"(GE_SOFF(u)) : "memory");
-                if (u >= 7) asm volatile("" :: "v"(ost[(u + 1) & 7]));
-#endif
                 if (RES && u + GE_NR < 32) GE_LOAD(u + GE_NR);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -994,8 +936,7 @@ extern "C" int evo_linear_mfma_nf_bf16(const void* x, const void* w, const void*
                                        const float* row_scale, float* sumsq, int64_t ss_ld, int64_t M, int64_t N, int64_t K, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0 || N % GBN != 0 || K % GBK != 0) return -1;
     if ((row_scale && (residual || sumsq)) || (sumsq && (!residual || ss_ld < (M + GBM - 1) / GBM * GBM))) return -1;
-    static const int form = [] { const char* e = getenv("EVO_GEMM_FORM"); return e ? atoi(e) : 1; }();   // 1: persistent, 0: tile per workgroup
-    const bool persistent = form == 1 && persistent_shape_ok(M, N, K);
+    const bool persistent = persistent_shape_ok(M, N, K);     // otherwise: a tile per workgroup (gemm_bf16_kernel)
     if ((row_scale || sumsq) && !persistent) return -1;         // the folded norm exists in the persistent kernel only: never fall through to a launch that ignores it
     GemmArgs a;
     if (!gemm_fill(a, x, w, bias, residual, y, M, N, K)) return -1;

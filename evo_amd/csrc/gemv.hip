@@ -730,103 +730,14 @@ __global__ __launch_bounds__(512) void skinny_mfma_kernel(const uint4* __restric
 // ---- 5 <= M <= 64, N >= 8192: n-split form (round 6).  The k-split form above is bound by L2, not by HBM: every weight fragment (1 KiB per
 // wave) pulls MT x fragments of the same size through L2 -- weights + x add up to 6-7 TB/s at every M (4.0 TB/s of weights at 8 rows, 3.4 at
 // 16, 2.2 at 32, 1.5 at 64; tools/bench_gemv.py) where hipBLASLt streams 4.2 TB/s at 32-64 rows.  Here a workgroup is WAVES waves, each owning a
-// 16-row n tile for the WHOLE K (no partial sums, no reduction), and the x rows of a 256-k chunk are staged in LDS once per workgroup and
-// read by all its waves as B fragments (ds_read_b128, conflict-free at a row pitch of 528 B): x costs L2 MT / WAVES of the weight bytes
-// instead of MT.  Weight fragments of chunk c + 1 and the x rows of chunk c + 1 are requested before chunk c is multiplied.  K % 256 == 0.
-template <int MT, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void skinny_n_kernel(const uint4* __restrict__ x, const uint4* __restrict__ w,
-                                                              const uint16_t* __restrict__ bias, const uint16_t* res,
-                                                              uint16_t* y, int M, int N, int nvec) {   // res may alias y
-    constexpr int KC = 8, ROWB = KC * 64 + 16;                   // steps per chunk; LDS bytes per x row (512 + 16 pad)
-    constexpr int XL = (MT * 16 * KC * 4 + 64 * WAVES - 1) / (64 * WAVES);   // 16-byte pieces of an x chunk per thread
-    __shared__ __attribute__((aligned(16))) unsigned char xs[2][MT * 16 * ROWB];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r16 = lane & 15, kb = lane >> 4;
-    const int n0 = (blockIdx.x * WAVES + wave) * 16;
-    const int nrow = n0 + r16 < N ? n0 + r16 : N - 1;
-    const uint4* wp = w + (int64_t)nrow * nvec + kb;
-    const int n_chunk = nvec / (KC * 4);
-    gv_f32x4 acc[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = gv_f32x4{0.f, 0.f, 0.f, 0.f};
-    // x chunk pieces of this thread: piece p = tid + i * threads -> row p / 32 (32 pieces of 16 B per 512-byte row), column p % 32
-    // (native vectors, not HIP's uint4 struct: as a loop-carried, conditionally written array of uint4 the pieces stayed in scratch memory)
-    typedef unsigned int sn_u32x4 __attribute__((ext_vector_type(4)));
-    sn_u32x4 xr[XL];
-#define SN_X_LOAD(C)                                                                                          \
-    _Pragma("unroll") for (int i_ = 0; i_ < XL; ++i_) {                                                       \
-        const int pidx_ = tid + i_ * 64 * WAVES;                                                              \
-        int row_ = pidx_ >> 5;                                                                                \
-        row_ = row_ < M ? row_ : M - 1;              /* rows past M (and pieces past the chunk) re-read a valid row: never stored */ \
-        xr[i_] = *(const sn_u32x4*)(x + (int64_t)row_ * nvec + (C) * (KC * 4) + (pidx_ & 31));               \
-    }
-#define SN_X_STORE(BUF)                                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < XL; ++i_) {                                                       \
-        const int pidx_ = tid + i_ * 64 * WAVES;                                                              \
-        if (pidx_ < MT * 16 * 32) *(sn_u32x4*)(xs[BUF] + (pidx_ >> 5) * ROWB + (pidx_ & 31) * 16) = xr[i_];   \
-    }
-#ifndef SN_PROBE_CONTIG
-#define SN_PROBE_CONTIG 0                    // measurement only (WRONG results): weight fragments read as if stored fragment-major, 1 KiB contiguous per request
-#endif
-    auto w_load = [&](int c, uint4 (&wf)[KC]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < KC; ++u)
-            wf[u] = SN_PROBE_CONTIG ? ld_stream(w + ((int64_t)(n0 >> 4) * (nvec >> 2) + c * KC + u) * 64 + lane) : ld_stream(wp + 4 * (c * KC + u));
-    };
-    auto mul = [&](int buf, const uint4 (&wf)[KC]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int u = 0; u < KC; ++u)
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const uint4 xv = *(const uint4*)(xs[buf] + (16 * t + r16) * ROWB + u * 64 + kb * 16);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[u]), __builtin_bit_cast(bf16x8_t, xv), acc[t], 0, 0, 0);
-            }
-    };
-    // weight fragments: chunk c multiplies while c + 1 is in flight (a ring of three -- 16 KiB per wave in flight -- measured 5-8 % SLOWER: the form is
-    // not latency-bound; what caps it is the access pattern, 64-byte pieces of 16 rows per request: read as if the weight were stored fragment-major
-    // (1 KiB contiguous per request, SN_PROBE_CONTIG) the same kernel streams 4.3-4.4 TB/s at 17-32 rows, hipBLASLt's rate, instead of 3.1-3.3)
-    uint4 wA[KC], wB[KC];
-    SN_X_LOAD(0);
-    w_load(0, wA);
-    SN_X_STORE(0);
-    __syncthreads();
-#define SN_STAGE(C, WCUR, WNEXT, BUF)                                                                         \
-    if ((C) < n_chunk) {                                                                                      \
-        if ((C) + 1 < n_chunk) { SN_X_LOAD((C) + 1); w_load((C) + 1, WNEXT); }                                \
-        mul(BUF, WCUR);                                                                                       \
-        if ((C) + 1 < n_chunk) { SN_X_STORE((BUF) ^ 1); }                                                     \
-        __syncthreads();                                                                                      \
-    }
-    for (int c = 0; c < n_chunk; c += 2) {                       // two chunks per trip: the fragment sets alternate without register copies
-        SN_STAGE(c, wA, wB, 0) SN_STAGE(c + 1, wB, wA, 1)
-    }
-#undef SN_STAGE
-#undef SN_X_LOAD
-#undef SN_X_STORE
-    // D[n][m]: lane holds n = n0 + 4 kb + r, m = 16 t + r16 -- four consecutive output columns of its row
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-        const int m = 16 * t + r16;
-        if (m < M) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + 4 * kb + r;
-                if (n < N) {
-                    float o = acc[t][r] + (bias ? bf_to_f(bias[n]) : 0.f);
-                    if (res) o += bf_to_f(res[(int64_t)m * N + n]);
-                    y[(int64_t)m * N + n] = f_to_bf(o);
-                }
-            }
-        }
-    }
-}
-
-// ---- the n-split form with CONTIGUOUS weight requests (round 6, second step).  skinny_n_kernel asks for a weight fragment as the MFMA wants it: 64 bytes
-// of each of 16 rows that lie K * 2 bytes apart -- and streams 3.1-3.3 TB/s where the same kernel reading 1 KiB contiguous per request runs 4.3-4.4
-// (profiles/r06_small_m_nsplit_ab.txt).  Here a request covers RPI = 2 (4) whole row pieces of 512 (256) contiguous bytes, the wave parks the chunk in a
-// PRIVATE LDS region in row order and reads its fragments back from there (ds_write_b128 / ds_read_b128, both conflict-free at the padded row pitch);
-// the requests of chunk c + 1 are in flight while chunk c multiplies.  Everything else as skinny_n_kernel.
+// 16-row n tile for the WHOLE K (no partial sums, no reduction), and the x rows of a chunk of KC MFMA steps are staged in LDS once per workgroup and
+// read by all its waves as B fragments (ds_read_b128, conflict-free at the padded row pitch): x costs L2 MT / WAVES of the weight bytes
+// instead of MT.  K % 256 == 0.
+// The weight requests are CONTIGUOUS.  Asked for as the MFMA wants it -- 64 bytes of each of 16 rows that lie K * 2 bytes apart -- a weight fragment
+// streams 3.1-3.3 TB/s where 1 KiB contiguous per request runs 4.3-4.4 (profiles/r06_small_m_nsplit_ab.txt; a ring of three fragment sets in flight
+// measured 5-8 % SLOWER: the form is not latency-bound, what caps it is the access pattern).  So a request covers RPI = 2 (4) whole row pieces of
+// 512 (256) contiguous bytes, the wave parks the chunk in a PRIVATE LDS region in row order and reads its fragments back from there (ds_write_b128 /
+// ds_read_b128, both conflict-free at the padded row pitch); the requests of chunk c + 1 (weights and x rows) are in flight while chunk c multiplies.
 // SPLITK (N < 8192, the two N = 4,096 layers of a block): blockIdx.y is a slice of the 256-k chunks; the slice's fp32 partial sums go to
 // ws [slices][M][N] and skinny_reduce_kernel adds them in slice order (+ bias, + residual, one rounding) -- 64 n groups x 4 slices = a workgroup
 // per CU with x still shared four ways, where the k-split form is L2-bound on x (2.1 TB/s at 32 rows).
@@ -907,9 +818,6 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_nw_kernel(const uint4* __re
         mul(buf);
         // no barrier here: x buffer buf ^ 1 has been free since the last barrier, and the weight region is the wave's own -- its stores follow its reads
         // in program order (same LDS array: the compiler keeps the order, the LDS unit executes a wave's accesses in order)
-#ifdef SW_TWO_BARRIERS
-        __syncthreads();
-#endif
         if (c + 1 < n_chunk) { SW_X_STORE(buf ^ 1); SW_W_STORE(); }
         __syncthreads();
     }
@@ -989,20 +897,21 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restr
     *(uint2*)(y + e) = out;
 }
 
+// host side: the skinny MFMA kernels' MT (m tiles of 16 batch rows, M <= 64) as a compile-time constant -- f(gv_int<MT>)
+template <int V> using gv_int = std::integral_constant<int, V>;
+template <class F>
+static void for_mt(int64_t M, F f) {
+    if (M <= 16) f(gv_int<1>{}); else if (M <= 32) f(gv_int<2>{}); else if (M <= 48) f(gv_int<3>{}); else f(gv_int<4>{});
+}
+
 template <int M>
 static void gemv_launch(const void* x, const void* w, const void* bias, const void* res, void* y, int64_t N, int64_t K,
                         hipStream_t s) {
     // rows per wave.  Measured (tools/bench_gemv.py, MI355X): R=4 wins for every M (R=8 starves the chip of
     // waves at N=4096; R=2 doubles the L2 re-reads of x): 4.9-5.4 TB/s at M=1-2, 3.0-3.6 TB/s at M=8.
-#ifndef GEMV_R_A
 #define GEMV_R_A 4
-#endif
-#ifndef GEMV_R_B
 #define GEMV_R_B 4
-#endif
-#ifndef GEMV_R_C
 #define GEMV_R_C 4
-#endif
     constexpr int R = M <= 2 ? GEMV_R_A : (M <= 4 ? GEMV_R_B : GEMV_R_C);
     const int64_t waves = (N + R - 1) / R;
     if (N <= 4096 && K >= 2048)
@@ -1057,12 +966,8 @@ extern "C" int evo_hyena_decode_fused_small_m(const void* x, const void* norm_sc
     // channels per wave, measured under a hipGraph on MI355X (tools/experiments/hyena_decode_cpw_bench.py): one channel per wave
     // (twice the waves, half the bytes in flight each) is 5 % faster at M = 1 and 6 % at M = 4, two channels win at M = 2
     // (22.8 / 26.1 / 42.6 us with two, 21.6 / 29.9 / 40.0 us with one, M = 1 / 2 / 4).  Same arithmetic either way.
-#ifndef GEMV_HYENA_CPW_STAGED
 #define GEMV_HYENA_CPW_STAGED 1
-#endif
-#ifndef GEMV_HYENA_CPW_STAGED1
 #define GEMV_HYENA_CPW_STAGED1 1
-#endif
     const float isd = 1.0f / sqrtf((float)D);
     const size_t lds = (size_t)M * D * 2;
 #define EVO_HD(MM, CPW, ST)                                                                                   \
@@ -1130,11 +1035,10 @@ extern "C" int evo_mlp_gate_small_m_bf16(const void* x, const void* w12, void* a
         // 5-64 rows: the MFMA weight-streaming form with the gate in its epilogue (skinny_nw_kernel GATE), both weight layouts
         if (I <= 0 || I % 32 != 0 || K <= 0 || K % 256 != 0 || I > 0x1fffffff) return -1;
         hipStream_t s = (hipStream_t)stream;
-#define EVO_SNG(MT) hipLaunchKernelGGL((skinny_nw_kernel<MT, 4, false, true>), dim3((unsigned)(I / 32)), dim3(256), 0, s, (const uint4*)x, (const uint4*)w12,   \
-                                       (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)a, (int)M, (int)(2 * I), (int)(K / 8), (float*)nullptr,     \
-                                       grouped ? 1 : 2)
-        if (M <= 16) EVO_SNG(1); else if (M <= 32) EVO_SNG(2); else if (M <= 48) EVO_SNG(3); else EVO_SNG(4);
-#undef EVO_SNG
+        for_mt(M, [&](auto mt) {
+            hipLaunchKernelGGL((skinny_nw_kernel<decltype(mt)::value, 4, false, true>), dim3((unsigned)(I / 32)), dim3(256), 0, s, (const uint4*)x, (const uint4*)w12,
+                               (const uint16_t*)nullptr, (const uint16_t*)nullptr, (uint16_t*)a, (int)M, (int)(2 * I), (int)(K / 8), (float*)nullptr, grouped ? 1 : 2);
+        });
         return evo_launch_status();
     }
     return mlp_gate_launch(x, nullptr, w12, a, M, I, K, 0.f, grouped, (hipStream_t)stream);
@@ -1152,63 +1056,50 @@ extern "C" int evo_linear_small_m_bf16(const void* x, const void* w, const void*
     if (M > 8 && K % 32 != 0) return -1;
     hipStream_t s = (hipStream_t)stream;
     if (M >= 5 && K % 32 == 0) {
-        // two n tiles per workgroup (every x fragment feeds two weight fragments) where that still leaves a workgroup or more per CU
-        static const int nt_env = [] { const char* e = getenv("EVO_SK_NT"); return e ? atoi(e) : 0; }();      // measurement knob: 1 / 2 force, 0 = auto
-        const int nt = nt_env ? nt_env : (N >= 8192 && M > 16 ? 2 : 1);
-        const dim3 block(512);
-        // n-split form: wide layers (a workgroup or more per CU with WAVES n tiles per workgroup), K in whole 256-k chunks
-        static const int ns_env = [] { const char* e = getenv("EVO_SK_NSPLIT"); return e ? atoi(e) : -1; }();  // measurement knob: 0 off, 2 / 4 force WAVES
-        // (measured, tools/bench_gemv.py: ahead of the k-split form from 17 rows up on the wide layers -- 2.2 -> 3.3+ TB/s at 32 rows, 1.4 -> 2.9 at 64;
-        //  behind it at <= 16 rows, where x is a small share of the L2 traffic and the k-split form's 11,000 short waves hide latency better)
-        const int waves_n = ns_env >= 0 ? ns_env : (K % 256 == 0 && N >= 8192 && M > 16 ? 4 : 0);
-        static const int nw_env = [] { const char* e = getenv("EVO_SK_WLDS"); return e ? atoi(e) : 1; }();    // measurement knob: 0 = fragment-shaped weight requests (skinny_n_kernel)
-        static const int nwm_env = [] { const char* e = getenv("EVO_SK_WLDS_MINM"); return e ? atoi(e) : 5; }();    // measurement knob: first row count on the contiguous form (measured ahead of the k-split form from 5 rows up on the wide layers)
-        static const int nww_env = [] { const char* e = getenv("EVO_SK_WLDS_WAVES"); return e ? atoi(e) : 0; }();   // measurement knob: 2 / 4 waves per workgroup (0 = auto)
+        const uint4 *xp = (const uint4*)x, *wp = (const uint4*)w;
+        const uint16_t *bp = (const uint16_t*)bias, *rp = (const uint16_t*)residual;
+        uint16_t* yp = (uint16_t*)y;
+        const int nvec = (int)(K / 8);
         // narrow layers (N < 8192: out_filter_dense / out_proj / l3 of a 7B block) with a workspace from the caller: four waves per workgroup AND a split
-        // over K across workgroups, partial sums through ws (see skinny_nw_kernel SPLITK)
-        static const int sk_env = [] { const char* e = getenv("EVO_SK_SPLITK"); return e ? atoi(e) : 1; }();      // measurement knob: 0 off
-        static const int skm_env = [] { const char* e = getenv("EVO_SK_SPLITK_MINM"); return e ? atoi(e) : 17; }();
+        // over K across workgroups, partial sums through ws (see skinny_nw_kernel SPLITK), from 17 rows up
         // (K = 4,096 at <= 32 rows: four chunks per slice are too short a run -- 2.0 against 2.45 TB/s at 17 rows -- the k-split form keeps those)
-        if (ws && sk_env && nw_env && ns_env < 0 && K % 256 == 0 && K >= 1024 && N < 8192 && N >= 1024 && N % 64 == 0 && M >= skm_env && (K >= 8192 || M > 32)) {
+        if (ws && K % 256 == 0 && K >= 1024 && N < 8192 && N >= 1024 && N % 64 == 0 && M >= 17 && (K >= 8192 || M > 32)) {
             int64_t slices = (256 + N / 64 - 1) / (N / 64);              // a workgroup per CU
             if (slices > K / 256) slices = K / 256;
             if (slices > 8) slices = 8;
             if (slices >= 2 && ws_bytes >= slices * M * N * 4 && ((uintptr_t)ws & 15) == 0) {
                 const dim3 grid((unsigned)(N / 64), (unsigned)slices);
-#define EVO_SNK(MT) hipLaunchKernelGGL((skinny_nw_kernel<MT, 4, true>), grid, dim3(256), 0, s, (const uint4*)x, (const uint4*)w, (const uint16_t*)nullptr,       \
-                                       (const uint16_t*)nullptr, (uint16_t*)nullptr, (int)M, (int)N, (int)(K / 8), (float*)ws)
-                if (M <= 16) EVO_SNK(1); else if (M <= 32) EVO_SNK(2); else if (M <= 48) EVO_SNK(3); else EVO_SNK(4);
-#undef EVO_SNK
-                hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0, s, (const float*)ws, (const uint16_t*)bias,
-                                   (const uint16_t*)residual, (uint16_t*)y, (int)M, (int)N, (int)slices);
+                for_mt(M, [&](auto mt) {
+                    hipLaunchKernelGGL((skinny_nw_kernel<decltype(mt)::value, 4, true>), grid, dim3(256), 0, s, xp, wp, (const uint16_t*)nullptr,
+                                       (const uint16_t*)nullptr, (uint16_t*)nullptr, (int)M, (int)N, nvec, (float*)ws);
+                });
+                hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0, s, (const float*)ws, bp, rp, yp, (int)M, (int)N,
+                                   (int)slices);
                 return evo_launch_status();
             }
         }
-        if (K % 256 == 0 && N >= 8192 && nw_env && M >= nwm_env && ns_env < 0) {
-            const int wv = nww_env ? nww_env : (N >= 256 * 64 ? 4 : (N >= 256 * 48 ? 3 : (N >= 256 * 32 ? 2 : 4)));   // a workgroup or more per CU where N allows
-#define EVO_SNW(MT, WV) hipLaunchKernelGGL((skinny_nw_kernel<MT, WV>), dim3((unsigned)((N + 16 * WV - 1) / (16 * WV))), dim3(64 * WV), 0, s, (const uint4*)x, \
-                                           (const uint4*)w, (const uint16_t*)bias, (const uint16_t*)residual, (uint16_t*)y, (int)M, (int)N, (int)(K / 8))
-            if (wv == 4) { if (M <= 16) EVO_SNW(1, 4); else if (M <= 32) EVO_SNW(2, 4); else if (M <= 48) EVO_SNW(3, 4); else EVO_SNW(4, 4); }
-            else if (wv == 3) { if (M <= 16) EVO_SNW(1, 3); else if (M <= 32) EVO_SNW(2, 3); else if (M <= 48) EVO_SNW(3, 3); else EVO_SNW(4, 3); }
-            else { if (M <= 16) EVO_SNW(1, 2); else if (M <= 32) EVO_SNW(2, 2); else if (M <= 48) EVO_SNW(3, 2); else EVO_SNW(4, 2); }
-#undef EVO_SNW
+        // n-split form: wide layers, K in whole 256-k chunks; WAVES n tiles per workgroup = a workgroup or more per CU where N allows
+        // (measured, tools/bench_gemv.py: ahead of the k-split form from 5 rows up on the wide layers -- 2.2 -> 3.3+ TB/s at 32 rows, 1.4 -> 2.9 at 64)
+        if (K % 256 == 0 && N >= 8192) {
+            const auto launch = [&](auto mt, auto waves) {
+                constexpr int WV = decltype(waves)::value;
+                hipLaunchKernelGGL((skinny_nw_kernel<decltype(mt)::value, WV>), dim3((unsigned)((N + 16 * WV - 1) / (16 * WV))), dim3(64 * WV), 0, s, xp, wp, bp, rp,
+                                   yp, (int)M, (int)N, nvec);
+            };
+            for_mt(M, [&](auto mt) {
+                if (N >= 256 * 64) launch(mt, gv_int<4>{}); else if (N >= 256 * 48) launch(mt, gv_int<3>{}); else launch(mt, gv_int<2>{});
+            });
             return evo_launch_status();
         }
-        if (waves_n && K % 256 == 0) {
-#define EVO_SN(MT, WV)                                                                                                     \
-            hipLaunchKernelGGL((skinny_n_kernel<MT, WV>), dim3((unsigned)((N + 16 * WV - 1) / (16 * WV))), dim3(64 * WV), 0, s, (const uint4*)x,  \
-                               (const uint4*)w, (const uint16_t*)bias, (const uint16_t*)residual, (uint16_t*)y, (int)M, (int)N, (int)(K / 8))
-            if (waves_n == 4) { if (M <= 16) EVO_SN(1, 4); else if (M <= 32) EVO_SN(2, 4); else if (M <= 48) EVO_SN(3, 4); else EVO_SN(4, 4); }
-            else { if (M <= 16) EVO_SN(1, 2); else if (M <= 32) EVO_SN(2, 2); else if (M <= 48) EVO_SN(3, 2); else EVO_SN(4, 2); }
-#undef EVO_SN
-            return evo_launch_status();
-        }
-#define EVO_SK(MT, NT)                                                                                                     \
-        hipLaunchKernelGGL((skinny_mfma_kernel<MT, NT>), dim3((unsigned)((N + 16 * NT - 1) / (16 * NT))), block, 0, s, (const uint4*)x, (const uint4*)w, \
-                           (const uint16_t*)bias, (const uint16_t*)residual, (uint16_t*)y, (int)M, (int)N, (int)(K / 8))
-        if (nt == 2) { if (M <= 16) EVO_SK(1, 2); else if (M <= 32) EVO_SK(2, 2); else if (M <= 48) EVO_SK(3, 2); else EVO_SK(4, 2); }
-        else { if (M <= 16) EVO_SK(1, 1); else if (M <= 32) EVO_SK(2, 1); else if (M <= 48) EVO_SK(3, 1); else EVO_SK(4, 1); }
-#undef EVO_SK
+        // k-split form; two n tiles per workgroup (every x fragment feeds two weight fragmentiles) where that still leaves a workgroup or more per CU
+        const auto launch = [&](auto mt, auto ntiles) {
+            constexpr int NT = decltype(ntiles)::value;
+            hipLaunchKernelGGL((skinny_mfma_kernel<decltype(mt)::value, NT>), dim3((unsigned)((N + 16 * NT - 1) / (16 * NT))), dim3(512), 0, s, xp, wp, bp, rp, yp,
+                               (int)M, (int)N, nvec);
+        };
+        for_mt(M, [&](auto mt) {
+            if (N >= 8192 && M > 16) launch(mt, gv_int<2>{}); else launch(mt, gv_int<1>{});
+        });
         return evo_launch_status();
     }
     switch (M) {

@@ -28,26 +28,13 @@
 // allocation is bounded for, per kernel.  seg_state (164 VGPRs) runs 3 waves per SIMD with a 4-slot ring: -29 % time
 // against 2 waves / 6 slots at the same bytes in flight per CU (profiles/r02_hyena_notes.txt); apply needs 236 VGPRs
 // and spills at 3.
-#ifndef HY_NSLOT_S
 #define HY_NSLOT_S 4
-#endif
-#ifndef HY_OCC_S
 #define HY_OCC_S 3
-#endif
-#ifndef HY_NSLOT_A
 #define HY_NSLOT_A 5
-#endif
-#ifndef HY_OCC_A
 #define HY_OCC_A 2
-#endif
-#ifndef HY_UNROLL_A
 #define HY_UNROLL_A 4   // steps of a chunk scheduled together in apply
-#endif
 #define HY_PRAGMA_(x) _Pragma(#x)
 #define HY_PRAGMA_UNROLL(n) HY_PRAGMA_(unroll n)
-#ifndef HY_VARIANT
-#define HY_VARIANT 1    // 0: round-1 instruction order (dependent pairs back to back); 1: mode-parallel stages
-#endif
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(1))) const void* glb_ptr_t;
@@ -187,15 +174,6 @@ __global__ __launch_bounds__(256, HY_OCC_S) void hyena_seg_state_kernel(
         const f32x2_t vc = pk_fma(fc.w[2][2], c1, pk_fma(fc.w[2][1], m1[1], pk_fma(fc.w[2][0], m2[1], fc.b[2])));
         f32x2_t x = x1c * vc;
         if (MASK) x = x * (mrow[t_abs] ? 1.f : 0.f);
-#if HY_VARIANT == 0
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const f32x2_t nr = pk_fma(pr[s], sr[s], pk_fma(-pi[s], si[s], x));
-            const f32x2_t ni = pk_fma(pr[s], si[s], pi[s] * sr[s]);
-            sr[s] = nr;
-            si[s] = ni;
-        }
-#else
         // the 8 modes are independent: issue each stage of the complex multiply-add for all of them before the next,
         // so that no packed FMA reads the result of the instruction just ahead of it (the round-1 order had 2/3 of
         // them at dependency distance 2)
@@ -208,7 +186,6 @@ __global__ __launch_bounds__(256, HY_OCC_S) void hyena_seg_state_kernel(
         for (int s = 0; s < NS; ++s) sr[s] = pk_fma(pr[s], sr[s], tt[s]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) si[s] = pk_fma(pr[s], si[s], uu[s]);
-#endif
         m2[0] = m1[0]; m1[0] = c0; m2[1] = m1[1]; m1[1] = c1;
     };
 
@@ -414,17 +391,6 @@ __global__ __launch_bounds__(256, HY_OCC_A) void hyena_apply_kernel(
             f[1] = f[1] * mk;
         }
         const f32x2_t x = f[1] * f[2];             // x1 * v
-#if HY_VARIANT == 0
-        f32x2_t acc = {0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const f32x2_t nr = pk_fma(pr[s], sr[s], pk_fma(-pi[s], si[s], x));
-            const f32x2_t ni = pk_fma(pr[s], si[s], pi[s] * sr[s]);
-            sr[s] = nr;
-            si[s] = ni;
-            acc = pk_fma(rr[s], nr, pk_fma(-ri[s], ni, acc));
-        }
-#else
         // mode-parallel stages (see seg_state) and FOUR partial sums for y = Re sum_s R_s S_s instead of one
         // 16-deep dependent chain
         f32x2_t tt[NS], uu[NS];
@@ -446,7 +412,6 @@ __global__ __launch_bounds__(256, HY_OCC_A) void hyena_apply_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) a4[k] = pk_fma(-ri[k + 4], si[k + 4], a4[k]);
         const f32x2_t acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-#endif
         const f32x2_t out = pk_fma(x, dk, acc) * f[0];   // (y + x1v * D) * x2
 #pragma unroll
         for (int g = 0; g < 3; ++g) { m2[g] = m1[g]; m1[g] = c0[g]; }

@@ -30,9 +30,7 @@
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
-#ifndef HT_XLO
-#define HT_XLO 1                            // 1: X = x1 * v as bf16 hi + lo (profiles/r04_hyena_cs_notes.txt: the closed X_lo question)
-#endif
+// X = x1 * v enters the matrix cores as bf16 hi + lo (xh / xl; profiles/r04_hyena_cs_notes.txt: the closed X_lo question)
 #define HT_NW 8                             // waves per workgroup, two per SIMD
 #define HT_CH 16
 #define HT_CPW 2                            // channels per wave
@@ -232,9 +230,7 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
         //  s_and_saveexec / s_or exec region for the lanes in range -- six EXEC writes per tile in the middle of the MFMA stream, each of which
         //  waits for the matrix pipe to drain; round 6)
         uint32_t in_range = a.y_blk ? yb : row0 + (uint32_t)row * yrb + (lane & 1) * 16;
-#ifndef HT_OLD_SELECT                   /* A/B knob: the round-5 form (EXEC regions) */
         asm volatile("" : "+v"(in_range));
-#endif
         const uint32_t off = (v.st && (full || t0 + row < Ti)) ? in_range : 0xfffffff0u;
         asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v.sdat[hs]), "v"(off), "s"(ysrd) : "memory");
     };
@@ -278,9 +274,7 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
         };
 
         bf16x8_t xh[HT_CPW];
-#if HT_XLO
         bf16x8_t xl[HT_CPW];
-#endif
         f32x2_t x2f[8];
         {
             // FIR of x1 and v, x = x1 * v; the lane's eight steps of both channels -> the two channels' B operands
@@ -319,20 +313,14 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 uint32_t hw[4];
-#if HT_XLO
                 uint32_t lw[4];
-#endif
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     hw[j] = pack_bf2(x[2 * j][e], x[2 * j + 1][e]);
-#if HT_XLO
                     lw[j] = pack_bf2(x[2 * j][e] - bf_lo(hw[j]), x[2 * j + 1][e] - bf_hi(hw[j]));
-#endif
                 }
                 xh[e] = __builtin_bit_cast(bf16x8_t, ht_u4(hw[0], hw[1], hw[2], hw[3]));
-#if HT_XLO
                 xl[e] = __builtin_bit_cast(bf16x8_t, ht_u4(lw[0], lw[1], lw[2], lw[3]));
-#endif
             }
         }
 
@@ -350,17 +338,13 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
 #define HT_FRAG(BASE) __builtin_bit_cast(bf16x8_t, ht_u4(t_[(BASE)], t_[(BASE) + 1], t_[(BASE) + 2], t_[(BASE) + 3]))
             const ht_f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
             ht_f32x4 e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(20), xh[cc], zero4, 0, 0, 0);       // W_mid . X_hi
-#if HT_XLO
             e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(16), xl[cc], e, 0, 0, 0);                    // W_hi . X_lo
-#endif
             e = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(16), xh[cc], e, 0, 0, 0);                    // W_hi . X_hi
             if (!SO)
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
                     ht_f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(8 * mt + 4), xh[cc], zero4, 0, 0, 0);
-#if HT_XLO
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(8 * mt), xl[cc], acc, 0, 0, 0);
-#endif
                     yv[cc][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(HT_FRAG(8 * mt), xh[cc], acc, 0, 0, 0);
                 }
             HT_FENCE_NOP();
@@ -427,9 +411,7 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
                 // cores consumed: the channel's fragments go through the wave's scratch planes (hi | lo, time-contiguous).
                 unsigned char* xs = smem + HT_OFF_XS + wave * 2048;
                 *(bf16x8_t*)(xs + (4 * la + lq) * 16) = xh[cc];
-#if HT_XLO
                 *(bf16x8_t*)(xs + 1024 + (4 * la + lq) * 16) = xl[cc];
-#endif
                 const int tin = Ti - t0;                     // 1..512 valid steps of this tile
                 const int a_ = (tin - 1) >> 5, r_ = tin - 32 * a_;
                 const int src = (16 * ((lane & 7) >> 1) + a_) * 4;
@@ -448,9 +430,7 @@ __global__ __launch_bounds__(HT_THREADS, 1) void hyena_ct_kernel(HtArgs a) {
                 for (int j = 0; j < r_; ++j) {
                     const unsigned char* up = xs + (4 * a_ + (j >> 3)) * 16 + (j & 7) * 2;
                     float xv = bf_to_f(*(const uint16_t*)up);
-#if HT_XLO
                     xv += bf_to_f(*(const uint16_t*)(up + 1024));
-#endif
                     const float nre = fmaf(pre, sre, fmaf(-pim, sim, xv));
                     sim = fmaf(pre, sim, pim * sre);
                     sre = nre;

@@ -11,7 +11,8 @@
  *   - raw DEVICE pointers (tensor.data_ptr()); bf16 = uint16 storage; "c64" = interleaved {re,im} f32;
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream);
  *   - no allocation, no host sync, no global state: safe to capture in a hipGraph; workspace is
- *     passed in by the caller;
+ *     passed in by the caller; which kernel a call launches depends on its arguments alone (the library
+ *     reads no environment variable);
  *   - return value is a hipError_t cast to int (0 = hipSuccess); -1 = bad argument.  The Python
  *     binding raises on non-zero;
  *   - alignment: every pointer to bf16 / f32 / c64 tensor data (activations, weights, states, tables, workspaces) is

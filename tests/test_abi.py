@@ -74,6 +74,15 @@ def test_argument_validation_needs_no_gpu():
     assert lib.evo_attn_fwd_causal_bf16(None, None, None, None, 1, 1, 4, 4, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1.0, None, None) == -1
 
 
+def test_c_abi_reads_no_environment():
+    """Which kernel a C-ABI call launches is a function of its arguments alone (no global state inside the boundary): no
+    source or header of the library mentions getenv."""
+    import glob
+    files = sorted(glob.glob(os.path.join(ROOT, "evo_amd", "csrc", "*")) + glob.glob(os.path.join(ROOT, "include", "*")))
+    assert any(f.endswith(".hip") for f in files) and any(f.endswith(".h") for f in files)
+    assert [os.path.relpath(f, ROOT) for f in files if "getenv" in open(f, errors="replace").read()] == []
+
+
 def test_binding_refuses_misaligned_addresses():
     """include/evo_mi355x.h, Conventions: bf16 / f32 / c64 data 16-byte aligned and no more, integer vectors at their element's alignment.  HipOps._need and the hand-rolled checks of
     attention / attention_decode / rope_append_decode / pool_rows go through this one helper, which takes an address: no GPU needed."""

@@ -110,7 +110,7 @@ if "--no-time" not in sys.argv:
         fl = B * 4 * 4096 * T * T / 2
         rows = torch.tensor([0, 1, 255, 256, 257, T // 2, T - 2, T - 1], device=dev)
         e = rl2(o[:1, rows], ref64(q[:1], k[:1], v[:1], 0, rows))
-        print(f"[time form={os.environ.get('EVO_AMD_ATTN_FORM', '2')}] B={B} T={T}: median {ts[2]:.3f} ms (min {ts[0]:.3f}) = {fl / ts[2] / 1e9:.0f} TFLOP/s = "
+        print(f"[time] B={B} T={T}: median {ts[2]:.3f} ms (min {ts[0]:.3f}) = {fl / ts[2] / 1e9:.0f} TFLOP/s = "
               f"{fl / ts[2] / 1e9 / 2500:.3f} of 2.5 PFLOP/s | rows vs fp64 rel-L2 {e:.2e}", flush=True)
         del qkv, q, k, v, o
 print("CHECK", "FAILED" if bad else "PASSED", flush=True)
