@@ -16,9 +16,10 @@ __device__ __forceinline__ void pool_unpack8(const uint4& v, float* f) {
 }
 
 // The rows a strip pools: mode 0 (mean) splits [first, first + n) into n_strips nearly equal pieces, mode 1 (last) gives the last
-// row to strip 0.  A range outside [0, M) pools nothing here; pool_finish_kernel writes NaN for it.
+// row to strip 0.  A range outside [0, M) pools nothing here; pool_finish_kernel writes NaN for it.  (No first + n: a device-side
+// pair such as (2^62, 2^62) wraps that sum in int64 and would pass.)
 __device__ __forceinline__ bool pool_range_ok(int64_t first, int64_t n, int64_t M) {
-    return first >= 0 && n >= 1 && first + n <= M;
+    return first >= 0 && n >= 1 && first <= M && n <= M - first;
 }
 
 template <int NV, bool NORM>   // NV = 16-byte vectors per lane (D <= NV * 512)

@@ -386,7 +386,7 @@ int evo_unembed_profile_bf16(const void* hidden, const void* emb, const int64_t*
  * users swap in an identity unembedding and reduce [B, T, D] in eager torch)
  *   x      [M, D] bf16 rows with a pitch of `ld` elements (ld >= D, ld % 8 == 0, x 16-byte aligned): the residual stream
  *   ranges [B, 2] device int64: sequence b pools rows first_b .. first_b + n_b - 1 of x (a range with first_b < 0, n_b < 1 or
- *          first_b + n_b > M pools nothing and gets a NaN row)
+ *          first_b + n_b > M pools nothing and gets a NaN row; the test is n_b <= M - first_b, so no int64 pair can wrap past it)
  *   scale  [D] bf16 or NULL: with it f(x) = scale * x / (||x||_2 D^-1/2 + eps) (the engine's RMSNorm, eps outside the root) taken
  *          in fp32 from the bf16 rows, no rounding in between; NULL: f(x) = x.  The scale is applied once, after the sum.
  *   mode   0 = mean:  out[b] = (1 / n_b) * sum_t f(x_t);  1 = last:  out[b] = f(x_{first_b + n_b - 1})
