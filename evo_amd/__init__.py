@@ -14,6 +14,7 @@ from .version import version as __version__
 from .models import Evo
 from .generation import generate
 from .scoring import score_sequences, positional_entropies, position_profiles, substitution_scores, PositionProfile
+from .scoring import score_variants, single_substitutions, plan_variants, VariantScores
 from .embeddings import embed_sequences
 
 SHIM_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "shim")

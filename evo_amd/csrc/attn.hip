@@ -820,6 +820,7 @@ extern "C" int evo_attn_fwd_causal_bf16(const void* q, const void* k, const void
     // (vt_ws == NULL) the 8-wave pipelined kernel of rounds 2-4; shorter ones the 128-row kernel
     a.nbh = (int)(B * H);
     a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
+    a.k_pre = nullptr; a.vt_pre = nullptr; a.kp_st = 0; a.kp_sh = 0; a.vtp_row = 0; a.n_pre = 0;
     if (Tq > QB && vt_ws) return evo_attn_w64_launch(a, B, vt_ws, stream);
     const int use_pipe = Tq > QB;
     const int qblock = use_pipe ? PQB : QB;
@@ -850,6 +851,7 @@ extern "C" int evo_attn_decode_bf16(const void* q, const void* k, const void* v,
     a.prescaled = softmax_scale <= 0.f ? 1 : 0;
     a.scale_log2 = a.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
     a.n_qblocks = 1; a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
+    a.k_pre = nullptr; a.vt_pre = nullptr; a.kp_st = 0; a.kp_sh = 0; a.vtp_row = 0; a.n_pre = 0;
     a.dyn_pos = dyn_pos; a.part_o = part_o; a.part_ml = part_ml; a.n_splits = (int)n_splits; a.nbh = (int)(B * H);
     hipStream_t s = (hipStream_t)stream;
     // the streaming kernel, one split per wave; its 32-bit key offsets need both caches below 4 GiB, beyond that the MFMA split kernel

@@ -28,6 +28,11 @@ struct AttnArgs {
     int q_pad;                // attn_fwd_w64_kernel: query blocks are aligned to the END of the query range; block 0 starts at row -q_pad
     const uint16_t* vt;       // attn_fwd_w64_kernel: V^T [B][H][128][vt_row] (keys contiguous; written by attn_vt_kernel from v)
     int64_t vt_row;           // keys per row of vt (Tk rounded up to 64)
+    // attn_fwd_w64_kernel<., SEG> (evo_attn_fwd_prefix_bf16): n_pre whole key tiles shared by every batch row in front of the row's own keys
+    const uint16_t* k_pre;    // [64 n_pre, H, 128] with token / head strides kp_st, kp_sh (no batch stride)
+    const uint16_t* vt_pre;   // V^T of the prefix [H][128][vtp_row] (evo_attn_prefix_vt_bf16)
+    int64_t kp_st, kp_sh, vtp_row;
+    int n_pre;
 };
 
 // Workgroup -> (query block, head, batch) for the prefill kernel, 1-D grid.  Blocks are dispatched round-robin

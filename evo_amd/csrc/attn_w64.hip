@@ -176,7 +176,14 @@ __device__ __forceinline__ void w_static_for(F&& f) { w_static_for_impl(f, std::
 // tile may also move it down): P = 2^s up to 2^64, l <= 2^81, |O| <= 2^91 at T = 131,073 -- fp32 / bf16 carry the exponent, every rounding is
 // relative.  While no row of the wave has moved nothing is subtracted at all; once one has (wave-uniform `any_nm`) the tile's scores get
 // their row's offset in a burst between the two phases, like the masking of a diagonal tile.
-template <bool PRE>
+// SEG (evo_attn_fwd_prefix_bf16): the keys are TWO segments -- a prefix of a.n_pre whole tiles shared by every batch row (a.k_pre, a.vt_pre:
+// no batch stride) followed by the row's own keys (a.k, a.vt); a.Tk = 64 a.n_pre + a.Tq and a.q_pos0 = 64 a.n_pre, so tile numbers, masks and the
+// ragged last tile are those of the concatenated key range.  KB = 64 puts every tile wholly inside one segment: a tile's descriptors pick
+// their segment with scalar selects (tile_srd / vt_srd), and the per-lane DMA offsets -- which hold the segment's token stride / V^T row
+// pitch -- are rebuilt ONCE per workgroup, in a wave-uniform branch at the head of the trip that first fetches a tile of the second
+// segment (the tiles are walked in order, so the seam is crossed once per ring).  The trip itself is the instruction stream of the
+// one-segment form: same tiles, same order, same arithmetic -- the results are bit for bit those of that form on the concatenated keys.
+template <bool PRE, bool SEG = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[W_LDS];
 
@@ -194,6 +201,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     const uint16_t* qp = a.q + bat * a.q_sb + head * a.q_sh;
     const unsigned char* kp = (const unsigned char*)(a.k + bat * a.k_sb + head * a.k_sh);
     const int64_t kst_b = a.k_st * 2;
+    // SEG: the shared prefix (no batch stride), its token stride and V^T row pitch in bytes, its length in tiles
+    const unsigned char* kpre = SEG ? (const unsigned char*)(a.k_pre + head * a.kp_sh) : nullptr;
+    const int64_t kpst_b = SEG ? a.kp_st * 2 : 0;
+    const int n_pre = SEG ? a.n_pre : 0;
 
     // ---- this lane's two query rows (column l31 of the wave's two 32-row blocks) ---------------------------------------------------
     const int64_t wrow0 = q0 + wave * 64;                               // wave-uniform
@@ -212,41 +223,55 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     int64_t max_key = q0 + W_QB - 1 + q_pos0_;                          // (q0 + 255 <= Tq - 1 by construction)
     if (max_key > Tk_ - 1) max_key = Tk_ - 1;
     const int n_tiles = (int)(max_key / KB) + 1;
+    if constexpr (SEG) __builtin_assume(n_tiles >= 1);
 
     // ---- DMA plan ---------------------------------------------------------------------------------------------------------------
     // K piece j (17 of 1 KiB: padded rows) -> waves j % 4, five per-lane offsets; V piece j (16: 4 rows each) -> one per-lane offset
     // (row (lane >> 4) of the piece, 64-byte block XOR (row & 3)) + a wave-uniform row offset in the instruction's SGPR offset.
     uint32_t dk_off[5];
+    auto set_dk = [&](const int64_t st_b) __attribute__((always_inline)) {       // (SEG: called again with the other segment's token stride)
 #pragma unroll
-    for (int jj = 0; jj < 5; ++jj) {
-        const int j = wave + 4 * jj;
-        const int pos = j * 1024 + 16 * lane;
-        const int r = pos / W_KROW;
-        int c = pos - r * W_KROW;
-        c = c < 256 ? c : 0;                                            // pad lanes re-fetch the row's first granule (never read back)
-        dk_off[jj] = (uint32_t)r * (uint32_t)kst_b + (uint32_t)c;
-    }
+        for (int jj = 0; jj < 5; ++jj) {
+            const int j = wave + 4 * jj;
+            const int pos = j * 1024 + 16 * lane;
+            const int r = pos / W_KROW;
+            int c = pos - r * W_KROW;
+            c = c < 256 ? c : 0;                                        // pad lanes re-fetch the row's first granule (never read back)
+            dk_off[jj] = (uint32_t)r * (uint32_t)st_b + (uint32_t)c;
+        }
+    };
+    set_dk(kst_b);
     // V^T piece j (16 of 1 KiB) = d rows 8 j .. 8 j + 7 of the tile, 128 B (64 keys) each: lane -> row (lane >> 3), LDS chunk lane & 7, which
     // holds the row's chunk (lane & 7) ^ ((d >> 1) & 7); d >> 1 = 4 j + (lane >> 4) and j = wave + 4 jj, so the swizzle is one per-lane
     // constant of the wave.  The piece's row offset goes into the instruction's SGPR offset.
     const int64_t vt_row_b = a.vt_row * 2;
-    uint32_t dv_off;
-    {
+    uint32_t dv_off, dv_soff;                                           // dv_soff: per V^T piece: 8 rows
+    auto set_dv = [&](const int64_t row_b) __attribute__((always_inline)) {      // (SEG: called again with the other segment's row pitch)
         const int r = lane >> 3;
         const int f = (4 * (wave & 1) + (lane >> 4)) & 7;
-        dv_off = (uint32_t)r * (uint32_t)vt_row_b + (uint32_t)(((lane & 7) ^ f) << 4);
-    }
-    const uint32_t dv_soff = (uint32_t)(8 * vt_row_b);                 // per V^T piece: 8 rows
+        dv_off = (uint32_t)r * (uint32_t)row_b + (uint32_t)(((lane & 7) ^ f) << 4);
+        dv_soff = (uint32_t)(8 * row_b);
+    };
+    set_dv(vt_row_b);
     const unsigned char* vtp = (const unsigned char*)(a.vt + ((int64_t)bat * a.H + head) * DH * a.vt_row);
+    const unsigned char* vtpre = SEG ? (const unsigned char*)(a.vt_pre + (int64_t)head * DH * a.vtp_row) : nullptr;
+    const int64_t vtp_row_b = SEG ? a.vtp_row * 2 : 0;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     // Buffer descriptors of one tile: base = its first row, num_records = bytes up to the end of the last VALID key (0 past the end):
     // the hardware bounds check returns zeros beyond -- no clamping, every trip issues the same instructions.  Branch-free scalar code:
     // tiles below n_full are whole, tile n_full holds the Tk % 64 last keys, later ones nothing.
     const int n_full = (int)(Tk_ / KB), k_rem = (int)(Tk_ % KB);
     auto tile_srd = [&](const unsigned char* base, int64_t st_b, int tile) __attribute__((always_inline)) {
+        int ti = tile;                                                  // the tile's number inside its segment
+        if constexpr (SEG) {                                            // (n_full, k_rem count the concatenated keys: 64 n_pre + Tq)
+            const bool pre_ = tile < n_pre;
+            base = pre_ ? kpre : base;
+            st_b = pre_ ? kpst_b : st_b;
+            ti = pre_ ? tile : tile - n_pre;
+        }
         const uint32_t rec_full = (uint32_t)((KB - 1) * st_b + 256);
         const uint32_t rec_rem = k_rem ? (uint32_t)((k_rem - 1) * st_b + 256) : 0u;
-        const uint64_t a64 = (uint64_t)base + (uint64_t)(uint32_t)tile * (uint64_t)(KB * st_b);
+        const uint64_t a64 = (uint64_t)base + (uint64_t)(uint32_t)ti * (uint64_t)(KB * st_b);
         w_srd_t d;
         d[0] = (int)(uint32_t)a64;
         d[1] = (int)(uint32_t)(a64 >> 32);
@@ -257,6 +282,18 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     // V^T tile: base = column 64 tile of the head's plane, rows vt_row_b apart; the plane is padded to whole tiles
     const int n_vt = (int)(a.vt_row / KB);
     auto vt_srd = [&](int tile) __attribute__((always_inline)) {
+        if constexpr (SEG) {                                            // the prefix plane's tiles all exist; the row's own plane from tile n_pre on
+            const bool pre_ = tile < n_pre;
+            const int ti = pre_ ? tile : tile - n_pre;
+            const uint64_t a64 = (uint64_t)(pre_ ? vtpre : vtp) + (uint64_t)(uint32_t)ti * (uint64_t)(KB * 2);
+            const int64_t row_b = pre_ ? vtp_row_b : vt_row_b;
+            w_srd_t d;
+            d[0] = (int)(uint32_t)a64;
+            d[1] = (int)(uint32_t)(a64 >> 32);
+            d[2] = (int)((pre_ || ti < n_vt) ? (uint32_t)((DH - 1) * row_b + KB * 2) : 0u);
+            d[3] = 0x00020000;
+            return d;
+        } else {
         const uint64_t a64 = (uint64_t)vtp + (uint64_t)(uint32_t)tile * (uint64_t)(KB * 2);
         w_srd_t d;
         d[0] = (int)(uint32_t)a64;
@@ -264,6 +301,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
         d[2] = (int)(tile < n_vt ? (uint32_t)((DH - 1) * vt_row_b + KB * 2) : 0u);
         d[3] = 0x00020000;
         return d;
+        }
     };
 // One DMA piece = "m0 <- LDS address" + the load.  In the prologue both in one asm; inside a trip the m0 write heads the gap and the load
 // ends it (W_M0_* / W_LD_*): the MFMA between them is the wait state the pair needs, and the piece costs two issue slots instead of four.
@@ -285,13 +323,17 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
 #define W_LD_V(SRD, JJ) asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(dv_off), "s"(SRD), "s"((wave + 4 * (JJ)) * dv_soff) : "memory")
 #define W_KSLOT(T) (lds0 + (uint32_t)((T) & (W_NK - 1)) * W_KSTAGE)
 #define W_VSLOT(T) (lds0 + W_VBASE + (uint32_t)((T) % W_NV) * W_VSTAGE)
+    // dma_k / dma_v: PROLOGUE ONLY.  A trip issues its pieces itself (W_M0P / W_LD_*) with the offsets the seam branch at its head left.
+    // SEG: both rebuild the per-lane offsets for the tile's segment on every call (five VGPRs for K) -- never call them from the loop.
     auto dma_k = [&](int tile) __attribute__((always_inline)) {
+        if constexpr (SEG) set_dk(tile < n_pre ? kpst_b : kst_b);
         const w_srd_t s_ = tile_srd(kp, kst_b, tile);
         const uint32_t st_ = W_KSLOT(tile);
 #pragma unroll
         for (int jj = 0; jj < 5; ++jj) W_DMA_K(s_, st_, jj);
     };
     auto dma_v = [&](int tile) __attribute__((always_inline)) {
+        if constexpr (SEG) set_dv(tile < n_pre ? vtp_row_b : vt_row_b);
         const w_srd_t s_ = vt_srd(tile);
         const uint32_t st_ = W_VSLOT(tile);
 #pragma unroll
@@ -532,6 +574,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) vb[g] = v_rd[g];
     w_srd_t ksrd = tile_srd(kp, kst_b, 4), vsrd = vt_srd(2);
+    if constexpr (SEG) {                                   // trip 0 fetches K tile 4 and V tile 2: the offsets of THEIR segments
+        set_dk(4 < n_pre ? kpst_b : kst_b);
+        set_dv(2 < n_pre ? vtp_row_b : vt_row_b);
+    }
     uint32_t kslot = W_KSLOT(4), vslot = W_VSLOT(2);
     bool mask_nxt = 1 >= mask_from;
     int v_idx = 0;                                         // tile % 3
@@ -545,6 +591,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w64_kernel(AttnArgs a) {
     uint64_t tp_[6] = {0, 0, 0, 0, 0, 0}, tl_ = __builtin_readcyclecounter();
 #endif
     for (int tile = 0; tile < n_tiles; ++tile) {
+        if constexpr (SEG) {                               // once per workgroup each: this trip's K fetch (tile + 4) / V fetch (tile + 2) is the row's own first tile
+            if (tile + 4 == n_pre) set_dk(kst_b);
+            if (tile + 2 == n_pre) set_dv(vt_row_b);
+        }
         if (resc) {                                        // rare (deferred max): some row moved its reference point for this tile
             W_NOP24();
 #pragma unroll
@@ -733,5 +783,51 @@ int evo_attn_w64_launch(AttnArgs a, int64_t B, void* vt_ws, void* stream) {
                        a.v, (uint16_t*)vt_ws, a.Tk, a.v_sb, a.v_st, a.v_sh, a.vt_row, a.H);
     if (a.prescaled) hipLaunchKernelGGL(attn_fwd_w64_kernel<true>, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(attn_fwd_w64_kernel<false>, dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
+    return evo_launch_status();
+}
+
+// ---- shared prefix + private suffix (include/evo_mi355x.h, ABI 14) ---------------------------------------------------------------------
+// The prefix's V^T plane [H][128][vt_row]: attn_vt_kernel on a "batch" of one.  Written once per reference and layer, read by every group.
+extern "C" int evo_attn_prefix_vt_bf16(const void* v_pre, void* vt_pre, int64_t P, int64_t H, int64_t vp_st, int64_t vp_sh, int64_t vt_row,
+                                       void* stream) {
+    if (!v_pre || !vt_pre || P <= 0 || H <= 0 || H > 65535 || (vp_st % 8) || (vp_sh % 8)) return -1;
+    if (vt_row % KB || vt_row < P || (P + KB - 1) / KB > 0x7fffffff || DH * vt_row * 2 > 0xffffffffll) return -1;
+    hipLaunchKernelGGL(attn_vt_kernel, dim3((unsigned)((P + KB - 1) / KB), (unsigned)H, 1u), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)v_pre, (uint16_t*)vt_pre, P, (int64_t)0, vp_st, vp_sh, vt_row, (int)H);
+    return evo_launch_status();
+}
+
+extern "C" int evo_attn_fwd_prefix_bf16(const void* q, const void* k, const void* v, const void* k_pre, const void* vt_pre, void* o,
+                                        int64_t B, int64_t H, int64_t Tq, int64_t P, int64_t q_sb, int64_t q_st, int64_t q_sh,
+                                        int64_t k_sb, int64_t k_st, int64_t k_sh, int64_t v_sb, int64_t v_st, int64_t v_sh,
+                                        int64_t kp_st, int64_t kp_sh, int64_t vtp_row, float softmax_scale, void* vt_ws, void* stream) {
+    if (B <= 0 || H <= 0 || H > 65535 || B > 65535) return -1;
+    if (P < KB || P % KB || Tq <= QB) return -1;                        // whole prefix tiles; only the 64-rows-per-wave form is built
+    if (!q || !k || !v || !k_pre || !vt_pre || !o || !vt_ws) return -1;
+    if ((q_sb % 8) || (q_st % 8) || (q_sh % 8) || (k_sb % 8) || (k_st % 8) || (k_sh % 8) || (v_sb % 8) || (v_st % 8) || (v_sh % 8) ||
+        (kp_st % 8) || (kp_sh % 8)) return -1;                          // 16-byte row accesses
+    if (vtp_row % KB || vtp_row < P || DH * vtp_row * 2 > 0xffffffffll) return -1;
+    AttnArgs a;
+    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.o = (uint16_t*)o;
+    a.Tq = Tq; a.Tk = P + Tq; a.q_pos0 = P;
+    a.q_sb = q_sb; a.q_st = q_st; a.q_sh = q_sh; a.k_sb = k_sb; a.k_st = k_st; a.k_sh = k_sh;
+    a.v_sb = v_sb; a.v_st = v_st; a.v_sh = v_sh;
+    a.H = (int)H;
+    a.prescaled = softmax_scale <= 0.f ? 1 : 0;
+    a.scale_log2 = a.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
+    a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1;
+    a.nbh = (int)(B * H);
+    a.n_qblocks = (int)((Tq + W_QB - 1) / W_QB);
+    a.q_pad = (int)((int64_t)a.n_qblocks * W_QB - Tq);
+    a.vt = (const uint16_t*)vt_ws;
+    a.vt_row = (Tq + KB - 1) / KB * KB;                                 // the suffix planes: [B][H][128][Tq rounded up to 64]
+    a.k_pre = (const uint16_t*)k_pre; a.vt_pre = (const uint16_t*)vt_pre;
+    a.kp_st = kp_st; a.kp_sh = kp_sh; a.vtp_row = vtp_row; a.n_pre = (int)(P / KB);
+    const int64_t n_wg = (int64_t)a.n_qblocks * a.nbh;
+    if (n_wg > 0x7fffffff || P / KB > 0x3fffffff || DH * a.vt_row * 2 > 0xffffffffll) return -1;
+    hipLaunchKernelGGL(attn_vt_kernel, dim3((unsigned)(a.vt_row / KB), (unsigned)a.H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       a.v, (uint16_t*)vt_ws, Tq, a.v_sb, a.v_st, a.v_sh, a.vt_row, a.H);
+    if (a.prescaled) hipLaunchKernelGGL((attn_fwd_w64_kernel<true, true>), dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((attn_fwd_w64_kernel<false, true>), dim3((unsigned)n_wg), dim3(256), 0, (hipStream_t)stream, a);
     return evo_launch_status();
 }

@@ -34,6 +34,8 @@ _SIGNATURES = {
     "evo_hyena_step": ([_PTR] * 9 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_rope_qk_bf16": ([_PTR, _PTR, _PTR, _I64, _I64, _I64, _I64, _F32, _PTR], _c.c_int),
     "evo_attn_fwd_causal_bf16": ([_PTR] * 4 + [_I64] * 14 + [_F32, _PTR, _PTR], _c.c_int),
+    "evo_attn_fwd_prefix_bf16": ([_PTR] * 6 + [_I64] * 16 + [_F32, _PTR, _PTR], _c.c_int),
+    "evo_attn_prefix_vt_bf16": ([_PTR] * 2 + [_I64] * 5 + [_PTR], _c.c_int),
     "evo_attn_decode_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
     "evo_linear_small_m_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR, _I64, _PTR], _c.c_int),
     "evo_linear_mfma_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR], _c.c_int),
@@ -63,7 +65,7 @@ _SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 13        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 14        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 
 
 class EvoLibraryError(RuntimeError):
@@ -892,6 +894,58 @@ class HipOps:
                 q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, H, Tq, Tk, int(q_pos0),
                 q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
                 v.stride(0), v.stride(1), v.stride(2), 0.0 if prescaled else 1.0 / math.sqrt(hd), _ptr(vt), _stream()), "evo_attn_fwd_causal_bf16")
+        return o
+
+    def attention_prefix_vt(self, v_pre: torch.Tensor, cols: Optional[int] = None) -> torch.Tensor:
+        """The V^T plane [H, 128, cols] of a shared prefix v_pre [P, H, 128] (a strided view, e.g. kv[0, :P, 1] of a KV cache) for
+        `attention_prefix`: built once per reference and layer, reused by every call whose prefix is the first P' <= P keys.  `cols`
+        (default: P rounded up to 64) is the plane's row pitch."""
+        if v_pre.dim() != 3 or v_pre.shape[2] != 128 or not v_pre.is_cuda or v_pre.dtype != torch.bfloat16 or v_pre.stride(-1) != 1:
+            raise RuntimeError("attention_prefix_vt: need a ROCm bf16 tensor [P, H, 128] with a dense last dim")
+        self._check_address(v_pre.data_ptr(), "attention_prefix_vt v_pre")
+        P, H, hd = v_pre.shape
+        cols = (P + 63) // 64 * 64 if cols is None else int(cols)
+        if P < 1 or cols % 64 or cols < P:
+            raise RuntimeError(f"attention_prefix_vt: {cols} columns for {P} keys (need a multiple of 64, >= P >= 1)")
+        vt = torch.empty(H, hd, cols, dtype=torch.bfloat16, device=v_pre.device)
+        with self._t("attn_prefix_vt"):
+            _check(self.lib.evo_attn_prefix_vt_bf16(v_pre.data_ptr(), vt.data_ptr(), P, H, v_pre.stride(0), v_pre.stride(1), cols, _stream()),
+                   "evo_attn_prefix_vt_bf16")
+        return vt
+
+    def attention_prefix(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_pre: torch.Tensor, v_pre: Optional[torch.Tensor],
+                         vt_pre: Optional[torch.Tensor] = None, prescaled: bool = False) -> torch.Tensor:
+        """Causal attention of B rows that share ONE prefix: q, k, v [B, Tq, H, 128] are the rows' own (suffix) tokens, k_pre / v_pre
+        [P, H, 128] the prefix (no batch dimension; strided views allowed, e.g. kv[0, :P, 0] / kv[0, :P, 1] of a KV cache).  Query i of
+        row b sees the P prefix keys and suffix keys 0 .. i of its row -- bit for bit `attention(q, cat(k_pre, k_b), cat(v_pre, v_b), P)`
+        without the B copies.  vt_pre: the prefix's V^T plane from `attention_prefix_vt` (of these or MORE prefix keys), built here
+        when None -- a caller with several groups per reference passes it.  P >= 64, P % 64 == 0 and Tq >= 129 (csrc/attn_w64.hip SEG)."""
+        named = [(q, "q"), (k, "k"), (v, "v"), (k_pre, "k_pre")] + ([(v_pre, "v_pre")] if v_pre is not None else []) \
+            + ([(vt_pre, "vt_pre")] if vt_pre is not None else [])
+        for t, nm in named:
+            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
+                raise RuntimeError(f"attention_prefix {nm}: need a ROCm bf16 tensor with a dense last dim")
+            self._check_address(t.data_ptr(), f"attention_prefix {nm}")
+        B, Tq, H, hd = q.shape
+        if hd != 128 or k.shape != q.shape or v.shape != q.shape or k_pre.dim() != 3 or tuple(k_pre.shape[1:]) != (H, hd):
+            raise RuntimeError("attention_prefix: expects q / k / v [B, Tq, H, 128] and k_pre [P, H, 128]")
+        P = k_pre.shape[0]
+        if P < 64 or P % 64 or Tq < 129:
+            raise RuntimeError(f"attention_prefix: P = {P}, Tq = {Tq}: needs P >= 64, P % 64 == 0 and Tq >= 129")
+        if vt_pre is None:
+            if v_pre is None or tuple(v_pre.shape) != (P, H, hd):
+                raise RuntimeError("attention_prefix: v_pre [P, H, 128] is needed to build the prefix's V^T plane")
+            vt_pre = self.attention_prefix_vt(v_pre)
+        if vt_pre.dim() != 3 or tuple(vt_pre.shape[:2]) != (H, hd) or not vt_pre.is_contiguous() or vt_pre.shape[2] % 64 or vt_pre.shape[2] < P:
+            raise RuntimeError("attention_prefix vt_pre: need a contiguous [H, 128, cols] plane with cols % 64 == 0 and cols >= P")
+        o = torch.empty(B, Tq, H, hd, dtype=torch.bfloat16, device=q.device)
+        vt = torch.empty(B, H, hd, (Tq + 63) // 64 * 64, dtype=torch.bfloat16, device=q.device)
+        with self._t("attn_prefix"):
+            _check(self.lib.evo_attn_fwd_prefix_bf16(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), k_pre.data_ptr(), vt_pre.data_ptr(), o.data_ptr(), B, H, Tq, P,
+                q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
+                k_pre.stride(0), k_pre.stride(1), vt_pre.shape[2], 0.0 if prescaled else 1.0 / math.sqrt(hd), vt.data_ptr(), _stream()),
+                "evo_attn_fwd_prefix_bf16")
         return o
 
     def attention_decode(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

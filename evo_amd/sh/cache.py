@@ -7,6 +7,15 @@ from torch import Tensor
 
 
 @dataclass
+class SharedPrefix:
+    """Keys / values of ONE reference sequence that every row of a batch continues (evo_amd.scoring.score_variants):
+    kv[layer] = the reference's own KV buffer [1, cap, 2, H, hd] (read through views, never copied or expanded),
+    vt[layer] = its V^T plane [H, hd, cols] for HipOps.attention_prefix (absent on backends that need none)."""
+    kv: dict = field(default_factory=dict)
+    vt: dict = field(default_factory=dict)
+
+
+@dataclass
 class InferenceParams:
     """Attention layers: key_value_memory_dict[layer] = [B_max, max_seqlen, 2, H, hd] bf16."""
     max_seqlen: int
@@ -15,6 +24,9 @@ class InferenceParams:
     batch_size_offset: int = 0
     key_value_memory_dict: dict = field(default_factory=dict)
     lengths_per_sample: Optional[Tensor] = None
+    # set: the rows continue the first `seqlen_offset` tokens of a shared reference -- attention reads that prefix from shared_prefix.kv and
+    # no per-row KV buffer is allocated or written (StripedHyena._attn_block)
+    shared_prefix: Optional[SharedPrefix] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen

@@ -720,17 +720,24 @@ class StripedHyena(nn.Module):
         else:
             cos, sin = self._rotary(off, T, x2d.device)
             ops.rope_(qkv, cos, sin, **rk)
-            if cache is not None:
-                kv = self._kv_buffer(cache, i, B, off + T, qkv)
-                kv[:B, off:off + T].copy_(qkv[:, :, 1:3])
-                k = kv[:B, : off + T, 0]
-                v = kv[:B, : off + T, 1]
+            shared = getattr(cache, "shared_prefix", None) if cache is not None else None
+            if shared is not None:
+                # every row continues the first `off` tokens of ONE reference (score_variants): its keys / values are read from the
+                # reference's own buffer, the rows' own from qkv -- no per-row KV buffer exists
+                kvr = shared.kv[i]
+                a = ops.attention_prefix(q, qkv[:, :, 1], qkv[:, :, 2], kvr[0, :off, 0], kvr[0, :off, 1], vt_pre=shared.vt.get(i), **ak).view(B * T, D)
             else:
-                k, v = qkv[:, :, 1], qkv[:, :, 2]
-            if T == 1 and cache is not None:
-                a = ops.attention_decode(q, k, v, **ak).view(B, D)      # split-K over the KV cache
-            else:
-                a = ops.attention(q, k, v, off, **ak).view(B * T, D)
+                if cache is not None:
+                    kv = self._kv_buffer(cache, i, B, off + T, qkv)
+                    kv[:B, off:off + T].copy_(qkv[:, :, 1:3])
+                    k = kv[:B, : off + T, 0]
+                    v = kv[:B, : off + T, 1]
+                else:
+                    k, v = qkv[:, :, 1], qkv[:, :, 2]
+                if T == 1 and cache is not None:
+                    a = ops.attention_decode(q, k, v, **ak).view(B, D)      # split-K over the KV cache
+                else:
+                    a = ops.attention(q, k, v, off, **ak).view(B * T, D)
         if nf:
             return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, a, mha.out_proj.weight, mha.out_proj.bias))
         self._mlp_residual_(blk, x2d, self._mixer_out_(blk, x2d, a, mha.out_proj.weight, mha.out_proj.bias, mfma=True),

@@ -64,8 +64,10 @@ extern "C" {
  *      of every row through the operator and the one token behind them through the single-token launch, see below).
  *  11: evo_pool_rows_bf16 added (sequence embeddings: masked row pooling with the final RMSNorm optionally fused in); no signature changed.
  *  12: evo_sample_rows_f32 added (seeded sampling on the device); no signature changed.
- *  13: evo_unembed_profile_bf16 added (the fused scoring tail with the log-probs of up to 8 chosen vocabulary ids per row); no signature changed. */
-#define EVO_ABI_VERSION 13
+ *  13: evo_unembed_profile_bf16 added (the fused scoring tail with the log-probs of up to 8 chosen vocabulary ids per row); no signature changed.
+ *  14: evo_attn_fwd_prefix_bf16 and evo_attn_prefix_vt_bf16 added (causal attention whose keys are ONE prefix shared by every batch row plus
+ *      each row's own suffix: variant scoring from a cached reference); no signature changed. */
+#define EVO_ABI_VERSION 14
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -231,6 +233,35 @@ int evo_attn_fwd_causal_bf16(const void* q, const void* k, const void* v, void* 
                              int64_t k_sb, int64_t k_st, int64_t k_sh,
                              int64_t v_sb, int64_t v_st, int64_t v_sh,
                              float softmax_scale, void* vt_ws, void* stream);
+
+/* shared prefix + private suffix (ABI 14): B rows that continue ONE common prefix -- the variants of a reference sequence, scored from
+ * the reference's KV cache -- without B copies of the prefix's K, V and V^T.  (No counterpart in the reference, which forwards every
+ * variant whole [REF evo/scoring.py:80-84].)
+ *   q [B, Tq, H, 128]; k / v [B, Tq, H, 128]: the rows' OWN keys (the suffix), strided like above (e.g. the thirds of a packed qkv);
+ *   k_pre [P, H, 128]: the prefix keys, NO batch dimension, element strides (token kp_st, head kp_sh) -- a view into a KV cache
+ *   [1, cap, 2, H, 128] works without a copy; o [B, Tq, H, 128] bf16 contiguous.
+ *   Query i of row b sees prefix keys 0 .. P-1 and suffix keys 0 .. i of row b: the result is bit for bit that of
+ *   evo_attn_fwd_causal_bf16 (with vt_ws) on k = cat(k_pre, k_b), Tk = P + Tq, q_pos0 = P -- same key tiles, same order, same arithmetic
+ *   (csrc/attn_w64.hip SEG: a 64-key tile lies in one segment; its descriptors pick the segment with scalar selects).
+ *   Contract: P >= 64, P % 64 == 0 and Tq >= 129, otherwise -1 without a launch: only the 64-rows-per-wave form is built; shorter
+ *   ranges are the caller's business (evo_amd/scoring.py plans variant suffixes accordingly).
+ *   V^T workspaces (keys contiguous, bf16):
+ *     vt_pre  the PREFIX plane [H][128][vtp_row], vtp_row % 64 == 0, vtp_row >= P, 128 * vtp_row * 2 < 4 GiB: written ONCE per reference
+ *             and layer by evo_attn_prefix_vt_bf16 below (for as many keys as any later call uses as its prefix: a call with a shorter P
+ *             reads the first P columns of the same plane), never by this entry -- const here;
+ *     vt_ws   the SUFFIX planes [B][H][128][Tq rounded up to 64], written by this entry's pre-pass on every call.
+ *   softmax_scale <= 0: the queries are pre-scaled, as above. */
+int evo_attn_fwd_prefix_bf16(const void* q, const void* k, const void* v, const void* k_pre, const void* vt_pre, void* o,
+                             int64_t B, int64_t H, int64_t Tq, int64_t P,
+                             int64_t q_sb, int64_t q_st, int64_t q_sh,
+                             int64_t k_sb, int64_t k_st, int64_t k_sh,
+                             int64_t v_sb, int64_t v_st, int64_t v_sh,
+                             int64_t kp_st, int64_t kp_sh, int64_t vtp_row,
+                             float softmax_scale, void* vt_ws, void* stream);
+/* v_pre [P, H, 128] (element strides vp_st, vp_sh; no batch dimension) -> vt_pre [H][128][vt_row]: columns 0 .. P-1 hold V^T, the
+ * columns up to the next multiple of 64 zeros, later ones are not written.  vt_row % 64 == 0, vt_row >= P, P >= 1. */
+int evo_attn_prefix_vt_bf16(const void* v_pre, void* vt_pre, int64_t P, int64_t H, int64_t vp_st, int64_t vp_sh, int64_t vt_row,
+                            void* stream);
 
 /* decode form (one query per sequence, Tq = 1): split-K over the key range ("flash-decoding") + combine.
  * replaces flash_attn_with_kvcache                           [REF evo/generation.py:109-110,138-155]
