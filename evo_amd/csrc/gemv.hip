@@ -1,17 +1,25 @@
-// Skinny dense layer for decoding: y[M,N] = x[M,K] . W[N,K]^T (+ bias[N]) (+ residual[M,N]), M <= 16.
-//
-// Two kernels.  gemv_kernel (M <= 4, or any K % 8 == 0 shape): dot2 on the VALU, below.  skinny_mfma_kernel
-// (5 <= M <= 16, K % 32 == 0): the batch rows become the N side of v_mfma_f32_16x16x32_bf16 -- with 5+ rows the VALU
-// form spends more on re-reading x from L2 (M loads per R weight loads) than on the weights; here one 1-KiB x
-// fragment meets one 1-KiB weight fragment per MFMA and the math is free.
+// Weight-streaming dense layers for decoding and small batches: y[M,N] = x[M,K] . W[N,K]^T and what is fused around it.
 //
 // At batch 1-8 a decode step streams all 12.9 GB of weights once and is bound by HBM, not by MFMA: through
-// hipBLASLt's tile GEMM it ran at ~2.5 TB/s (5.2 ms/token).  This kernel is the weight-streaming form: one wave
+// hipBLASLt's tile GEMM it ran at ~2.5 TB/s (5.2 ms/token).  The dot2 kernels here are the weight-streaming form: one wave
 // owns R consecutive output rows, its lanes stride over K with 16-byte non-temporal loads straight into
 // VGPRs (no LDS round trip -- the operand is streamed once and shared with nobody), accumulates with
 // v_dot2c_f32_bf16 (two bf16 MACs per lane-op, fp32 accumulate, no unpack), and reduces across the wave at
 // the end.  x (<= 8 x K bf16) is re-read by every wave and lives in L2.
-// Entry point and reference citation: include/evo_mi355x.h.
+//
+// Seven kernels (batch rows M, K % 8 == 0 throughout):
+//   gemv_kernel             1 <= M <= 8 (5-8 only where K % 32 != 0)   dot2; + bias, + residual; SPLIT: four waves share R rows
+//   gemv_norm_kernel        1 <= M <= 4 any K, 5 <= M <= 8 at K = 4096 RMSNorm folded in front of the dot2 stream; + bias
+//   gemv_norm_hyena_kernel  same rows, D = K                           norm + Hyena projection + FIR / modal step + gate
+//   gemv_gate_kernel        same rows; without the norm 1 <= M <= 4    gated MLP input gelu(x W1^T) * (x W2^T), norm optional
+//   skinny_mfma_kernel      5 <= M <= 64, K % 32 == 0                  MFMA, K split over the eight waves of a workgroup
+//   skinny_nw_kernel        5 <= M <= 64, K % 256 == 0                 MFMA, n split: N >= 8192; SPLITK (+ ws) N < 8192; GATE
+//   skinny_reduce_kernel    17 <= M <= 64                              sums skinny_nw_kernel's SPLITK slices; + bias, + residual
+// The three norm-folding kernels run the same streaming loop; at K = 4096 they take its STAGE form (rows normalised once into LDS).
+// With 5+ rows the dot2 form spends more on re-reading x from L2 (M loads per R weight loads) than on the weights; in the
+// MFMA forms the batch rows become the N side of v_mfma_f32_16x16x32_bf16: one 1-KiB x fragment meets one 1-KiB weight
+// fragment per MFMA and the math is free.
+// Entry points and reference citation: include/evo_mi355x.h.
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
@@ -897,11 +905,24 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restr
     *(uint2*)(y + e) = out;
 }
 
-// host side: the skinny MFMA kernels' MT (m tiles of 16 batch rows, M <= 64) as a compile-time constant -- f(gv_int<MT>)
+// host side: compile-time constants from run-time row counts, as f(gv_int<V>).  for_mt: the skinny MFMA kernels' MT (m tiles of 16 batch
+// rows, M <= 64).  for_m: the dot2 kernels' M (1 <= M <= 8: the callers check).  for_m_stage: the norm-folding kernels' (M, STAGE), as
+// f(gv_int<M>, std::bool_constant<STAGE>) -- they exist LDS-staged (K = 4096: written out for four 1024-element trips) for 1-8 rows and
+// unstaged for 1-4, and nothing else is instantiated.
 template <int V> using gv_int = std::integral_constant<int, V>;
 template <class F>
 static void for_mt(int64_t M, F f) {
     if (M <= 16) f(gv_int<1>{}); else if (M <= 32) f(gv_int<2>{}); else if (M <= 48) f(gv_int<3>{}); else f(gv_int<4>{});
+}
+template <int V = 1, class F>
+static void for_m(int64_t M, F f) {
+    if constexpr (V == 8) f(gv_int<8>{}); else if (M == V) f(gv_int<V>{}); else for_m<V + 1>(M, f);
+}
+template <class F>
+static void for_m_stage(int64_t M, bool stage, F f) {
+    for_m(M, [&](auto m) {
+        if (stage) f(m, std::true_type{}); else if constexpr (decltype(m)::value <= 4) f(m, std::false_type{});
+    });
 }
 
 template <int M>
@@ -909,17 +930,13 @@ static void gemv_launch(const void* x, const void* w, const void* bias, const vo
                         hipStream_t s) {
     // rows per wave.  Measured (tools/bench_gemv.py, MI355X): R=4 wins for every M (R=8 starves the chip of
     // waves at N=4096; R=2 doubles the L2 re-reads of x): 4.9-5.4 TB/s at M=1-2, 3.0-3.6 TB/s at M=8.
-#define GEMV_R_A 4
-#define GEMV_R_B 4
-#define GEMV_R_C 4
-    constexpr int R = M <= 2 ? GEMV_R_A : (M <= 4 ? GEMV_R_B : GEMV_R_C);
+    constexpr int R = 4;
     const int64_t waves = (N + R - 1) / R;
-    if (N <= 4096 && K >= 2048)
-        hipLaunchKernelGGL((gemv_kernel<M, R, true>), dim3((unsigned)waves), dim3(256), 0, s, (const uint4*)x,
+    const auto launch = [&](auto split, int64_t groups) {
+        hipLaunchKernelGGL((gemv_kernel<M, R, decltype(split)::value>), dim3((unsigned)groups), dim3(256), 0, s, (const uint4*)x,
                            (const uint4*)w, (const uint16_t*)bias, (const uint16_t*)res, (uint16_t*)y, (int)N, (int)(K / 8));
-    else
-        hipLaunchKernelGGL((gemv_kernel<M, R, false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint4*)x,
-                           (const uint4*)w, (const uint16_t*)bias, (const uint16_t*)res, (uint16_t*)y, (int)N, (int)(K / 8));
+    };
+    if (N <= 4096 && K >= 2048) launch(std::true_type{}, waves); else launch(std::false_type{}, (waves + 3) / 4);
 }
 
 extern "C" int evo_norm_linear_small_m_bf16(const void* x, const void* scale, const void* w, const void* bias, void* y,
@@ -929,30 +946,12 @@ extern "C" int evo_norm_linear_small_m_bf16(const void* x, const void* scale, co
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(((N + 3) / 4 + 3) / 4)), block(256);
     const float isd = 1.0f / sqrtf((float)K);
-    const size_t lds = (size_t)M * K * 2;                   // normalised rows staged in LDS (when they fit)
-    const bool stage = K == 4096;                            // the staged kernels are written out for four 1024-element trips
-#define EVO_NL(MM)                                                                                            \
-    if (stage)                                                                                                \
-        hipLaunchKernelGGL((gemv_norm_kernel<MM, 4, true>), grid, block, lds, s, (const uint4*)x, (const uint4*)scale, \
-                           (const uint4*)w, (const uint16_t*)bias, (uint16_t*)y, (int)N, (int)(K / 8), eps, isd); \
-    else                                                                                                      \
-        hipLaunchKernelGGL((gemv_norm_kernel<MM, 4, false>), grid, block, 0, s, (const uint4*)x, (const uint4*)scale, \
-                           (const uint4*)w, (const uint16_t*)bias, (uint16_t*)y, (int)N, (int)(K / 8), eps, isd)
-#define EVO_NLS(MM)                                                                                           \
-    hipLaunchKernelGGL((gemv_norm_kernel<MM, 4, true>), grid, block, lds, s, (const uint4*)x, (const uint4*)scale, \
-                       (const uint4*)w, (const uint16_t*)bias, (uint16_t*)y, (int)N, (int)(K / 8), eps, isd)
-    switch (M) {
-        case 1: EVO_NL(1); break;
-        case 2: EVO_NL(2); break;
-        case 3: EVO_NL(3); break;
-        case 4: EVO_NL(4); break;
-        case 5: EVO_NLS(5); break;
-        case 6: EVO_NLS(6); break;
-        case 7: EVO_NLS(7); break;
-        default: EVO_NLS(8); break;
-    }
-#undef EVO_NLS
-#undef EVO_NL
+    const size_t lds = (size_t)M * K * 2;                   // normalised rows staged in LDS
+    for_m_stage(M, K == 4096, [&](auto m, auto st) {
+        constexpr bool ST = decltype(st)::value;
+        hipLaunchKernelGGL((gemv_norm_kernel<decltype(m)::value, 4, ST>), grid, block, ST ? lds : 0, s, (const uint4*)x, (const uint4*)scale,
+                           (const uint4*)w, (const uint16_t*)bias, (uint16_t*)y, (int)N, (int)(K / 8), eps, isd);
+    });
     return evo_launch_status();
 }
 
@@ -963,31 +962,21 @@ extern "C" int evo_hyena_decode_fused_small_m(const void* x, const void* norm_sc
     if (M < 1 || M > 8 || D <= 0 || D != n_heads * 128 || D % 8 != 0) return -1;
     if (M > 4 && D != 4096) return -1;                       // batches of 5-8 rows exist in the LDS-staged form only
     hipStream_t s = (hipStream_t)stream;
-    // channels per wave, measured under a hipGraph on MI355X (tools/experiments/hyena_decode_cpw_bench.py): one channel per wave
-    // (twice the waves, half the bytes in flight each) is 5 % faster at M = 1 and 6 % at M = 4, two channels win at M = 2
-    // (22.8 / 26.1 / 42.6 us with two, 21.6 / 29.9 / 40.0 us with one, M = 1 / 2 / 4).  Same arithmetic either way.
-#define GEMV_HYENA_CPW_STAGED 1
-#define GEMV_HYENA_CPW_STAGED1 1
     const float isd = 1.0f / sqrtf((float)D);
     const size_t lds = (size_t)M * D * 2;
-#define EVO_HD(MM, CPW, ST)                                                                                   \
-    hipLaunchKernelGGL((gemv_norm_hyena_kernel<MM, CPW, ST>), dim3((unsigned)((D / CPW + 3) / 4)), dim3(256), ST ? lds : 0, s, \
-                       (const uint4*)x, (const uint4*)norm_scale,                                             \
-                       (const uint4*)proj_w, (const uint16_t*)proj_b, (uint16_t*)fir_state, iir_state,          \
-                       (const uint16_t*)fir_w, (const uint16_t*)fir_b, poles, residues, (const uint16_t*)dskip, \
-                       (uint16_t*)y, (int)D, (int)(D / 8), eps, isd)
-    const bool stage = D == 4096;
-    switch (M) {
-        case 1: if (stage) EVO_HD(1, GEMV_HYENA_CPW_STAGED1, true); else EVO_HD(1, 1, false); break;
-        case 2: if (stage) EVO_HD(2, GEMV_HYENA_CPW_STAGED, true); else EVO_HD(2, 2, false); break;
-        case 3: if (stage) EVO_HD(3, GEMV_HYENA_CPW_STAGED, true); else EVO_HD(3, 2, false); break;
-        case 4: if (stage) EVO_HD(4, GEMV_HYENA_CPW_STAGED, true); else EVO_HD(4, 1, false); break;
-        case 5: EVO_HD(5, 1, true); break;
-        case 6: EVO_HD(6, 1, true); break;
-        case 7: EVO_HD(7, 1, true); break;
-        default: EVO_HD(8, 1, true); break;
-    }
-#undef EVO_HD
+    for_m_stage(M, D == 4096, [&](auto m, auto st) {
+        constexpr int MM = decltype(m)::value;
+        constexpr bool ST = decltype(st)::value;
+        // channels per wave, measured under a hipGraph on MI355X (tools/experiments/hyena_decode_cpw_bench.py): one channel per wave
+        // (twice the waves, half the bytes in flight each) is 5 % faster at M = 1 and 6 % at M = 4, two channels win at M = 2
+        // (22.8 / 26.1 / 42.6 us with two, 21.6 / 29.9 / 40.0 us with one, M = 1 / 2 / 4).  Same arithmetic either way.
+        // Unstaged: 1 / 2 / 2 / 1 at M = 1 / 2 / 3 / 4; staged: 1.
+        constexpr int CPW = !ST && (MM == 2 || MM == 3) ? 2 : 1;
+        hipLaunchKernelGGL((gemv_norm_hyena_kernel<MM, CPW, ST>), dim3((unsigned)((D / CPW + 3) / 4)), dim3(256), ST ? lds : 0, s,
+                           (const uint4*)x, (const uint4*)norm_scale, (const uint4*)proj_w, (const uint16_t*)proj_b, (uint16_t*)fir_state,
+                           iir_state, (const uint16_t*)fir_w, (const uint16_t*)fir_b, poles, residues, (const uint16_t*)dskip,
+                           (uint16_t*)y, (int)D, (int)(D / 8), eps, isd);
+    });
     return evo_launch_status();
 }
 
@@ -1000,32 +989,14 @@ static int mlp_gate_launch(const void* x, const void* scale, const void* w12, vo
     const dim3 grid((unsigned)((I / 2 + 3) / 4)), block(256);
     const float isd = 1.0f / sqrtf((float)K);
     const size_t lds = (size_t)M * K * 2;
-    const bool stage = scale && K == 4096;
-#define EVO_MG(MM)                                                                                            \
-    if (scale && stage)                                                                                       \
-        hipLaunchKernelGGL((gemv_gate_kernel<MM, true, true>), grid, block, lds, s, (const uint4*)x, (const uint4*)scale, \
-                           (const uint4*)w12, (uint16_t*)a, (int)I, (int)(K / 8), eps, isd, grp);             \
-    else if (scale)                                                                                           \
-        hipLaunchKernelGGL((gemv_gate_kernel<MM, true, false>), grid, block, 0, s, (const uint4*)x, (const uint4*)scale, \
-                           (const uint4*)w12, (uint16_t*)a, (int)I, (int)(K / 8), eps, isd, grp);             \
-    else                                                                                                      \
-        hipLaunchKernelGGL((gemv_gate_kernel<MM, false, false>), grid, block, 0, s, (const uint4*)x, (const uint4*)nullptr, \
-                           (const uint4*)w12, (uint16_t*)a, (int)I, (int)(K / 8), 0.f, 0.f, grp)
-#define EVO_MGS(MM)                                                                                           \
-    hipLaunchKernelGGL((gemv_gate_kernel<MM, true, true>), grid, block, lds, s, (const uint4*)x, (const uint4*)scale, \
-                       (const uint4*)w12, (uint16_t*)a, (int)I, (int)(K / 8), eps, isd, grp)
-    switch (M) {
-        case 1: EVO_MG(1); break;
-        case 2: EVO_MG(2); break;
-        case 3: EVO_MG(3); break;
-        case 4: EVO_MG(4); break;
-        case 5: EVO_MGS(5); break;
-        case 6: EVO_MGS(6); break;
-        case 7: EVO_MGS(7); break;
-        default: EVO_MGS(8); break;
-    }
-#undef EVO_MGS
-#undef EVO_MG
+    const auto launch = [&](auto m, auto norm, auto st) {
+        constexpr bool NORM = decltype(norm)::value, ST = decltype(st)::value;
+        hipLaunchKernelGGL((gemv_gate_kernel<decltype(m)::value, NORM, ST>), grid, block, ST ? lds : 0, s, (const uint4*)x, (const uint4*)scale,
+                           (const uint4*)w12, (uint16_t*)a, (int)I, (int)(K / 8), NORM ? eps : 0.f, NORM ? isd : 0.f, grp);
+    };
+    for_m_stage(M, scale && K == 4096, [&](auto m, auto st) {
+        if (scale) launch(m, std::true_type{}, st); else if constexpr (!decltype(st)::value) launch(m, std::false_type{}, st);
+    });
     return evo_launch_status();
 }
 
@@ -1102,15 +1073,6 @@ extern "C" int evo_linear_small_m_bf16(const void* x, const void* w, const void*
         });
         return evo_launch_status();
     }
-    switch (M) {
-        case 1: gemv_launch<1>(x, w, bias, residual, y, N, K, s); break;
-        case 2: gemv_launch<2>(x, w, bias, residual, y, N, K, s); break;
-        case 3: gemv_launch<3>(x, w, bias, residual, y, N, K, s); break;
-        case 4: gemv_launch<4>(x, w, bias, residual, y, N, K, s); break;
-        case 5: gemv_launch<5>(x, w, bias, residual, y, N, K, s); break;
-        case 6: gemv_launch<6>(x, w, bias, residual, y, N, K, s); break;
-        case 7: gemv_launch<7>(x, w, bias, residual, y, N, K, s); break;
-        default: gemv_launch<8>(x, w, bias, residual, y, N, K, s); break;
-    }
+    for_m(M, [&](auto m) { gemv_launch<decltype(m)::value>(x, w, bias, residual, y, N, K, s); });
     return evo_launch_status();
 }

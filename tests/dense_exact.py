@@ -237,9 +237,10 @@ SPLITK = [((33, 64), 1024, 1024, 4), ((33, 64), 1024, 2304, 8), ((33, 64), 8128,
           ((17, 32), 4096, 8192, 4), ((17, 32), 4096, 11008, 4)]            # (Ms, N, K, slices the launch must use; 0: must NOT split)
 GATE_SMALL_M = [1, 2, 3, 4, 5, 6, 7, 8, 13, 17, 40, 64]
 GATE_SMALL = [(40, 264), (64, 256), (1408, 4096), (11008, 4096)]            # (I, K); (40, 264): M <= 4 only
-NORM_LINEAR = [(4104, 4096), (12288, 4096), (4104, 256)]                    # (N, K); K = 256: M <= 4 (the forms that do not stage the rows in LDS)
-NORM_GATE = [(1408, 4096), (64, 256)]                                       # (I, K); K = 256: M <= 4
-HYENA_FUSED = [(4096, (1, 4, 5, 8)), (256, (1, 2, 3, 4))]                   # (D, Ms)
+# K = 256, 1024: M <= 4, the forms that do not stage the rows in LDS (32 vectors of 8: the single-slice tail only; 128: exactly one paired trip)
+NORM_LINEAR = [(4104, 4096), (12288, 4096), (4104, 256), (4104, 1024)]      # (N, K)
+NORM_GATE = [(1408, 4096), (64, 256), (64, 1024)]                           # (I, K)
+HYENA_FUSED = [(4096, (1, 4, 5, 8)), (256, (1, 2, 3, 4)), (1024, (1, 2, 3, 4))]   # (D, Ms)
 
 
 def all_reductions():

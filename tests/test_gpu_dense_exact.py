@@ -40,13 +40,13 @@ Instantiation -> the test that reaches it (ids abridged):
     skinny_nw_kernel<1..4, 4, false, GATE> (both layouts)      test_gate_small_m (M 5..8 -> MT 1, 13 -> 1, 17 -> 2, 40 -> 3, 64 -> 4)
   evo_norm_linear_small_m_bf16:
     gemv_norm_kernel<1..8, 4, true>                            test_norm_linear[4104-4096], [12288-4096]
-    gemv_norm_kernel<1..4, 4, false>                           test_norm_linear[4104-256]
+    gemv_norm_kernel<1..4, 4, false>                           test_norm_linear[4104-256], [4104-1024]
   evo_norm_mlp_gate_small_m_bf16:
     gemv_gate_kernel<1..8, true, true>                         test_norm_gate[1408-4096]
-    gemv_gate_kernel<1..4, true, false>                        test_norm_gate[64-256]
+    gemv_gate_kernel<1..4, true, false>                        test_norm_gate[64-256], [64-1024]
   evo_hyena_decode_fused_small_m:
     gemv_norm_hyena_kernel<1..8, 1, true>                      test_hyena_decode_fused[4096]   (z_t at every M; the outputs at M = 1, 4, 5, 8)
-    gemv_norm_hyena_kernel<1, 1 | 2, 2 | 3, 2 | 4, 1, false>   test_hyena_decode_fused[256]
+    gemv_norm_hyena_kernel<1, 1 | 2, 2 | 3, 2 | 4, 1, false>   test_hyena_decode_fused[256], [1024]
 """
 import time
 

@@ -86,11 +86,14 @@ def test_mlp_gate_fused_matches_unfused_and_fp64(M, I, K):
 
 
 @pytest.mark.parametrize("M", [1, 2, 4, 5, 7, 8])
-@pytest.mark.parametrize("N,K", [(12288, 4096), (4104, 264)])
+@pytest.mark.parametrize("N,K", [(12288, 4096), (4104, 264),
+                                 # the unstaged double-buffered loop with a refill (K / 8 > 192 vectors): 193 vectors (lane 0 alone refills, the
+                                 # other lanes end on a tail slice), 256 (whole trips, one refill)
+                                 (4104, 1544), (4104, 2048)])
 def test_norm_linear_fused_is_bitwise_the_two_kernels(M, N, K):
     """RMSNorm folded into the weight-streaming dense layer (M <= 4, or M <= 8 at K = 4096; N > 4096): the normalised row is
     rebuilt with the rmsnorm kernel's own reduction order, so the result equals rmsnorm -> linear bit for bit up to M = 4
-    (beyond: the two-kernel path sums on the MFMA; M = 7 at K = 264: the fallback)."""
+    (beyond: the two-kernel path sums on the MFMA; M = 7 at K != 4096: the fallback)."""
     from evo_amd.ops import default_ops
     ops = default_ops()
     g = torch.Generator().manual_seed(M * 13 + N + K)
@@ -110,26 +113,31 @@ def test_norm_linear_fused_is_bitwise_the_two_kernels(M, N, K):
     assert ((got.double() - want).norm() / want.norm()).item() < 4e-3
 
 
-@pytest.mark.parametrize("M", [1, 3, 4, 6, 8])
-def test_norm_mlp_gate_fused_is_bitwise_norm_then_gate(M):
+# K = 1544, 2048 (M <= 4): the unstaged double-buffered loop with a refill, as in test_norm_linear_fused_is_bitwise_the_two_kernels -- plain
+# layout and (I % 32 == 0) grouped; both sides of the comparison run it (with and without the norm)
+@pytest.mark.parametrize("M,I,K,grouped", [pytest.param(M, 11008, 4096, False, id=str(M)) for M in (1, 3, 4, 6, 8)]
+                         + [pytest.param(M, I, K, grouped, id=f"{M}-{I}-{K}-{'grouped' if grouped else 'plain'}") for M in (1, 3, 4)
+                            for I, K, grouped in ((40, 1544, False), (40, 2048, False), (64, 1544, True), (64, 2048, True))])
+def test_norm_mlp_gate_fused_is_bitwise_norm_then_gate(M, I, K, grouped):
     from evo_amd.ops import default_ops
     ops = default_ops()
-    I, K = 11008, 4096
     g = torch.Generator().manual_seed(M)
     x = (torch.randn(M, K, generator=g) * 2).bfloat16().to(DEV)
     scale = (1 + 0.1 * torch.randn(K, generator=g)).bfloat16().to(DEV)
     w12 = (torch.randn(2 * I, K, generator=g) * (1.5 / K ** 0.5)).bfloat16().to(DEV)
-    got = ops.mlp_gate(x, w12, scale, 1e-6)
-    two = ops.mlp_gate(ops.rmsnorm(x.clone(), None, scale, 1e-6), w12)
+    kw = dict(w12g=ops.pack_gate_weights(w12)) if grouped else {}
+    got = ops.mlp_gate(x, None if grouped else w12, scale, 1e-6, **kw)
+    two = ops.mlp_gate(ops.rmsnorm(x.clone(), None, scale, 1e-6), None if grouped else w12, **kw)
     if M <= 4:
         assert torch.equal(got, two)
-    else:     # 5-8 rows: fused = VALU sums, unfused = MFMA sums; both round l1 / l2 to bf16 before the gate
-        xd = ops.rmsnorm(x.clone(), None, scale, 1e-6).double()
-        u, v = (xd @ w12[:I].double().t()).bfloat16().double(), (xd @ w12[I:].double().t()).bfloat16().double()
-        want = torch.nn.functional.gelu(u) * v
-        err = (got.double() - want).abs()
-        assert bool((err <= want.abs() * 2.0 ** -6 + 2e-3 * want.abs().max()).all())
-        assert ((got.double() - want).norm() / want.norm()).item() < 4e-3
+    # 5-8 rows: fused = VALU sums, unfused = MFMA sums; both round l1 / l2 to bf16 before the gate.  Up to 4 rows both sides of the
+    # comparison above run the same streaming loop, so every case is held against fp64 as well
+    xd = ops.rmsnorm(x.clone(), None, scale, 1e-6).double()
+    u, v = (xd @ w12[:I].double().t()).bfloat16().double(), (xd @ w12[I:].double().t()).bfloat16().double()
+    want = torch.nn.functional.gelu(u) * v
+    err = (got.double() - want).abs()
+    assert bool((err <= want.abs() * 2.0 ** -6 + 2e-3 * want.abs().max()).all())
+    assert ((got.double() - want).norm() / want.norm()).item() < 4e-3
 
 
 def test_linear_residual_with_bias_small_m():
@@ -145,14 +153,15 @@ def test_linear_residual_with_bias_small_m():
     assert ((got.double() - want).abs() <= want.abs() * 2.0 ** -8 + 1e-2).all()
 
 
-@pytest.mark.parametrize("M", [1, 2, 4, 5])
-def test_hyena_decode_fused_is_bitwise_the_separate_kernels(M):
+@pytest.mark.parametrize("M,D,H", [pytest.param(M, 512, 4, id=str(M)) for M in (1, 2, 4, 5)]
+                         # D = 2176 (272 vectors): the unstaged loop with a refill, a second paired trip and a tail slice on lanes 0-15 only
+                         + [pytest.param(M, 2176, 17, id=f"{M}-2176-17") for M in (1, 2, 4, 5)])
+def test_hyena_decode_fused_is_bitwise_the_separate_kernels(M, D, H):
     """pre-norm + projections + FIR/modal step + gate in one launch == evo_norm_linear + evo_hyena_step, outputs AND the
     carried states, bit for bit, over several consecutive tokens (M = 5: the fallback of the same call)."""
     import math
     from evo_amd.ops import default_ops
     ops = default_ops()
-    D, H = 512, 4
     g = torch.Generator().manual_seed(M)
     scale = (1 + 0.1 * torch.randn(D, generator=g)).bfloat16().to(DEV)
     w = (torch.randn(3 * D, D, generator=g) / D ** 0.5).bfloat16().to(DEV)
