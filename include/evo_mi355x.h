@@ -272,7 +272,12 @@ int evo_attn_prefix_vt_bf16(const void* v_pre, void* vt_pre, int64_t P, int64_t 
  *            every token, and rows may be at DIFFERENT positions (continuous batching of decode streams);
  *   part_o [B, H, n_splits, 128] f32 and part_ml [B, H, n_splits, 2] f32: caller-owned workspace;
  *   n_splits <= 1024.  A bandwidth kernel (the KV cache is read once, 512 * H bytes per key): a WAVE owns a split = every
- *   n_splits-th 64-key block, requests the 32 KiB of a block at once and needs neither LDS nor barriers. */
+ *   n_splits-th 64-key block, requests the 32 KiB of a block at once and needs neither LDS nor barriers.
+ *   That kernel (attn_decode_stream_kernel) addresses a key by a 32-bit byte offset from the (batch, head) base, so it runs while
+ *   Tk * k_st * 2 < 2^32 - 1 and Tk * v_st * 2 < 2^32 - 1 (Tk as passed: the capacity).  A cache view beyond that -- e.g. capacity
+ *   262,144 at H = 32: 4 GiB per batch row -- takes the SECOND kernel, attn_fwd_kernel<true> (csrc/attn.hip: the MFMA split kernel,
+ *   64-bit tile bases, split s = ceil(n_tiles / n_splits) CONSECUTIVE 64-key tiles, splits past the last tile leave (m, l) = (-inf, 0)),
+ *   with the same part_o / part_ml layout, the same combine launch and the same bounds (tests/PARITY.md row 22g). */
 int evo_attn_decode_bf16(const void* q, const void* k, const void* v, void* o,
                          int64_t B, int64_t H, int64_t Tk,
                          int64_t q_sb, int64_t q_sh,
