@@ -728,7 +728,7 @@ __global__ __launch_bounds__(256) void attn_decode_stream_kernel(AttnArgs a) {
         o[e] += __shfl_xor(o[e], 32, 64);
     }
     if (split < a.n_splits) {
-        const int64_t slot = ((int64_t)bat * a.H + head) * a.n_splits + split;
+        const int64_t slot = ((int64_t)bat * a.H + head) * a.part_row + a.split0 + split;
         if (ks == 0) {
             float4* po = (float4*)(a.part_o + slot * DH + dc * 8);
             po[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -815,7 +815,7 @@ extern "C" int evo_attn_fwd_causal_bf16(const void* q, const void* k, const void
     // softmax_scale <= 0 (ABI 10): the queries are PRE-SCALED by softmax_scale * log2(e) (evo_rope_qk_bf16's q_scale): scores are exponents
     a.prescaled = softmax_scale <= 0.f ? 1 : 0;
     a.scale_log2 = a.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
-    a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1;
+    a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1; a.part_row = 1; a.split0 = 0;
     // query ranges longer than one 128-row block take the 64-rows-per-wave kernel of csrc/attn_w64.hip, or without its V^T workspace
     // (vt_ws == NULL) the 8-wave pipelined kernel of rounds 2-4; shorter ones the 128-row kernel
     a.nbh = (int)(B * H);
@@ -853,6 +853,7 @@ extern "C" int evo_attn_decode_bf16(const void* q, const void* k, const void* v,
     a.n_qblocks = 1; a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
     a.k_pre = nullptr; a.vt_pre = nullptr; a.kp_st = 0; a.kp_sh = 0; a.vtp_row = 0; a.n_pre = 0;
     a.dyn_pos = dyn_pos; a.part_o = part_o; a.part_ml = part_ml; a.n_splits = (int)n_splits; a.nbh = (int)(B * H);
+    a.part_row = (int)n_splits; a.split0 = 0;
     hipStream_t s = (hipStream_t)stream;
     // the streaming kernel, one split per wave; its 32-bit key offsets need both caches below 4 GiB, beyond that the MFMA split kernel
     if (Tk * k_st * 2 < 0xffffffffll && Tk * v_st * 2 < 0xffffffffll)
@@ -861,5 +862,214 @@ extern "C" int evo_attn_decode_bf16(const void* q, const void* k, const void* v,
         hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((unsigned)n_splits, (unsigned)H, (unsigned)B), dim3(256), 0, s, a);
     hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)H, (unsigned)B), dim3(512), 0, s, part_o, part_ml,
                        (uint16_t*)o, (int)H, (int)n_splits);
+    return evo_launch_status();
+}
+
+// ---- decode attention behind SHARED prompts (evo_attn_decode_prefix_bf16): the copies of a prompt that a decode pool samples from read
+// ONE stored K/V of that prompt instead of a private copy each.  A workgroup tile is GR consecutive batch rows (slots); a wave owns one
+// split of the prefix (blocks s, s + n_pre_splits, ... of the store row, the streaming kernel's map) and keeps an (m, l, o[8]) per row
+// of the tile.  For every DISTINCT store row among the tile's rows the wave streams that row's blocks once, through the same
+// double-buffered 32-key halves as attn_decode_stream_kernel, and reduces each half into the rows that reference it (a wave-uniform
+// branch per row; the per-row arithmetic is that kernel's, statement for statement).  A tile whose rows share one prompt reads it once,
+// a tile of GR different prompts reads GR streams: the arrangement of the slots decides the speed, never the result.  No LDS, no barrier.
+// GR = EVO_ATTN_GROUP_ROWS (include/evo_mi355x.h).
+struct AttnGroupArgs {
+    const uint16_t* q; const uint16_t* k_pre; const uint16_t* v_pre;
+    int64_t q_sb, q_sh, kp_sb, kp_st, kp_sh, vp_sb, vp_st, vp_sh;
+    const int64_t* pre_row;   // [B]: the store row a batch row continues, or -1
+    const int64_t* pre_len;   // [R]: keys held by each store row
+    int64_t R, P_cap;
+    float* part_o; float* part_ml;
+    int B, H, n_pre_splits, part_row;
+    float scale_log2;
+};
+
+template <int GR>
+__global__ __launch_bounds__(256) void attn_decode_group_kernel(AttnGroupArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int head = blockIdx.y, bat0 = blockIdx.z * GR;
+    const int split = blockIdx.x * 4 + wave;                 // one split of the prefix per wave
+    if (split >= a.n_pre_splits) return;                     // (no barrier below)
+    const int ks = lane >> 4, dc = lane & 15;
+    typedef const __attribute__((address_space(1))) unsigned char* gptr_t;
+    typedef unsigned int attn_u32x4 __attribute__((ext_vector_type(4)));
+    auto ld16 = [](gptr_t base, uint32_t off) {
+        const attn_u32x4 t = *(const __attribute__((address_space(1))) attn_u32x4*)(base + off);
+        return make_uint4(t[0], t[1], t[2], t[3]);
+    };
+    int pr[GR];                                              // wave-uniform: the tile's store rows (-1: none, or a row behind the batch)
+    uint4 qv[GR];
+    float m_run[GR], l_run[GR], o[GR][8];
+#pragma unroll
+    for (int r = 0; r < GR; ++r) {
+        const int bat = bat0 + r;
+        int64_t row = -1;
+        qv[r] = make_uint4(0u, 0u, 0u, 0u);
+        if (bat < a.B) {
+            row = a.pre_row[bat];
+            qv[r] = ((const uint4*)(a.q + bat * a.q_sb + head * a.q_sh))[dc];
+        }
+        pr[r] = row >= 0 && row < a.R ? (int)row : -1;
+        m_run[r] = -INFINITY; l_run[r] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[r][e] = 0.f;
+    }
+    const uint32_t kst = (uint32_t)(a.kp_st * 2), vst = (uint32_t)(a.vp_st * 2), dco = (uint32_t)dc * 16;
+    const int ns = a.n_pre_splits;
+#pragma nounroll
+    for (int g = 0; g < GR; ++g) {                           // row g leads its store row unless an earlier row of the tile named it
+        int row = -1;
+#pragma unroll
+        for (int r = 0; r < GR; ++r) row = r == g ? pr[r] : row;
+        bool lead = row >= 0;
+        unsigned members = 0;
+#pragma unroll
+        for (int r = 0; r < GR; ++r)
+            if (pr[r] == row) { members |= 1u << r; lead = lead && r >= g; }
+        if (!lead) continue;
+        int64_t n_keys = a.pre_len[row];
+        n_keys = n_keys < a.P_cap ? n_keys : a.P_cap;
+        if (n_keys <= 0) continue;
+        const int nblk = (int)((n_keys + 63) >> 6);
+        const int nhalf = (int)((n_keys + 31) >> 5);
+        const gptr_t kp = (gptr_t)(uint64_t)(a.k_pre + row * a.kp_sb + head * a.kp_sh);
+        const gptr_t vp = (gptr_t)(uint64_t)(a.v_pre + row * a.vp_sb + head * a.vp_sh);
+        const int nb_my = split < nblk ? (nblk - split + ns - 1) / ns : 0;
+        auto half_of = [&](int jh) { return 2 * (split + (jh >> 1) * ns) + (jh & 1); };
+        int n_my = 2 * nb_my;
+        if (n_my > 0 && half_of(n_my - 1) >= nhalf) --n_my;
+        auto load_half = [&](int jh, uint4 (&kr)[8], uint4 (&vr)[8]) {
+            const int64_t k0 = (int64_t)half_of(jh) * 32 + ks;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                int64_t key = k0 + 4 * i;
+                key = key < n_keys ? key : n_keys - 1;       // a ragged last half re-reads the last key (masked below)
+                kr[i] = ld16(kp, (uint32_t)key * kst + dco);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                int64_t key = k0 + 4 * i;
+                key = key < n_keys ? key : n_keys - 1;
+                vr[i] = ld16(vp, (uint32_t)key * vst + dco);
+            }
+        };
+        auto reduce_half = [&](int jh, const uint4 (&kr)[8], const uint4 (&vr)[8]) {
+            const int64_t k0 = (int64_t)half_of(jh) * 32 + ks;
+#pragma unroll
+            for (int r = 0; r < GR; ++r) {
+                if (!(members & (1u << r))) continue;        // wave-uniform
+                float sc[8];
+                float mb = -INFINITY;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    float d = attn_dot8(kr[i], qv[r]);
+                    d += __shfl_xor(d, 1, 64);
+                    d += __shfl_xor(d, 2, 64);
+                    d += __shfl_xor(d, 4, 64);
+                    d += __shfl_xor(d, 8, 64);
+                    sc[i] = k0 + 4 * i < n_keys ? d * a.scale_log2 : -INFINITY;
+                    mb = fmaxf(mb, sc[i]);
+                }
+                mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+                mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+                const float m_new = fmaxf(m_run[r], mb);     // finite: the half holds at least one key
+                const float alpha = __builtin_amdgcn_exp2f(m_run[r] - m_new);
+                l_run[r] *= alpha;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[r][e] *= alpha;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float pw = __builtin_amdgcn_exp2f(sc[i] - m_new);
+                    l_run[r] += pw;
+                    o[r][0] = fmaf(pw, bf_lo(vr[i].x), o[r][0]); o[r][1] = fmaf(pw, bf_hi(vr[i].x), o[r][1]);
+                    o[r][2] = fmaf(pw, bf_lo(vr[i].y), o[r][2]); o[r][3] = fmaf(pw, bf_hi(vr[i].y), o[r][3]);
+                    o[r][4] = fmaf(pw, bf_lo(vr[i].z), o[r][4]); o[r][5] = fmaf(pw, bf_hi(vr[i].z), o[r][5]);
+                    o[r][6] = fmaf(pw, bf_lo(vr[i].w), o[r][6]); o[r][7] = fmaf(pw, bf_hi(vr[i].w), o[r][7]);
+                }
+                m_run[r] = m_new;
+            }
+        };
+        uint4 kA[8], vA[8], kB[8], vB[8];
+        if (n_my > 0) load_half(0, kA, vA);
+        for (int jh = 0; jh < n_my; jh += 2) {
+            if (jh + 1 < n_my) load_half(jh + 1, kB, vB);
+            reduce_half(jh, kA, vA);
+            if (jh + 1 < n_my) {
+                if (jh + 2 < n_my) load_half(jh + 2, kA, vA);
+                reduce_half(jh + 1, kB, vB);
+            }
+        }
+    }
+    // every row of the tile writes its split: a row without a prefix (or whose split took no block) writes (-inf, 0) and ZEROS --
+    // the combine gives such a split the weight 0, and 0 x NaN would be NaN
+#pragma unroll
+    for (int r = 0; r < GR; ++r) {
+        const int bat = bat0 + r;
+        if (bat >= a.B) continue;
+        float lr = l_run[r];
+        lr += __shfl_xor(lr, 16, 64);
+        lr += __shfl_xor(lr, 32, 64);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            o[r][e] += __shfl_xor(o[r][e], 16, 64);
+            o[r][e] += __shfl_xor(o[r][e], 32, 64);
+        }
+        const int64_t slot = ((int64_t)bat * a.H + head) * a.part_row + split;
+        if (ks == 0) {
+            float4* po = (float4*)(a.part_o + slot * DH + dc * 8);
+            po[0] = make_float4(o[r][0], o[r][1], o[r][2], o[r][3]);
+            po[1] = make_float4(o[r][4], o[r][5], o[r][6], o[r][7]);
+        }
+        if (lane == 0) { a.part_ml[slot * 2] = m_run[r]; a.part_ml[slot * 2 + 1] = lr; }
+    }
+}
+
+extern "C" int evo_attn_decode_prefix_bf16(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
+                                           int64_t Tk, int64_t q_sb, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                                           int64_t v_sb, int64_t v_st, int64_t v_sh, const int64_t* own_pos, const void* k_pre,
+                                           const void* v_pre, int64_t R, int64_t P_cap, int64_t kp_sb, int64_t kp_st,
+                                           int64_t kp_sh, int64_t vp_sb, int64_t vp_st, int64_t vp_sh, const int64_t* pre_row,
+                                           const int64_t* pre_len, float* part_o, float* part_ml, int64_t n_pre_splits,
+                                           int64_t n_splits, float softmax_scale, void* stream) {
+    if (!q || !k || !v || !o || !own_pos || !k_pre || !v_pre || !pre_row || !pre_len || !part_o || !part_ml) return -1;
+    if (B <= 0 || H <= 0 || Tk <= 0 || R < 1 || P_cap < 1 || n_pre_splits < 1 || n_splits < 1 ||
+        n_pre_splits + n_splits > ATTN_MAX_SPLITS) return -1;
+    if (attn_check_strides(q_sb, 8, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh)) return -1;
+    if (attn_check_strides(8, 8, 8, kp_sb, kp_st, kp_sh, vp_sb, vp_st, vp_sh)) return -1;
+    if (H > 65535 || B > 65535) return -1;
+    if (k_st <= 0 || v_st <= 0 || kp_st <= 0 || vp_st <= 0) return -1;
+    // both kernels address keys with 32-bit offsets from a wave-uniform base: this entry has no other form to fall back on
+    const int64_t lim = 0xffffffffll;
+    if (Tk > lim / (k_st * 2) || Tk > lim / (v_st * 2) || P_cap > lim / (kp_st * 2) || P_cap > lim / (vp_st * 2)) return -1;
+    if (Tk * k_st * 2 >= lim || Tk * v_st * 2 >= lim || P_cap * kp_st * 2 >= lim || P_cap * vp_st * 2 >= lim) return -1;
+    const float scale_log2 = softmax_scale <= 0.f ? 1.0f : softmax_scale * 1.4426950408889634f;
+    const int n_tot = (int)(n_pre_splits + n_splits);
+    hipStream_t s = (hipStream_t)stream;
+    AttnGroupArgs g;
+    g.q = (const uint16_t*)q; g.k_pre = (const uint16_t*)k_pre; g.v_pre = (const uint16_t*)v_pre;
+    g.q_sb = q_sb; g.q_sh = q_sh; g.kp_sb = kp_sb; g.kp_st = kp_st; g.kp_sh = kp_sh; g.vp_sb = vp_sb; g.vp_st = vp_st; g.vp_sh = vp_sh;
+    g.pre_row = pre_row; g.pre_len = pre_len; g.R = R; g.P_cap = P_cap;
+    g.part_o = part_o; g.part_ml = part_ml;
+    g.B = (int)B; g.H = (int)H; g.n_pre_splits = (int)n_pre_splits; g.part_row = n_tot;
+    g.scale_log2 = scale_log2;
+    constexpr int GR = EVO_ATTN_GROUP_ROWS;
+    hipLaunchKernelGGL(attn_decode_group_kernel<GR>, dim3((unsigned)((n_pre_splits + 3) / 4), (unsigned)H, (unsigned)((B + GR - 1) / GR)),
+                       dim3(256), 0, s, g);
+    AttnArgs a;
+    a.q = (const uint16_t*)q; a.k = (const uint16_t*)k; a.v = (const uint16_t*)v; a.o = (uint16_t*)o;
+    a.Tq = 1; a.Tk = Tk; a.q_pos0 = Tk - 1;
+    a.q_sb = q_sb; a.q_st = 0; a.q_sh = q_sh; a.k_sb = k_sb; a.k_st = k_st; a.k_sh = k_sh;
+    a.v_sb = v_sb; a.v_st = v_st; a.v_sh = v_sh;
+    a.H = (int)H;
+    a.prescaled = softmax_scale <= 0.f ? 1 : 0;
+    a.scale_log2 = scale_log2;
+    a.n_qblocks = 1; a.q_pad = 0; a.vt = nullptr; a.vt_row = 0;
+    a.k_pre = nullptr; a.vt_pre = nullptr; a.kp_st = 0; a.kp_sh = 0; a.vtp_row = 0; a.n_pre = 0;
+    a.dyn_pos = own_pos; a.part_o = part_o; a.part_ml = part_ml; a.n_splits = (int)n_splits; a.nbh = (int)(B * H);
+    a.part_row = n_tot; a.split0 = (int)n_pre_splits;       // the own keys' splits lie behind the prefix's
+    hipLaunchKernelGGL(attn_decode_stream_kernel, dim3((unsigned)((n_splits + 3) / 4), (unsigned)H, (unsigned)B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)H, (unsigned)B), dim3(512), 0, s, part_o, part_ml,
+                       (uint16_t*)o, (int)H, n_tot);
     return evo_launch_status();
 }

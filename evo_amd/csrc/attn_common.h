@@ -24,6 +24,8 @@ struct AttnArgs {
     float* part_o;            // [B, H, n_splits, 128] unnormalised partial outputs
     float* part_ml;           // [B, H, n_splits, 2]   running max (log2 domain) and denominator
     int n_splits;
+    int part_row, split0;     // attn_decode_stream_kernel: splits per (batch, head) row of part_o / part_ml and the index of this launch's first one
+                              // (n_splits, 0 unless the splits of another key range lie in front: evo_attn_decode_prefix_bf16)
     int nbh;                  // B * H (prefill: 1-D grid of n_qblocks * nbh workgroups)
     int q_pad;                // attn_fwd_w64_kernel: query blocks are aligned to the END of the query range; block 0 starts at row -q_pad
     const uint16_t* vt;       // attn_fwd_w64_kernel: V^T [B][H][128][vt_row] (keys contiguous; written by attn_vt_kernel from v)

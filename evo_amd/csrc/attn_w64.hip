@@ -815,7 +815,7 @@ extern "C" int evo_attn_fwd_prefix_bf16(const void* q, const void* k, const void
     a.H = (int)H;
     a.prescaled = softmax_scale <= 0.f ? 1 : 0;
     a.scale_log2 = a.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
-    a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1;
+    a.dyn_pos = nullptr; a.part_o = nullptr; a.part_ml = nullptr; a.n_splits = 1; a.part_row = 1; a.split0 = 0;
     a.nbh = (int)(B * H);
     a.n_qblocks = (int)((Tq + W_QB - 1) / W_QB);
     a.q_pad = (int)((int64_t)a.n_qblocks * W_QB - Tq);

@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256) void rope_append_decode_kernel(uint4* __restri
                                                                  const int64_t* __restrict__ pos,
                                                                  const float* __restrict__ inv_freq, float scaling, int B,
                                                                  int H, int hd, int64_t kv_sb, int64_t kv_st, int64_t kv_sw,
-                                                                 int64_t kv_sh, float q_scale) {   // kv strides in 16-byte vectors
+                                                                 int64_t kv_sh, float q_scale,
+                                                                 const int64_t* __restrict__ widx) {   // kv strides in 16-byte vectors
     const int half_vec = hd / 16;
     const int total = B * H * half_vec;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -312,7 +313,8 @@ __global__ __launch_bounds__(256) void rope_append_decode_kernel(uint4* __restri
         si[e] = round_bf(sinf(f));
     }
     const int rv = hd / 8;                                   // vectors per head row
-    uint4* krow = kv + b * kv_sb + p * kv_st + h * kv_sh;
+    const int64_t w = widx ? widx[b] : p;                    // the cache row written (evo_rope_append_decode_at_bf16); the angle stays pos's
+    uint4* krow = kv + b * kv_sb + w * kv_st + h * kv_sh;
     uint4* vrow = krow + kv_sw;
 #pragma unroll
     for (int which = 0; which < 2; ++which) {                // q, k
@@ -344,7 +346,19 @@ extern "C" int evo_rope_append_decode_bf16(void* qkv, void* kv, const int64_t* p
     const int total = (int)(B * H * (hd / 16));
     hipLaunchKernelGGL(rope_append_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (uint4*)qkv, (uint4*)kv, pos, inv_freq, scaling, (int)B, (int)H, (int)hd, kv_sb / 8, kv_st / 8, kv_sw / 8,
-                       kv_sh / 8, q_scale);
+                       kv_sh / 8, q_scale, (const int64_t*)nullptr);
+    return evo_launch_status();
+}
+
+extern "C" int evo_rope_append_decode_at_bf16(void* qkv, void* kv, const int64_t* pos, const float* inv_freq, float scaling,
+                                              int64_t B, int64_t H, int64_t hd, int64_t kv_sb, int64_t kv_st, int64_t kv_sw,
+                                              int64_t kv_sh, float q_scale, const int64_t* widx, void* stream) {
+    if (B <= 0 || H <= 0 || hd <= 0 || hd % 16 != 0 || !qkv || !kv || !pos || !widx || !inv_freq || scaling <= 0.f || !(q_scale > 0.f)) return -1;
+    if ((kv_sb % 8) || (kv_st % 8) || (kv_sw % 8) || (kv_sh % 8) || B * H * (hd / 16) > 0x7fffffff) return -1;
+    const int total = (int)(B * H * (hd / 16));
+    hipLaunchKernelGGL(rope_append_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (uint4*)qkv, (uint4*)kv, pos, inv_freq, scaling, (int)B, (int)H, (int)hd, kv_sb / 8, kv_st / 8, kv_sw / 8,
+                       kv_sh / 8, q_scale, widx);
     return evo_launch_status();
 }
 

@@ -61,11 +61,15 @@ _SIGNATURES = {
     "evo_unembed_profile_bf16": ([_PTR] * 3 + [_c.POINTER(_c.c_int32), _I64] + [_PTR] * 3 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_rope_append_decode_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR], _c.c_int),
     "evo_pool_rows_bf16": ([_PTR, _I64, _I64, _I64, _PTR, _I64, _PTR, _F32, _I64, _I64, _PTR, _PTR, _PTR], _c.c_int),
+    "evo_attn_decode_prefix_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64] * 8 + [_PTR] * 4 + [_I64, _I64, _F32, _PTR], _c.c_int),
+    "evo_rope_append_decode_at_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR, _PTR], _c.c_int),
     "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 14        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 15        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
+                        # `prefix_streams` counter is computed from it on the host)
 
 
 class EvoLibraryError(RuntimeError):
@@ -859,9 +863,11 @@ class HipOps:
         return qkv
 
     def rope_append_decode(self, qkv: torch.Tensor, kv: torch.Tensor, pos: torch.Tensor, inv_freq: torch.Tensor,
-                           scaling: float, q_scale: float = 1.0) -> None:
+                           scaling: float, q_scale: float = 1.0, widx: Optional[torch.Tensor] = None) -> None:
         """One decode token per stream: NeoX rotary on q and k of qkv [B,1,3,H,hd] (in place) at position pos[b] (/ scaling) and
-        kv[b, pos[b]] = (k, v) -- kv [>=B, cap, 2, H, hd].  One launch; bit-identical to the rotary table + rope_ + indexed copy."""
+        kv[b, pos[b]] = (k, v) -- kv [>=B, cap, 2, H, hd].  One launch; bit-identical to the rotary table + rope_ + indexed copy.
+        `widx` (device int64 [B]): the row is written at kv[b, widx[b]] instead; the angle stays pos[b]'s (a cache that starts behind
+        a prompt stored elsewhere: attention_decode_prefix)."""
         self._need(qkv, torch.bfloat16, "rope_append_decode qkv")
         B, T, three, H, hd = qkv.shape
         if T != 1 or three != 3 or kv.dtype != torch.bfloat16 or not kv.is_cuda or kv.stride(-1) != 1 or kv.shape[0] < B:
@@ -871,6 +877,15 @@ class HipOps:
             raise RuntimeError("rope_append_decode pos: need a contiguous device int64 tensor with B entries")
         self._check_address(pos.data_ptr(), "rope_append_decode pos", 8)
         self._need(inv_freq, torch.float32, "rope_append_decode inv_freq")
+        if widx is not None:
+            if widx.dtype != torch.int64 or not widx.is_cuda or widx.numel() != B or not widx.is_contiguous():
+                raise RuntimeError("rope_append_decode widx: need a contiguous device int64 tensor with B entries")
+            self._check_address(widx.data_ptr(), "rope_append_decode widx", 8)
+            _check(self.lib.evo_rope_append_decode_at_bf16(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(),
+                                                           float(scaling), B, H, hd, kv.stride(0), kv.stride(1), kv.stride(2),
+                                                           kv.stride(3), float(q_scale), widx.data_ptr(), _stream()),
+                   "evo_rope_append_decode_at_bf16")
+            return
         _check(self.lib.evo_rope_append_decode_bf16(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(),
                                                     float(scaling), B, H, hd, kv.stride(0), kv.stride(1), kv.stride(2),
                                                     kv.stride(3), float(q_scale), _stream()), "evo_rope_append_decode_bf16")
@@ -981,6 +996,52 @@ class HipOps:
                 k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2), _ptr(pos),
                 part_o.data_ptr(), part_ml.data_ptr(), n_splits, 0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()),
                 "evo_attn_decode_bf16")
+        return o
+
+    attn_group_rows = ATTN_GROUP_ROWS
+
+    @staticmethod
+    def _decode_splits(n_keys: int) -> int:
+        """attention_decode's rule (see there): one split per wave, whole workgroups of four, at most one per 64-key block, at most 32."""
+        return min(((n_keys + 63) // 64 + 3) // 4 * 4, 32)
+
+    def attention_decode_prefix(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, own_pos: torch.Tensor,
+                                k_store: torch.Tensor, v_store: torch.Tensor, pre_row: torch.Tensor, pre_len: torch.Tensor,
+                                n_splits: Optional[int] = None, n_pre_splits: Optional[int] = None, prescaled: bool = False) -> torch.Tensor:
+        """One query per row behind a SHARED prompt: q [B,1,H,128]; k / v [B,cap,H,128] the rows' own caches, row b holds keys
+        [0, own_pos[b]]; k_store / v_store [R,P_cap,H,128] views of a prompt store, pre_row [B] the store row each batch row continues
+        (-1: none), pre_len [R] the keys each store row holds.  Row b sees the store row's keys, then its own -- `attention_decode` on the
+        concatenation without a copy of the prompt per row.  All four index vectors are device int64 (nothing is read back)."""
+        B, Tq, H, hd = q.shape
+        if Tq != 1 or hd != 128:
+            raise RuntimeError("attention_decode_prefix: expects [B,1,H,128] queries")
+        for t, nm in ((q, "q"), (k, "k"), (v, "v"), (k_store, "k_store"), (v_store, "v_store")):
+            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1 or t.dim() != 4:
+                raise RuntimeError(f"attention_decode_prefix {nm}: need a 4-d ROCm bf16 tensor with a dense last dim")
+            self._check_address(t.data_ptr(), f"attention_decode_prefix {nm}")
+        R, P_cap = k_store.shape[:2]
+        if k.shape[0] < B or v.shape != k.shape or tuple(k.shape[2:]) != (H, hd) or v_store.shape != k_store.shape or tuple(k_store.shape[2:]) != (H, hd) \
+                or R < 1 or P_cap < 1:
+            raise RuntimeError("attention_decode_prefix: expects k / v [B,cap,H,128] and k_store / v_store [R,P_cap,H,128]")
+        for t, n, nm in ((own_pos, B, "own_pos"), (pre_row, B, "pre_row"), (pre_len, R, "pre_len")):
+            if t.dtype != torch.int64 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+                raise RuntimeError(f"attention_decode_prefix {nm}: need a contiguous device int64 tensor with {n} entries")
+            self._check_address(t.data_ptr(), f"attention_decode_prefix {nm}", 8)
+        Tk = k.shape[1]
+        n_splits = self._decode_splits(Tk) if n_splits is None else int(n_splits)
+        n_pre_splits = self._decode_splits(P_cap) if n_pre_splits is None else int(n_pre_splits)
+        n_tot = n_splits + n_pre_splits
+        o = torch.empty(B, 1, H, hd, dtype=torch.bfloat16, device=q.device)
+        part_o = torch.empty(B, H, n_tot, hd, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(B, H, n_tot, 2, dtype=torch.float32, device=q.device)
+        with self._t("attn_decode_prefix"):
+            _check(self.lib.evo_attn_decode_prefix_bf16(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, H, Tk, q.stride(0), q.stride(2),
+                k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2), own_pos.data_ptr(),
+                k_store.data_ptr(), v_store.data_ptr(), R, P_cap, k_store.stride(0), k_store.stride(1), k_store.stride(2),
+                v_store.stride(0), v_store.stride(1), v_store.stride(2), pre_row.data_ptr(), pre_len.data_ptr(),
+                part_o.data_ptr(), part_ml.data_ptr(), n_pre_splits, n_splits, 0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()),
+                "evo_attn_decode_prefix_bf16")
         return o
 
     def norm_linear(self, x: torch.Tensor, scale: torch.Tensor, eps: float, w: torch.Tensor,

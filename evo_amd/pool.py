@@ -21,6 +21,11 @@ last node of the step (captured with it), writes the next ids where the next ste
 a device-resident history, so the host reads nothing back per step -- a job's rows are copied out once, when its slot finishes.
 Every job draws from its own random stream (its output index), so a sample does not depend on the slot it ran in, on the step
 it was admitted at, or on the other prompts of the job -- for a fixed `n_slots` (the logits themselves depend on the row count).
+
+`share_prompt_kv=True` (opt-in): the copies of a prompt no longer get a private copy of its K/V each.  A prompt's
+K/V is installed ONCE into a row of a `PromptStore`; a slot's own cache holds only the `n_tokens` it generates, and the decode
+attention reads the store row and then the slot's own keys (`HipOps.attention_decode_prefix`).  Which store row a slot continues, how
+many keys that row holds and the slot's own index are device vectors, so the captured step still replays while slots are re-filled.
 """
 from __future__ import annotations
 
@@ -31,14 +36,19 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
+from .sh.cache import PromptStore
 from .sh.sample import allowed_mask, sample
 
 
 class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
-                 seed: Optional[int] = None, allowed_tokens=None):
+                 seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False):
         self.model = model
+        self.share_prompt_kv = bool(share_prompt_kv)
+        if self.share_prompt_kv and not hasattr(getattr(model, "ops", None), "attention_decode_prefix"):
+            raise RuntimeError("share_prompt_kv=True needs a compute backend with attention_decode_prefix (the decode attention over a "
+                               "shared prompt store); this model's backend has none")
         self.tok = tokenizer
         self.n_slots = int(n_slots)
         self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
@@ -49,6 +59,12 @@ class DecodePool:
         self.capacity = 0
         self._graph = None
         self.stats = {"steps": 0, "prefills": 0, "tokens": 0}
+        if self.share_prompt_kv:
+            self.stats.update({"prompt_kv_installs": 0, "store_rows": 0, "prefix_streams": 0})
+        self.store = None
+        self.store_refs: List[int] = []                              # host: live copies per store row
+        self._store_prompt: List[Optional[int]] = []                 # host: the prompt a store row holds (kept after its last copy finished)
+        self._slot_row: List[int] = []                               # host mirror of store.row
         # seeded / restricted sampling runs on the device; with neither the host sampler of the reference stays (the default)
         self.device_sampler = seed is not None or allowed_tokens is not None
         self.seed = 0 if seed is None else int(seed)
@@ -85,16 +101,97 @@ class DecodePool:
         self._graph = None
         self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
         self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
-        if self.device_sampler:                                      # per-slot sampler state, all of it read by the captured launch
-            self.s_top_k = torch.full((S,), int(self.top_k), dtype=torch.int32, device=dev)
-            self.s_top_p = torch.full((S,), float(self.top_p), dtype=torch.float32, device=dev)
-            self.s_temperature = torch.full((S,), float(self.temperature), dtype=torch.float32, device=dev)
-            self.s_stream = torch.zeros(S, dtype=torch.int64, device=dev)
-            self.s_count = torch.zeros(S, dtype=torch.int64, device=dev)
-            self.s_active = torch.zeros(S, dtype=torch.bool, device=dev)
-            self.s_logprob = torch.zeros(S, dtype=torch.float32, device=dev)
-            self.s_allow = None if self.allow_mask is None else m.ops.pack_allow_mask(self.allow_mask, dev)
-            self.hist_ids = self.hist_logits = None
+        if self.device_sampler:
+            self._allocate_sampler_state()
+
+    def _allocate_sampler_state(self) -> None:
+        m, S, dev = self.model, self.n_slots, self.device
+        # per-slot sampler state, all of it read by the captured launch
+        self.s_top_k = torch.full((S,), int(self.top_k), dtype=torch.int32, device=dev)
+        self.s_top_p = torch.full((S,), float(self.top_p), dtype=torch.float32, device=dev)
+        self.s_temperature = torch.full((S,), float(self.temperature), dtype=torch.float32, device=dev)
+        self.s_stream = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.s_count = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.s_active = torch.zeros(S, dtype=torch.bool, device=dev)
+        self.s_logprob = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.s_allow = None if self.allow_mask is None else m.ops.pack_allow_mask(self.allow_mask, dev)
+        self.hist_ids = self.hist_logits = None
+
+    def _allocate_shared(self, p_max: int, n_tokens: int, n_sample_per_prompt: int) -> None:
+        """share_prompt_kv: own caches of `n_tokens` rows per slot and a store of R rows of the longest prompt's length.  Jobs run in
+        order and have one length, so the live jobs are a window of at most S consecutive jobs: they touch at most ceil(S / n) + 1
+        prompts (and never more than S)."""
+        m, S, dev = self.model, self.n_slots, self.device
+        R = min(S, -(-S // int(n_sample_per_prompt)) + 1)
+        st = self.store
+        if st is not None and self.capacity >= n_tokens and self.store_cap >= p_max and len(self.store_refs) >= R:
+            self._store_prompt = [None] * len(self.store_refs)       # prompt indices belong to one job list
+            return
+        ipd = m.initialize_inference_params()
+        ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
+        ipd["mha"].max_seqlen = n_tokens
+        D, H, hd = m.hidden_size, m.num_heads, m.head_dim
+        dt = m.embedding_layer.weight.dtype
+        st = PromptStore(row=torch.full((S,), -1, dtype=torch.int64, device=dev), length=torch.ones(R, dtype=torch.int64, device=dev),
+                         own_pos=torch.zeros(S, dtype=torch.int64, device=dev))
+        for i in m.attn_layer_idxs:
+            ipd["mha"].key_value_memory_dict[i] = torch.zeros(S, n_tokens, 2, H, hd, dtype=dt, device=dev)
+            st.kv[i] = torch.zeros(R, p_max, 2, H, hd, dtype=dt, device=dev)
+        for i in m.hyena_layer_idxs:
+            ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
+            ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
+        ipd["mha"].prompt_store = st
+        self.ipd, self.capacity, self.store, self.store_cap = ipd, n_tokens, st, p_max
+        self.store_refs, self._store_prompt, self._slot_row = [0] * R, [None] * R, [-1] * S
+        self.stats["store_rows"] = R
+        self._graph = None
+        self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+        if self.device_sampler:
+            self._allocate_sampler_state()
+
+    def _install_shared(self, slot: int, pi: int, tmp: dict, P: int) -> None:
+        """Slot `slot` continues prompt `pi`: its K/V goes into a store row unless one holds it already; the Hyena states stay per slot."""
+        m, st = self.model, self.store
+        if pi in self._store_prompt:
+            r = self._store_prompt.index(pi)
+        else:
+            r = self.store_refs.index(0)                             # (exists: see _allocate_shared)
+            for i in m.attn_layer_idxs:
+                st.kv[i][r, :P] = tmp["mha"].key_value_memory_dict[i][0, :P]
+            st.length[r] = P
+            self._store_prompt[r] = pi
+            self.stats["prompt_kv_installs"] += 1
+        self.store_refs[r] += 1
+        self._slot_row[slot] = r
+        st.row[slot] = r
+        st.own_pos[slot] = 0
+        for i in m.hyena_layer_idxs:
+            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][0]
+            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][0].reshape(
+                self.ipd["hyena"].state_dict[i][slot].shape)
+
+    def _release_shared(self, slots: Sequence[int]) -> None:
+        """Finished slots let go of their store rows (the host knows when: a job's length is fixed) and point at none."""
+        for s in slots:
+            self.store_refs[self._slot_row[s]] -= 1
+            self._slot_row[s] = -1
+        self.store.row[torch.tensor(list(slots), dtype=torch.int64, device=self.device)] = -1
+
+    def _advance(self) -> None:
+        """Every slot moves on by one token (idle slots drift harmlessly; fill() resets them)."""
+        self.pos.add_(1)
+        if self.share_prompt_kv:
+            self.pos.clamp_(max=self.store_cap + self.capacity - 1)
+            self.store.own_pos.add_(1)
+            self.store.own_pos.clamp_(max=self.capacity - 1)
+        else:
+            self.pos.clamp_(max=self.capacity - 1)
+
+    def _count_prefix_streams(self) -> None:
+        """The store rows one step streams: per workgroup tile of the grouped kernel, the distinct rows among its slots."""
+        gr = int(getattr(self.model.ops, "attn_group_rows", 4))
+        self.stats["prefix_streams"] += sum(len({r for r in self._slot_row[t:t + gr] if r >= 0}) for t in range(0, self.n_slots, gr))
 
     def _allocate_history(self, n_tokens: int) -> None:
         """Device-resident record of every slot's current job: tokens [S, L] and the f32 logits that produced them [S, L, V]."""
@@ -164,8 +261,7 @@ class DecodePool:
 
     def _step_sample_eager(self) -> None:
         self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
-        self.pos.add_(1)                                              # (idle slots drift harmlessly; fill() resets them)
-        self.pos.clamp_(max=self.capacity - 1)
+        self._advance()
 
     def _step_sampled(self) -> None:
         """One token for every active slot, nothing returned to the host: ids, counters and history advance on the device."""
@@ -213,7 +309,10 @@ class DecodePool:
                 raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
         if streams is not None and (not self.device_sampler or len(streams) != len(prompts) * int(n_sample_per_prompt)):
             raise ValueError("streams: one id per output, and only with the device sampler")
-        self._allocate(max(e.shape[1] for e in encoded) + n_tokens)
+        if self.share_prompt_kv:
+            self._allocate_shared(max(e.shape[1] for e in encoded), n_tokens, int(n_sample_per_prompt))
+        else:
+            self._allocate(max(e.shape[1] for e in encoded) + n_tokens)
         if self.device_sampler:
             self._allocate_history(n_tokens)
         # job = (output index, prompt index); the copies of one prompt are adjacent so that they share a prefill
@@ -232,7 +331,10 @@ class DecodePool:
                 cached_prefill[pi] = self._prefill(encoded[pi])
             last_logits, tmp = cached_prefill[pi]
             P = encoded[pi].shape[1]
-            self._install(slot, tmp, P)
+            if self.share_prompt_kv:
+                self._install_shared(slot, pi, tmp, P)
+            else:
+                self._install(slot, tmp, P)
             if self.device_sampler:
                 # the job's settings and its own random stream (its output index); the first token is draw 0 of that stream,
                 # taken by the same kernel from the prefill's last logits
@@ -258,6 +360,8 @@ class DecodePool:
             """Finished slots: their history rows leave the device (the only read-back of the device sampler), the slots go idle."""
             idx = torch.tensor(slots, dtype=torch.int64, device=dev)
             self.s_active[idx] = False
+            if self.share_prompt_kv:
+                self._release_shared(slots)
             ids_cpu, lg_cpu = self.hist_ids[idx, :n_tokens].cpu(), self.hist_logits[idx, :n_tokens].cpu()
             for r, s in enumerate(slots):
                 out_ids[slot_job[s]], out_logits[slot_job[s]] = ids_cpu[r], lg_cpu[r]
@@ -271,11 +375,15 @@ class DecodePool:
                     if n_tokens == 1:
                         if self.device_sampler:
                             fetch([s])
+                        elif self.share_prompt_kv:
+                            self._release_shared([s])
                         slot_job[s] = None
                         done += 1
             active = [s for s in range(S) if slot_job[s] is not None]
             if not active:
                 continue
+            if self.share_prompt_kv:
+                self._count_prefix_streams()
             if self.device_sampler:
                 self._step_sampled()
                 for s in active:
@@ -290,8 +398,8 @@ class DecodePool:
             nxt = sample(logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
             lg_cpu, nxt_cpu = logits.cpu(), nxt.cpu()
             self.ids[:, 0] = nxt
-            self.pos += 1                                             # (idle slots drift harmlessly; fill() resets them)
-            self.pos.clamp_(max=self.capacity - 1)
+            self._advance()
+            ended = []
             for s in active:
                 j, k = slot_job[s], slot_n[s]
                 out_ids[j, k] = nxt_cpu[s]
@@ -300,7 +408,10 @@ class DecodePool:
                 self.stats["tokens"] += 1
                 if k + 1 == n_tokens:
                     slot_job[s] = None
+                    ended.append(s)
                     done += 1
+            if ended and self.share_prompt_kv:
+                self._release_shared(ended)
 
         self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
         seqs = list(tok.detokenize_batch(out_ids))
@@ -312,12 +423,13 @@ class DecodePool:
 
 def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, temp: float = 0.7, top_k: int = 4,
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
-                device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None):
+                device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
-    (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device."""
+    (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
+    samples of a prompt read one stored copy of its K/V."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
-                      allowed_tokens=allowed_tokens)
+                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv)
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos)
     return [prompts[i] for i in owner], seqs, scores

@@ -16,6 +16,18 @@ class SharedPrefix:
 
 
 @dataclass
+class PromptStore:
+    """Keys / values of the PROMPTS a decode pool samples from, one stored copy per live prompt (evo_amd.pool.DecodePool with
+    share_prompt_kv): kv[layer] = [R, P_cap, 2, H, hd]; row [S]: the store row slot s continues (-1: none); length [R]: the keys a
+    store row holds; own_pos [S]: the index of the slot's current token in its OWN cache (its absolute position minus the prompt's
+    length).  All three vectors are device int64, so a captured step replays unchanged while slots are re-filled."""
+    kv: dict = field(default_factory=dict)
+    row: Optional[Tensor] = None
+    length: Optional[Tensor] = None
+    own_pos: Optional[Tensor] = None
+
+
+@dataclass
 class InferenceParams:
     """Attention layers: key_value_memory_dict[layer] = [B_max, max_seqlen, 2, H, hd] bf16."""
     max_seqlen: int
@@ -27,6 +39,9 @@ class InferenceParams:
     # set: the rows continue the first `seqlen_offset` tokens of a shared reference -- attention reads that prefix from shared_prefix.kv and
     # no per-row KV buffer is allocated or written (StripedHyena._attn_block)
     shared_prefix: Optional[SharedPrefix] = None
+    # set (with pos_tensor, single-token steps): key_value_memory_dict holds only the tokens each row GENERATED; the prompt it continues is
+    # read from prompt_store (StripedHyena._attn_block)
+    prompt_store: Optional[PromptStore] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen

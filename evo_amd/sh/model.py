@@ -709,14 +709,28 @@ class StripedHyena(nn.Module):
             # device memory.  The rotary kernel indexes its table by token, so the B rows are presented as one
             # sequence of B tokens with the per-row table.
             kv = cache.key_value_memory_dict[i][:B]
-            if hasattr(ops, "rope_append_decode") and pos.numel() == B:
-                # rotary at each row's position + the KV append in one launch (no per-step cos / sin table)
-                ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, **rk)
+            store = getattr(cache, "prompt_store", None)
+            if store is not None:
+                # the rows continue prompts held ONCE in a store (DecodePool share_prompt_kv): rotary at the absolute position, the append
+                # at the row's own index, attention over the store row's keys and then the row's own
+                if hasattr(ops, "rope_append_decode") and pos.numel() == B:
+                    ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, widx=store.own_pos, **rk)
+                else:
+                    cos, sin = getattr(cache, "_rot_dyn", None) or self._rotary_dyn(pos)
+                    ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, **rk)
+                    kv[self._row_index(B, x2d.device), store.own_pos] = qkv[:, 0, 1:3]
+                skv = store.kv[i]
+                a = ops.attention_decode_prefix(q, kv[:, :, 0], kv[:, :, 1], store.own_pos, skv[:, :, 0], skv[:, :, 1], store.row,
+                                                store.length, **ak).view(B, D)
             else:
-                cos, sin = getattr(cache, "_rot_dyn", None) or self._rotary_dyn(pos)
-                ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, **rk)
-                kv[self._row_index(B, x2d.device), pos] = qkv[:, 0, 1:3]
-            a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, **ak).view(B, D)
+                if hasattr(ops, "rope_append_decode") and pos.numel() == B:
+                    # rotary at each row's position + the KV append in one launch (no per-step cos / sin table)
+                    ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, **rk)
+                else:
+                    cos, sin = getattr(cache, "_rot_dyn", None) or self._rotary_dyn(pos)
+                    ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, **rk)
+                    kv[self._row_index(B, x2d.device), pos] = qkv[:, 0, 1:3]
+                a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, **ak).view(B, D)
         else:
             cos, sin = self._rotary(off, T, x2d.device)
             ops.rope_(qkv, cos, sin, **rk)

@@ -66,8 +66,11 @@ extern "C" {
  *  12: evo_sample_rows_f32 added (seeded sampling on the device); no signature changed.
  *  13: evo_unembed_profile_bf16 added (the fused scoring tail with the log-probs of up to 8 chosen vocabulary ids per row); no signature changed.
  *  14: evo_attn_fwd_prefix_bf16 and evo_attn_prefix_vt_bf16 added (causal attention whose keys are ONE prefix shared by every batch row plus
- *      each row's own suffix: variant scoring from a cached reference); no signature changed. */
-#define EVO_ABI_VERSION 14
+ *      each row's own suffix: variant scoring from a cached reference); no signature changed.
+ *  15: evo_attn_decode_prefix_bf16 (decode attention of rows that continue SHARED stored prompts: the copies of a prompt in a decode pool
+ *      read one K/V of it) and evo_rope_append_decode_at_bf16 (the decode rotary + append with the cache row given apart from the
+ *      position) added; no signature changed. */
+#define EVO_ABI_VERSION 15
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -215,6 +218,12 @@ int evo_rope_qk_bf16(void* qkv, const float* cos_t, const float* sin_t,
 int evo_rope_append_decode_bf16(void* qkv, void* kv, const int64_t* pos, const float* inv_freq, float scaling,
                                 int64_t B, int64_t H, int64_t hd, int64_t kv_sb, int64_t kv_st, int64_t kv_sw, int64_t kv_sh,
                                 float q_scale, void* stream);
+/* the same (ABI 15) with the cache row given apart from the position: the angle comes from pos[b] (absolute), the row is written at
+ * token widx[b] of the cache (device int64 [B], < cap) -- a slot whose own cache starts behind a prompt stored elsewhere
+ * (evo_attn_decode_prefix_bf16).  widx == pos is evo_rope_append_decode_bf16 bit for bit (one kernel serves both). */
+int evo_rope_append_decode_at_bf16(void* qkv, void* kv, const int64_t* pos, const float* inv_freq, float scaling,
+                                   int64_t B, int64_t H, int64_t hd, int64_t kv_sb, int64_t kv_st, int64_t kv_sw, int64_t kv_sh,
+                                   float q_scale, const int64_t* widx, void* stream);
 
 /* ---- causal multi-head attention forward ------------------------------------------------------------
  * replaces flash_attn_2_cuda fwd / flash_attn_with_kvcache  [REF README.md:47-50; evo/configs/evo-1-8k-base_inference.yml:9,30]
@@ -285,6 +294,40 @@ int evo_attn_decode_bf16(const void* q, const void* k, const void* v, void* o,
                          int64_t v_sb, int64_t v_st, int64_t v_sh,
                          const int64_t* dyn_pos, float* part_o, float* part_ml, int64_t n_splits,
                          float softmax_scale, void* stream);
+
+/* decode behind SHARED prompts (ABI 15): row b attends to the keys [0, pre_len[pre_row[b]]) of row pre_row[b] of a prompt store and
+ * then to its OWN keys [0, own_pos[b]] -- what evo_attn_decode_bf16 returns on the concatenation, without a copy of the prompt per
+ * row (a decode pool that draws many samples from few prompts; no counterpart in the reference).
+ *   q, k, v, o, B, H, Tk, strides: as above, k / v the rows' own caches (Tk their capacity); own_pos [B] device int64.
+ *   k_pre / v_pre: views [R, P_cap, H, 128] of the store with element strides (row, token, head); pre_row [B] device int64: the store
+ *   row a batch row continues, or -1 (none); pre_len [R] device int64: the keys each store row holds (>= 1 where referenced; values
+ *   beyond P_cap are read as P_cap, rows >= R as -1).  Everything per row or per prompt is device memory: a captured step replays
+ *   unchanged while slots are re-filled.
+ *   part_o [B, H, n_pre_splits + n_splits, 128] f32, part_ml [.., 2] f32: splits [0, n_pre_splits) are the prefix -- split s takes the
+ *   64-key blocks s, s + n_pre_splits, ... of the store row; a row without a prefix (or a split without a block) holds (m, l) =
+ *   (-inf, 0) and zeros -- the remaining n_splits the own keys, partitioned as attn_decode_stream_kernel partitions them (it is that
+ *   kernel, writing behind the prefix's splits).  One combine launch merges them all.
+ *   Prefix kernel (attn_decode_group_kernel): a workgroup serves EVO_ATTN_GROUP_ROWS consecutive batch rows, a wave one split; for
+ *   every DISTINCT store row among the tile's rows the wave streams that row's blocks once and updates the rows that name it.  Rows
+ *   of one prompt placed next to each other read it once per tile; any other arrangement is as correct and reads more.
+ *   Refused (-1, no launch): null pointers; R < 1; n_pre_splits < 1; n_splits < 1; n_pre_splits + n_splits > 1024; a stride that is
+ *   not a multiple of 8; P_cap * kp_st * 2, P_cap * vp_st * 2, Tk * k_st * 2 or Tk * v_st * 2 at or above 2^32 - 1 (both kernels
+ *   address keys with 32-bit offsets; this entry has no MFMA form to fall back on). */
+#ifndef EVO_ATTN_GROUP_ROWS
+#define EVO_ATTN_GROUP_ROWS 8
+#endif
+int evo_attn_decode_prefix_bf16(const void* q, const void* k, const void* v, void* o,
+                                int64_t B, int64_t H, int64_t Tk,
+                                int64_t q_sb, int64_t q_sh,
+                                int64_t k_sb, int64_t k_st, int64_t k_sh,
+                                int64_t v_sb, int64_t v_st, int64_t v_sh,
+                                const int64_t* own_pos,
+                                const void* k_pre, const void* v_pre, int64_t R, int64_t P_cap,
+                                int64_t kp_sb, int64_t kp_st, int64_t kp_sh,
+                                int64_t vp_sb, int64_t vp_st, int64_t vp_sh,
+                                const int64_t* pre_row, const int64_t* pre_len,
+                                float* part_o, float* part_ml, int64_t n_pre_splits, int64_t n_splits,
+                                float softmax_scale, void* stream);
 
 /* ---- skinny dense layer (decode) ----------------------------------------------------------------------
  * replaces cuBLAS GEMV-shaped nn.Linear calls of the single-token forward   [REF evo/generation.py:151-155]

@@ -41,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="reproducible run (for a fixed --n-slots): every sample draws from its own "
                                                            "random stream; the sampler then runs on the device")
     ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
+    ap.add_argument("--share-prompt-kv", action="store_true", help="the samples of a prompt read ONE stored copy of its K/V instead of a "
+                                                                   "private copy per decode stream (long prompts, many samples)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -52,7 +54,8 @@ def main(argv=None):
         raise SystemExit(f"no prompts in {args.prompts}")
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
-                      temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens)
+                      temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
+                      share_prompt_kv=args.share_prompt_kv)
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
                                         prepend_bos=args.prepend_bos)
     rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] for s, sc, o in zip(seqs, scores, owner)
