@@ -82,6 +82,9 @@ class Generator:
 
         prefilled = False
         if inference_params_dict is not None:
+            if any(getattr(c, "lengths", None) is not None for c in inference_params_dict.values()):
+                raise ValueError("Generator cannot continue a ragged prefill (StripedHyena.prefill_ragged): its rows end at different positions "
+                                 "and the scalar seqlen_offset of this loop describes one; decode such a cache per row (DecodePool)")
             cached_generation = True
             prefilled = True
             self._rehome_cache(inference_params_dict, x.device)

@@ -63,13 +63,17 @@ _SIGNATURES = {
     "evo_pool_rows_bf16": ([_PTR, _I64, _I64, _I64, _PTR, _I64, _PTR, _F32, _I64, _I64, _PTR, _PTR, _PTR], _c.c_int),
     "evo_attn_decode_prefix_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64] * 8 + [_PTR] * 4 + [_I64, _I64, _F32, _PTR], _c.c_int),
     "evo_rope_append_decode_at_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR, _PTR], _c.c_int),
+    "evo_hyena_state_at_zt": ([_PTR] * 8 + [_I64] * 8 + [_PTR], _c.c_int),
     "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 15        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 16        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
                         # `prefix_streams` counter is computed from it on the host)
+
+
+HYENA_RAGGED_SEG = 256  # must equal EVO_HYENA_RAGGED_SEG there: steps per time segment of evo_hyena_state_at_zt (csrc/hyena_ragged.hip)
 
 
 class EvoLibraryError(RuntimeError):
@@ -590,6 +594,44 @@ class HipOps:
             return torch.view_as_complex(s_fin)
         self.last_hyena_io = {"mfma": B * T_run * 3 * D * 2 + B * T_run * D * 2}
         return (y, torch.view_as_complex(s_fin)) if want_state else y
+
+    def hyena_state_at_zt(self, zt, B, T, lens, fir_w, fir_b, poles, n_heads):
+        """Ragged batch (csrc/hyena_ragged.hip: evo_hyena_state_at_zt): the modal state after token lens[b] - 1 of every batch row, from a
+        zero start, and the two steps of FIR history there -- what a cached prefill of row b ALONE would hand to decode.  zt [blocks, 3 D,
+        256] bf16 in the plain form of zt_layout(B, T); lens [B] int64 (a device tensor is never read by the host; values outside [1, T]
+        are clamped).  -> (state complex64 [B, D, 8], fir bf16 [B, 3 D, 2]).  Positions at and behind lens[b] may hold anything."""
+        self._need(zt, torch.bfloat16, "hyena z^T")
+        assert zt.dim() == 3 and zt.shape[2] == 256
+        D3, P = zt.shape[1], zt.shape[0] * 256
+        D = D3 // 3
+        _, Tp, Mp, r = self.zt_layout(B, T)
+        if r or P != Mp or D3 != 3 * D:
+            raise RuntimeError("hyena_state_at_zt: z^T must be the plain form of zt_layout (no tail block)")
+        for t, nm in ((fir_w, "fir_w"), (fir_b, "fir_b")):
+            self._need(t, torch.bfloat16, "hyena " + nm)
+        self._need(poles, torch.float32, "hyena poles")
+        assert tuple(poles.shape) == (D, 8, 2)
+        lens = torch.as_tensor(lens, dtype=torch.int64).to(zt.device).contiguous()
+        assert tuple(lens.shape) == (B,)
+        state = torch.empty(B, D, 8, 2, dtype=torch.float32, device=zt.device)
+        fir = torch.empty(B, D3, 2, dtype=torch.bfloat16, device=zt.device)
+        args = (zt.data_ptr(), lens.data_ptr(), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(), state.data_ptr(), fir.data_ptr())
+        need = self.lib.evo_hyena_state_at_zt(*args, None, 0, B, T, D, n_heads, P, Tp, 0, None)
+        if need < 0:
+            raise RuntimeError(f"evo_hyena_state_at_zt refused B = {B}, T = {T}, D = {D}, heads = {n_heads}")
+        ws = torch.empty(need // 4, dtype=torch.float32, device=zt.device)
+        self._launch("hyena_state_at", "evo_hyena_state_at_zt", *args, ws.data_ptr(), need, B, T, D, n_heads, P, Tp, 0)
+        return torch.view_as_complex(state), fir
+
+    def hyena_state_at(self, z, lens, fir_w, fir_b, poles, n_heads):
+        """The same from TOKEN-major z [B, T, 3 D] (the modal routing: layers the table guard refuses, shapes zt_shape_ok refuses): z is laid
+        out channel-major (a copy -- a rare path) with T rounded up to a whole number of 64 positions, and goes through the same kernel."""
+        B, T, D3 = z.shape
+        Tw = (T + self.ZT_ALIGN - 1) // self.ZT_ALIGN * self.ZT_ALIGN
+        if Tw != T:
+            z = torch.nn.functional.pad(z, (0, 0, 0, Tw - T))
+        lens = torch.as_tensor(lens, dtype=torch.int64).to(z.device).clamp(1, T)
+        return self.hyena_state_at_zt(self.zt_from_rows(z, B, Tw), B, Tw, lens, fir_w, fir_b, poles, n_heads)
 
     def hyena_prefill(self, z: torch.Tensor, fir_w: torch.Tensor, fir_b: torch.Tensor, poles: torch.Tensor,
                       residues: torch.Tensor, dskip: torch.Tensor, n_heads: int,

@@ -10,7 +10,7 @@ attention all read per-row positions (`evo_attn_decode_bf16` dyn_pos[B]), so str
 and different ages advance together, a finished stream's slot is re-filled while the others keep going, and the
 step has one shape for the whole job -- it is captured once in a hipGraph and replayed.
 
-Prompts are prefilled one at a time with the ordinary parallel forward (the long-convolution kernel ends with the
+Prompts are prefilled one at a time (by default; `prefill_batch` > 1 below) with the ordinary parallel forward (the long-convolution kernel ends with the
 exact modal state); the `n_sample_per_prompt` copies of a prompt share ONE prefill, whose caches are replicated
 into their slots.  Sampling and scoring follow the reference wrapper verbatim (same `sample`, same shifted
 logits/token pairing [REF evo/generation.py:162-167,287]), so with greedy sampling a pool run reproduces per-prompt
@@ -26,6 +26,10 @@ it was admitted at, or on the other prompts of the job -- for a fixed `n_slots` 
 K/V is installed ONCE into a row of a `PromptStore`; a slot's own cache holds only the `n_tokens` it generates, and the decode
 attention reads the store row and then the slot's own keys (`HipOps.attention_decode_prefix`).  Which store row a slot continues, how
 many keys that row holds and the slot's own index are device vectors, so the captured step still replays while slots are re-filled.
+
+`prefill_batch=N` > 1 (opt-in): when a prompt needs a prefill, the distinct prompts among the jobs the idle slots are
+about to take -- at most N, and at most `prefill_max_tokens` padded positions -- are prefilled in ONE forward of the right-padded batch
+(`StripedHyena.prefill_ragged`); each slot is installed from its prompt's row of that batch.  With the default 1 nothing changes by a bit.
 """
 from __future__ import annotations
 
@@ -43,8 +47,14 @@ from .sh.sample import allowed_mask, sample
 class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
-                 seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False):
+                 seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
+                 prefill_max_tokens: int = 32768):
         self.model = model
+        self.prefill_batch, self.prefill_max_tokens = int(prefill_batch), int(prefill_max_tokens)
+        if self.prefill_batch < 1:
+            raise ValueError("prefill_batch must be >= 1")
+        if self.prefill_batch > 1 and not hasattr(model, "prefill_ragged"):
+            raise RuntimeError("prefill_batch > 1 needs a model with prefill_ragged (one forward over prompts of unequal length)")
         self.share_prompt_kv = bool(share_prompt_kv)
         if self.share_prompt_kv and not hasattr(getattr(model, "ops", None), "attention_decode_prefix"):
             raise RuntimeError("share_prompt_kv=True needs a compute backend with attention_decode_prefix (the decode attention over a "
@@ -61,6 +71,8 @@ class DecodePool:
         self.stats = {"steps": 0, "prefills": 0, "tokens": 0}
         if self.share_prompt_kv:
             self.stats.update({"prompt_kv_installs": 0, "store_rows": 0, "prefix_streams": 0})
+        if self.prefill_batch > 1:                                   # (prefills then counts forwards)
+            self.stats.update({"prefill_prompts": 0, "prefill_pad_tokens": 0})
         self.store = None
         self.store_refs: List[int] = []                              # host: live copies per store row
         self._store_prompt: List[Optional[int]] = []                 # host: the prompt a store row holds (kept after its last copy finished)
@@ -150,15 +162,16 @@ class DecodePool:
         if self.device_sampler:
             self._allocate_sampler_state()
 
-    def _install_shared(self, slot: int, pi: int, tmp: dict, P: int) -> None:
-        """Slot `slot` continues prompt `pi`: its K/V goes into a store row unless one holds it already; the Hyena states stay per slot."""
+    def _install_shared(self, slot: int, pi: int, tmp: dict, P: int, row: int = 0) -> None:
+        """Slot `slot` continues prompt `pi` (row `row` of the prefill's caches): its K/V goes into a store row unless one holds it already;
+        the Hyena states stay per slot."""
         m, st = self.model, self.store
         if pi in self._store_prompt:
             r = self._store_prompt.index(pi)
         else:
             r = self.store_refs.index(0)                             # (exists: see _allocate_shared)
             for i in m.attn_layer_idxs:
-                st.kv[i][r, :P] = tmp["mha"].key_value_memory_dict[i][0, :P]
+                st.kv[i][r, :P] = tmp["mha"].key_value_memory_dict[i][row, :P]
             st.length[r] = P
             self._store_prompt[r] = pi
             self.stats["prompt_kv_installs"] += 1
@@ -167,8 +180,8 @@ class DecodePool:
         st.row[slot] = r
         st.own_pos[slot] = 0
         for i in m.hyena_layer_idxs:
-            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][0]
-            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][0].reshape(
+            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
+            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
                 self.ipd["hyena"].state_dict[i][slot].shape)
 
     def _release_shared(self, slots: Sequence[int]) -> None:
@@ -212,13 +225,46 @@ class DecodePool:
         self.stats["prefills"] += 1
         return logits[0, -1].float(), tmp
 
-    def _install(self, slot: int, tmp: dict, P: int) -> None:
+    # ------------------------------------------------------------------ prompts admitted together share one prefill (opt-in)
+    PREFILL_PAD = 64                                                   # StripedHyena.prefill_ragged's pad_to
+
+    def _prefill_group(self, window: Sequence[int], lengths: Sequence[int]) -> List[int]:
+        """The admission rule of `prefill_batch` > 1.  `window`: the prompt index of every job the currently idle slots will take, in job
+        order (the first one is the prompt that needs a prefill now).  Taken: the distinct prompts in that order, at most `prefill_batch`,
+        stopping before (prompts) x (longest length, rounded up to PREFILL_PAD) exceeds `prefill_max_tokens`.  A single prompt -- nothing
+        to share with, or alone beyond the cap -- is returned alone: it goes through the B = 1 prefill unchanged."""
+        group: List[int] = []
+        t_max = 0
+        for pi in window:
+            if pi in group:
+                continue
+            if len(group) == self.prefill_batch:
+                break
+            t = max(t_max, -(-int(lengths[pi]) // self.PREFILL_PAD) * self.PREFILL_PAD)
+            if group and (len(group) + 1) * t > self.prefill_max_tokens:
+                break
+            group.append(pi)
+            t_max = t
+        return group
+
+    def _prefill_ragged(self, encoded: Sequence[torch.Tensor], group: Sequence[int]):
+        """The prompts `group` in ONE forward -> (last-position logits [B, V] f32, the caches of the padded batch: row b = group[b])."""
+        lens = [int(encoded[pi].shape[1]) for pi in group]
+        T = max(lens)
+        ids = torch.stack([torch.cat([encoded[pi][0], encoded[pi][0, -1:].expand(T - n)]) for pi, n in zip(group, lens)])
+        with torch.inference_mode():
+            logits, tmp = self.model.prefill_ragged(ids, lens, pad_to=self.PREFILL_PAD)
+        self.stats["prefills"] += 1
+        self.stats["prefill_pad_tokens"] += len(group) * (-(-T // self.PREFILL_PAD) * self.PREFILL_PAD) - sum(lens)
+        return logits.float(), tmp
+
+    def _install(self, slot: int, tmp: dict, P: int, row: int = 0) -> None:
         m = self.model
         for i in m.attn_layer_idxs:
-            self.ipd["mha"].key_value_memory_dict[i][slot, :P] = tmp["mha"].key_value_memory_dict[i][0, :P]
+            self.ipd["mha"].key_value_memory_dict[i][slot, :P] = tmp["mha"].key_value_memory_dict[i][row, :P]
         for i in m.hyena_layer_idxs:
-            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][0]
-            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][0].reshape(
+            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
+            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
                 self.ipd["hyena"].state_dict[i][slot].shape)
 
     # ------------------------------------------------------------------ one token for every slot
@@ -327,14 +373,27 @@ class DecodePool:
         def fill(slot: int) -> None:
             j, pi = jobs.popleft()
             if pi not in cached_prefill:
-                cached_prefill.clear()                               # keep one prompt's caches alive at a time
-                cached_prefill[pi] = self._prefill(encoded[pi])
-            last_logits, tmp = cached_prefill[pi]
+                cached_prefill.clear()                               # keep one prefill's caches alive at a time (every earlier prompt's copies are installed)
+                group = [pi]
+                if self.prefill_batch > 1:
+                    # the jobs the idle slots (this one included) will take: copies of a prompt are adjacent, so none of them has a prefill yet
+                    n_idle = sum(1 for q in slot_job if q is None)
+                    group = self._prefill_group([pi] + [jobs[k][1] for k in range(min(n_idle - 1, len(jobs)))],
+                                                [e.shape[1] for e in encoded])
+                    self.stats["prefill_prompts"] += len(group)
+                if len(group) == 1:
+                    cached_prefill[pi] = self._prefill(encoded[pi]) + (0,)
+                else:
+                    lg, tmp_b = self._prefill_ragged(encoded, group)
+                    for r, q in enumerate(group):
+                        cached_prefill[q] = (lg[r], tmp_b, r)
+            last_logits, tmp, row = cached_prefill[pi]
             P = encoded[pi].shape[1]
+            kw = {"row": row} if row else {}                         # (row 0 of a B = 1 prefill: the call as it always was)
             if self.share_prompt_kv:
-                self._install_shared(slot, pi, tmp, P)
+                self._install_shared(slot, pi, tmp, P, **kw)
             else:
-                self._install(slot, tmp, P)
+                self._install(slot, tmp, P, **kw)
             if self.device_sampler:
                 # the job's settings and its own random stream (its output index); the first token is draw 0 of that stream,
                 # taken by the same kernel from the prefill's last logits
@@ -423,13 +482,15 @@ class DecodePool:
 
 def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, temp: float = 0.7, top_k: int = 4,
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
-                device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False):
+                device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
+                prefill_batch: int = 1):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
-    samples of a prompt read one stored copy of its K/V."""
+    samples of a prompt read one stored copy of its K/V.  `prefill_batch` > 1: up to that many prompts admitted
+    together are prefilled in one forward, right-padded."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
-                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv)
+                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch)
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos)
     return [prompts[i] for i in owner], seqs, scores

@@ -42,6 +42,9 @@ class InferenceParams:
     # set (with pos_tensor, single-token steps): key_value_memory_dict holds only the tokens each row GENERATED; the prompt it continues is
     # read from prompt_store (StripedHyena._attn_block)
     prompt_store: Optional[PromptStore] = None
+    # set by StripedHyena.prefill_ragged: device int64 [B], the tokens of every row of a right-padded batch that are real.  KV rows behind
+    # lengths[b] hold pad keys (a per-row-position decode overwrites them as it appends); a scalar seqlen_offset cannot describe such a cache
+    lengths: Optional[Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen
@@ -61,6 +64,8 @@ class RecurrentInferenceParams:
     fir_state_dict: dict = field(default_factory=dict)
     state_dict: dict = field(default_factory=dict)
     max_batch_size: int = 1
+    # ragged prefill (see InferenceParams.lengths): the states are those after token lengths[b] - 1 of row b
+    lengths: Optional[Tensor] = None
 
     def reset(self):
         self.fir_filter_length = 3

@@ -577,6 +577,9 @@ class StripedHyena(nn.Module):
         f = blk.filter
         have_state = cache is not None and i in cache.fir_state_dict
         K1 = self.short_filter_length - 1
+        lens = getattr(cache, "lengths", None) if cache is not None and T > 1 else None     # set by prefill_ragged: per-row end states
+        if lens is not None and (have_state or mask is not None):
+            raise ValueError("a ragged prefill (lengths) starts at t = 0 without a padding mask: no resumed prefill, no mask")
         if have_state and T == 1:                 # decode: norm + projections + FIR/modal step + gate in one launch
             y = ops.hyena_decode_fused(x2d, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias,
                                        cache.fir_state_dict[i], cache.state_dict[i], f._fir_w, f.short_filter_bias,
@@ -618,6 +621,10 @@ class StripedHyena(nn.Module):
                 yb[ix["yblk"], :, ix["yrow"], :] = y_tail.view(B, D // 16, 16)          # rows b T + Tm of the blocked y
             elif cache is None:
                 y = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, y_blk=yb)
+            elif lens is not None:
+                # ragged batch: y everywhere as usual; state and FIR history at every row's OWN last token (csrc/hyena_ragged.hip)
+                y = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, y_blk=yb)
+                cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at_zt(zt, B, T, lens, f._fir_w, f.short_filter_bias, f._poles, H)
             else:
                 halo = s0 = None
                 if have_state:              # continue a cached prefix with more than one token
@@ -642,9 +649,11 @@ class StripedHyena(nn.Module):
                 s0 = cache.state_dict[i]
             kw = {} if mask is None else {"mask": mask[1]}
             y3, state = ops.hyena_prefill(z3, f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, H,
-                                          z_halo=halo, s0=s0, want_state=cache is not None, **kw)
+                                          z_halo=halo, s0=s0, want_state=cache is not None and lens is None, **kw)
             y = y3.view(B * T, D)
-            if cache is not None:
+            if lens is not None:
+                cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at(z3, lens, f._fir_w, f.short_filter_bias, f._poles, H)
+            elif cache is not None:
                 tail = z3[:, -K1:, :]
                 if halo is not None and T < K1:
                     tail = torch.cat([halo[:, T:], tail], dim=1)
@@ -698,6 +707,9 @@ class StripedHyena(nn.Module):
             qkv = ops.norm_linear(x2d, blk.pre_norm.scale, self.eps, mha.Wqkv.weight, mha.Wqkv.bias, mfma=True).view(B, T, 3, H, hd)
         off = int(cache.seqlen_offset) if cache is not None else 0
         pos = getattr(cache, "pos_tensor", None) if cache is not None else None
+        if T > 1 and cache is not None and getattr(cache, "lengths", None) is not None \
+                and (off != 0 or mask is not None or getattr(cache, "shared_prefix", None) is not None):
+            raise ValueError("a ragged prefill (lengths) starts at t = 0 with keys of its own: no resumed prefill, no mask, no shared_prefix")
         q = qkv[:, :, 0]
         # round 6: the rotary kernel folds softmax_scale * log2(e) into its one rounding of q and the attention kernels take scores as
         # exponents (ops.attn_prescale; csrc/attn_w64.hip PRE: no per-score multiply) -- q is never cached, so K / V and the KV cache are untouched
@@ -945,6 +957,43 @@ class StripedHyena(nn.Module):
                 return logits, inference_params_dict
         h = self.hidden_states(x, inference_params_dict)
         return self._unembed_output(h, B, T), inference_params_dict
+
+    @torch.no_grad()
+    def prefill_ragged(self, ids: torch.Tensor, lengths, pad_to: int = 64, inference_params_dict=None, padding_mask=None):
+        """Cached prefill of B prompts of UNEQUAL length in one forward: ids [B, T] right-padded with any valid token id, lengths [B] (host
+        list or tensor, 1 <= L_b <= T) -> (last_logits [B, V] f32: the logits at every row's own last token, inference_params_dict).
+
+        The padded batch runs through the ordinary cached-prefill forward once, its width rounded up to a multiple of `pad_to` (the columns
+        added are filled with the row's last real token).  Every dense, norm and MLP launch is row-independent, attention and the Hyena
+        operator are causal, and a pad is an ordinary token, so every activation is finite and positions t < L_b of row b are what a
+        prefill of row b alone computes.  What the operator's one-T end state cannot give -- the modal state and FIR
+        history at L_b - 1 -- comes from HipOps.hyena_state_at_zt.  The cache holds KV [B, T_pad, 2, H, hd] (rows >= L_b are pad keys: a
+        decode that appends at its own position overwrites them), per-row FIR / modal states and `lengths` (device int64 [B]) on both
+        records.  It is meant for per-row-position decode (`pos_tensor`, DecodePool); Generator's scalar seqlen_offset cannot describe it.
+        A padding mask or an existing cache raises ValueError: a ragged batch starts at t = 0."""
+        if padding_mask is not None or inference_params_dict is not None:
+            raise ValueError("prefill_ragged: no padding_mask and no existing cache (a ragged batch starts at t = 0; pads are ordinary tokens)")
+        if ids.dim() != 2:
+            raise ValueError("input_ids must be [batch, length]")
+        B, T = ids.shape
+        lens = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if len(lens) != B or any(n < 1 or n > T for n in lens):
+            raise ValueError(f"prefill_ragged: one length per row with 1 <= L_b <= T = {T}, got {lens}")
+        pad_to = max(1, int(pad_to))
+        Tw = (T + pad_to - 1) // pad_to * pad_to
+        dev = self.device
+        ids = ids.to(dev)
+        lens_d = torch.tensor(lens, dtype=torch.int64, device=dev)
+        if Tw != T:
+            ids = torch.cat([ids, ids.gather(1, (lens_d - 1)[:, None]).expand(B, Tw - T)], dim=1)
+        ipd = self.initialize_inference_params()
+        ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = B
+        ipd["mha"].max_seqlen = Tw
+        ipd["mha"].lengths = ipd["hyena"].lengths = lens_d
+        h = self.hidden_states(ids.contiguous(), ipd)                                         # [B Tw, D]
+        last = h.index_select(0, torch.arange(B, device=dev) * Tw + lens_d - 1).contiguous()   # only the B rows that are read
+        logits = self.ops.linear(last, self.unembed.weight, None).view(B, self.vocab_size)
+        return logits.float(), ipd
 
     @property
     def has_own_unembed(self) -> bool:

@@ -69,8 +69,10 @@ extern "C" {
  *      each row's own suffix: variant scoring from a cached reference); no signature changed.
  *  15: evo_attn_decode_prefix_bf16 (decode attention of rows that continue SHARED stored prompts: the copies of a prompt in a decode pool
  *      read one K/V of it) and evo_rope_append_decode_at_bf16 (the decode rotary + append with the cache row given apart from the
- *      position) added; no signature changed. */
-#define EVO_ABI_VERSION 15
+ *      position) added; no signature changed.
+ *  16: evo_hyena_state_at_zt added (the Hyena end state and FIR history at every row's OWN last token: ragged batched prefill); no
+ *      signature changed. */
+#define EVO_ABI_VERSION 16
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -169,6 +171,28 @@ int evo_hyena_ct(const void* zt, const void* z_halo, const void* fir_w, const vo
                  const float* s0, float* s_out, const float* poles, int64_t B, int64_t T, int64_t D, int64_t n_heads,
                  int64_t zt_pitch, int64_t row_pitch, int64_t zt_row0, int64_t tail_T, int64_t tail_pos0, int64_t state_only,
                  int64_t y_blocked_rows, int64_t y_row0, int64_t y_row_pitch, void* stream);
+
+/* ---- Hyena end state of a ragged batch: the state and FIR history at every row's OWN last token ----------------------------
+ * what a cached prefill hands to decode (`s_out` of evo_hyena_ct, the last two rows of z), per row    [REF evo/generation.py:111-117,152]
+ * for a batch of right-padded prompts of unequal length run through ONE forward (csrc/hyena_ragged.hip).  The state at T cannot be
+ * rolled back to lens[b] < T (that divides by p^(T - lens[b]), |p| < 1), so it is computed from z^T directly: time is cut into
+ * segments of EVO_HYENA_RAGGED_SEG steps, a thread walks (row, segment, channel) from a zero state with the per-step fp32 arithmetic of
+ * evo_hyena_seg_state, segments wholly behind lens[b] exit at once, and a second small launch combines a row's segments with p^n in
+ * fp64 (as evo_hyena_carry_scan does).  Two launches whatever B and the lengths are; lens is read on the device only.
+ *   zt      the tensor evo_hyena_ct reads, plain form only (no tail block): batch row b, token t at position zt_row0 + b * row_pitch + t
+ *   lens    [B] int64, DEVICE memory; a value outside [1, T] is clamped into it
+ *   s_out   [B, D, 8] c64: the state after step lens[b] - 1 from a zero start (no carry-in, no halo: a ragged batch starts at t = 0)
+ *   fir_out [B, 3 D, 2] bf16: z[b, lens[b] - 2], z[b, lens[b] - 1] of every column in the reference's order, oldest first, zeros where
+ *           t < 0 -- the bits of zt, untouched
+ *   ws      workspace of ws_bytes bytes, 16-byte aligned; ws == NULL: nothing is launched and the bytes needed are returned
+ * Positions t >= lens[b] of a row and pad positions of the layout may hold anything (NaN included): nothing there reaches an output.
+ * Returns -1 before any launch unless D == n_heads * 128, T % 64 == 0 || B == 1, row_pitch % 8 == 0 (>= T for B > 1), zt_row0 % 8 == 0,
+ * zt_pitch % 256 == 0, the rows fit zt_pitch, every pointer but ws is non-null, and ws_bytes covers the need. */
+#define EVO_HYENA_RAGGED_SEG 256
+int evo_hyena_state_at_zt(const void* zt, const int64_t* lens, const void* fir_w, const void* fir_b, const float* poles,
+                          float* s_out, void* fir_out, float* ws, int64_t ws_bytes,
+                          int64_t B, int64_t T, int64_t D, int64_t n_heads,
+                          int64_t zt_pitch, int64_t row_pitch, int64_t zt_row0, void* stream);
 
 /* The Hyena block's output projection on the blocked y of evo_hyena_ct               [REF stripedhyena/model.py ParallelGatedConvBlock:
  * out_filter_dense]:  y [M, N] = x . w^T (+ bias [N]) (+ residual [M, N], may alias y), x = [M / 128][K / 16][128][16] bf16.  The persistent dense

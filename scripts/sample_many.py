@@ -43,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
     ap.add_argument("--share-prompt-kv", action="store_true", help="the samples of a prompt read ONE stored copy of its K/V instead of a "
                                                                    "private copy per decode stream (long prompts, many samples)")
+    ap.add_argument("--prefill-batch", type=int, default=1, help="prefill up to N prompts admitted together in one forward, right-padded "
+                                                                 "(default 1: every prompt alone)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -55,7 +57,7 @@ def main(argv=None):
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
                       temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
-                      share_prompt_kv=args.share_prompt_kv)
+                      share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch)
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
                                         prepend_bos=args.prepend_bos)
     rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] for s, sc, o in zip(seqs, scores, owner)
