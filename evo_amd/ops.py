@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _build
+from .backend import Backend
 
 _c = ctypes
 _PTR = _c.c_void_p
@@ -174,8 +175,8 @@ class _NoSpan:
 _NOSPAN = _NoSpan()
 
 
-class HipOps:
-    """The gfx950 op set.  All tensors must live on the same ROCm device."""
+class HipOps(Backend):
+    """The gfx950 op set (the contract: evo_amd/backend.py).  All tensors must live on the same ROCm device."""
 
     name = "hip-gfx950"
 
@@ -242,6 +243,14 @@ class HipOps:
             raise RuntimeError(f"{what}: tensor must be contiguous")
         HipOps._check_address(t.data_ptr(), what, HipOps._align_of(dtype))
 
+    @staticmethod
+    def _need_strided(op: str, dims: Optional[int] = None, **operands) -> None:
+        """The attention launches' q / k / v operands (strided views welcome): ROCm bf16, dense last dim, 16-byte aligned, `dims`-d if given."""
+        for nm, t in ((nm, t) for nm, t in operands.items() if t is not None):
+            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1 or (dims is not None and t.dim() != dims):
+                raise RuntimeError(f"{op} {nm}: need a {'' if dims is None else f'{dims}-d '}ROCm bf16 tensor with a dense last dim")
+            HipOps._check_address(t.data_ptr(), f"{op} {nm}")
+
     def _launch(self, span: str, name: str, *args) -> None:
         """One launch of entry point `name` on the current stream, under the timer span `span`."""
         with self._t(span):
@@ -251,7 +260,6 @@ class HipOps:
     TILE_ROWS = 256         # rows per tile of the persistent dense layer (csrc/gemm.hip GBM)
     SLIVER_ROWS = 16        # the most rows behind the last whole tile that count as a BOS sliver (the weight-streaming kernel's MFMA form: one m tile)
     TAIL_ROWS_FROM = 4096   # _tail_rows peels a sliver from this many rows on (below, one more row of tiles costs less than a second launch)
-    DECODE_ROWS = 8         # batches this small take the fused single-token launches (csrc/gemv.hip; 5-8 rows at a width of 4096 only)
 
     @staticmethod
     def _bf16_ok(*tensors, scale=None) -> bool:
@@ -273,11 +281,6 @@ class HipOps:
         (none when there are more, or fewer than `floor` rows in all)."""
         r = M % HipOps.TILE_ROWS
         return r if M >= floor and 1 <= r <= limit else 0
-
-    @staticmethod
-    def fused_rows_ok(M: int, K: int) -> bool:
-        """This many rows of width K fit the fused single-token launches (csrc/gemv.hip: norm + dense layer (+ gate / Hyena step) in one)."""
-        return 1 <= M <= 4 or (M <= HipOps.DECODE_ROWS and K == 4096)
 
     def _main_then_sliver(self, M: int, r: int, main, sliver) -> None:
         """The two launches of a dense layer of M rows whose last r are a sliver: `main(Mm)` for rows [0, Mm = M - r) -- whole tiles on the
@@ -415,38 +418,6 @@ class HipOps:
         return out
 
     # ---- the channel-major (z^T) form of the Hyena block's input: csrc/hyena_ct.hip -------------------------------------------
-    ZT_ALIGN = 64       # positions a batch row of z^T is padded to (% 8 == 0: 16-byte loads; 64 = whole cache lines -- tools/hc_bench.py A/B)
-
-    @staticmethod
-    def zt_layout(B: int, T: int):
-        """(Tm, Tp, Mp, r): where batch row b / token t of a [B, T] batch sits in z^T -- a pure function of the sizes.
-        Position b * Tp + t for t < Tm (the MAIN area: Mp = B Tp rounded up to the dense layer's 256-row tile positions), and for the
-        r = T - Tm last tokens of a row position Mp + 8 b + (t - Tm) (the TAIL block, one more block of 256 positions behind the main area).
-        Plain form: r = 0, Tm = T, Tp = T rounded up to ZT_ALIGN.  Tail form: T = 512 k + r with 1 <= r <= 8 (the bench shapes: a BOS token in
-        front of 2^k nucleotides) -- rows of 512 k positions need no padding and B * 512 k is a whole number of tiles, where the padded rows
-        cost the persistent dense layer one more round (+2.5 ... 4 % per projection, profiles/r04_hyena_ct_notes.txt section 3); the B r <= 16
-        tail tokens go through the weight-streaming kernel, as the BOS sliver of every other dense layer does (_tail_rows)."""
-        al = HipOps.ZT_ALIGN
-        Tp = (T + al - 1) // al * al
-        Mp = (B * Tp + 255) // 256 * 256
-        r = T % 512
-        Tm = T - r
-        if 1 <= r <= 8 and Tm >= 512 and B * r <= 16 and Tm % al == 0 and (B * Tm + 255) // 256 * 256 < Mp:
-            return Tm, Tm, (B * Tm + 255) // 256 * 256, r
-        return T, Tp, Mp, 0
-
-    @staticmethod
-    def zt_geometry(B: int, T: int):
-        """(Tp, Mp) of zt_layout: the row pitch and the number of positions of the main area."""
-        _, Tp, Mp, _ = HipOps.zt_layout(B, T)
-        return Tp, Mp
-
-    @staticmethod
-    def zt_positions(B: int, T: int, b: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-        """Position in z^T of (batch row b, token t), elementwise (zt_layout)."""
-        Tm, Tp, Mp, r = HipOps.zt_layout(B, T)
-        return torch.where(t < Tm, b * Tp + t, Mp + 8 * b + (t - Tm))
-
     def zt_shape_ok(self, B: int, T: int, N: int, K: int) -> bool:
         _, _, Mp, r = self.zt_layout(B, T)
         P = Mp + (256 if r else 0)
@@ -510,27 +481,6 @@ class HipOps:
         N = zt.shape[1]
         zt[-1].zero_()                                                                    # (6 MB: the tail block's unused positions hold zeros, not whatever the allocator left)
         zt[-1].view(N, 32, 8)[:, :B, :r] = z_tail.view(B, r, N).permute(2, 0, 1)
-
-    @staticmethod
-    def zt_rows(zt: torch.Tensor, B: int, T: int, t0: int, n: int) -> torch.Tensor:
-        """Steps t0 .. t0 + n - 1 of every batch row of a channel-major z^T [blocks, 3 D, 256] as token-major [B, n, 3 D] (reference
-        column order)."""
-        bb = torch.arange(B, device=zt.device)[:, None].expand(B, n)
-        tt = torch.arange(t0, t0 + n, device=zt.device)[None, :].expand(B, n)
-        pos = HipOps.zt_positions(B, T, bb, tt).reshape(-1)
-        return zt[pos // 256, :, pos % 256].view(B, n, zt.shape[1])
-
-    @staticmethod
-    def zt_from_rows(z: torch.Tensor, B: int, T: int, pad_value: float = 0.0) -> torch.Tensor:
-        """The inverse for whole sequences (tests, tools): token-major z [B, T, C] -> z^T [blocks, C, 256], pad positions = pad_value."""
-        Tm, Tp, Mp, r = HipOps.zt_layout(B, T)
-        C = z.shape[-1]
-        P = Mp + (256 if r else 0)
-        flat = torch.full((C, P), pad_value, dtype=z.dtype, device=z.device)
-        flat[:, :B * Tp].view(C, B, Tp)[:, :, :Tm] = z[:, :Tm].permute(2, 0, 1)
-        if r:
-            flat[:, Mp:].view(C, 32, 8)[:, :B, :r] = z[:, Tm:].permute(2, 0, 1)
-        return flat.view(C, P // 256, 256).permute(1, 0, 2).contiguous()
 
     def hyena_ct(self, zt, B, T, fir_w, fir_b, table, n_heads, z_halo=None, s0=None, want_state=False, poles=None,
                  state_only=False, b_first=0, y_blk=None, y_row0=0, b_total=None, main_only=False):
@@ -686,8 +636,6 @@ class HipOps:
                      residues.data_ptr(), dskip.data_ptr(), agg.data_ptr(), y.data_ptr(), _ptr(mask), B, T, D3 // 3, n_heads, C)
         return y
 
-    YBLK = 128          # rows per block of the blocked y layout (csrc/hyena_ct.hip)
-
     def yblk_empty(self, rows: int, D: int, device) -> torch.Tensor:
         """Uninitialised BLOCKED y for a [rows, D] matrix: [ceil(rows / 128), D / 16, 128, 16] bf16 (hyena_ct writes it, the output
         projection's dense layer reads it: linear_residual_yblk_)."""
@@ -720,11 +668,6 @@ class HipOps:
         return y_blk[Mf // self.YBLK:].permute(0, 2, 1, 3).reshape(-1, y_blk.shape[1] * 16)[:M - Mf].contiguous()
 
     # ---- RMSNorm folded into the dense layers around it (csrc/gemm.hip NF; include/evo_mi355x.h "RMSNorm folded ...") -----------------
-    @staticmethod
-    def fold_norm_scale(w: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-        """W diag(g) as a bf16 copy (fp32 product, one rounding): the weight the norm-consuming launches multiply the RAW stream by."""
-        return (w.float() * g.float()[None, :]).to(torch.bfloat16).contiguous()
-
     def nf_shape_ok(self, M: int, N: int, K: int) -> bool:
         """Shapes whose main rows the persistent dense layer takes with the norm folded in (sliver rows <= 16 or none)."""
         # (below 1,024 rows a forward is launch-bound -- four row tiles on 256 CUs -- and the fold would trade 63 small norm launches for 64 finalize launches)
@@ -887,11 +830,6 @@ class HipOps:
                      dskip.data_ptr(), y.data_ptr(), M, D, n_heads, float(eps))
         return y
 
-    @staticmethod
-    def attn_q_scale(hd: int) -> float:
-        """softmax_scale * log2(e) for head dim hd: what `rope_(..., q_scale=)` folds into the queries when the attention runs `prescaled`."""
-        return (1.0 / math.sqrt(hd)) * 1.4426950408889634
-
     def rope_(self, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, q_scale: float = 1.0) -> torch.Tensor:
         """In-place NeoX rotary on the q and k thirds of qkv [B,T,3,H,hd].  `q_scale`: the rotated queries are multiplied by it before their
         one rounding (attn_q_scale(hd) when the attention that follows is called with prescaled=True; 1.0: plain rotary, exact)."""
@@ -919,26 +857,19 @@ class HipOps:
             raise RuntimeError("rope_append_decode pos: need a contiguous device int64 tensor with B entries")
         self._check_address(pos.data_ptr(), "rope_append_decode pos", 8)
         self._need(inv_freq, torch.float32, "rope_append_decode inv_freq")
+        name, at = "evo_rope_append_decode_bf16", ()
         if widx is not None:
             if widx.dtype != torch.int64 or not widx.is_cuda or widx.numel() != B or not widx.is_contiguous():
                 raise RuntimeError("rope_append_decode widx: need a contiguous device int64 tensor with B entries")
             self._check_address(widx.data_ptr(), "rope_append_decode widx", 8)
-            _check(self.lib.evo_rope_append_decode_at_bf16(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(),
-                                                           float(scaling), B, H, hd, kv.stride(0), kv.stride(1), kv.stride(2),
-                                                           kv.stride(3), float(q_scale), widx.data_ptr(), _stream()),
-                   "evo_rope_append_decode_at_bf16")
-            return
-        _check(self.lib.evo_rope_append_decode_bf16(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(),
-                                                    float(scaling), B, H, hd, kv.stride(0), kv.stride(1), kv.stride(2),
-                                                    kv.stride(3), float(q_scale), _stream()), "evo_rope_append_decode_bf16")
+            name, at = "evo_rope_append_decode_at_bf16", (widx.data_ptr(),)
+        _check(getattr(self.lib, name)(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), inv_freq.data_ptr(), float(scaling), B, H, hd,
+                                       kv.stride(0), kv.stride(1), kv.stride(2), kv.stride(3), float(q_scale), *at, _stream()), name)
 
     def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_pos0: int, prescaled: bool = False) -> torch.Tensor:
         """Causal attention; q [B,Tq,H,128], k/v [B,Tk,H,128] (strided views allowed, last dim dense).  `prescaled`: q already carries
         softmax_scale * log2(e) (rope_'s q_scale = attn_q_scale(hd)): the 64-rows-per-wave kernel then runs without its per-score multiply."""
-        for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
-                raise RuntimeError(f"attention {nm}: need a ROCm bf16 tensor with a dense last dim")
-            self._check_address(t.data_ptr(), f"attention {nm}")
+        self._need_strided("attention", q=q, k=k, v=v)
         B, Tq, H, hd = q.shape
         Tk = k.shape[1]
         if hd != 128:
@@ -977,12 +908,7 @@ class HipOps:
         row b sees the P prefix keys and suffix keys 0 .. i of its row -- bit for bit `attention(q, cat(k_pre, k_b), cat(v_pre, v_b), P)`
         without the B copies.  vt_pre: the prefix's V^T plane from `attention_prefix_vt` (of these or MORE prefix keys), built here
         when None -- a caller with several groups per reference passes it.  P >= 64, P % 64 == 0 and Tq >= 129 (csrc/attn_w64.hip SEG)."""
-        named = [(q, "q"), (k, "k"), (v, "v"), (k_pre, "k_pre")] + ([(v_pre, "v_pre")] if v_pre is not None else []) \
-            + ([(vt_pre, "vt_pre")] if vt_pre is not None else [])
-        for t, nm in named:
-            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
-                raise RuntimeError(f"attention_prefix {nm}: need a ROCm bf16 tensor with a dense last dim")
-            self._check_address(t.data_ptr(), f"attention_prefix {nm}")
+        self._need_strided("attention_prefix", q=q, k=k, v=v, k_pre=k_pre, v_pre=v_pre, vt_pre=vt_pre)
         B, Tq, H, hd = q.shape
         if hd != 128 or k.shape != q.shape or v.shape != q.shape or k_pre.dim() != 3 or tuple(k_pre.shape[1:]) != (H, hd):
             raise RuntimeError("attention_prefix: expects q / k / v [B, Tq, H, 128] and k_pre [P, H, 128]")
@@ -1018,17 +944,9 @@ class HipOps:
             self._check_address(pos.data_ptr(), "attention_decode pos", 8)
         if Tq != 1 or hd != 128:
             raise RuntimeError("attention_decode: expects [B,1,H,128] queries")
-        for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1:
-                raise RuntimeError(f"attention_decode {nm}: need a ROCm bf16 tensor with a dense last dim")
-            self._check_address(t.data_ptr(), f"attention_decode {nm}")
+        self._need_strided("attention_decode", q=q, k=k, v=v)
         Tk = k.shape[1]
-        if n_splits is None:                     # one split per WAVE of the streaming kernel, whole workgroups of four, at most
-            # one per 64-key block.  Measured on MI355X (tools/experiments/attn_decode_bench.py, round 6: the kernel keeps the next 32-key
-            # half's requests in flight while it reduces the current one): 32 is best from 8 k to 131 k keys at batch 1-3 (29.5 / 78.7 /
-            # 102 / 384 us at 1 x 8 k / 3 x 8 k / 32 k / 131 k; 64 splits: 31.7 / 81.3 / 107 / 385; the load-then-reduce loop of rounds
-            # 3-5 wanted 64 and took 36.8 / 94.5 / 118 / 428)
-            n_splits = min(((Tk + 63) // 64 + 3) // 4 * 4, 32)
+        n_splits = self._decode_splits(Tk) if n_splits is None else n_splits
         o = torch.empty(B, 1, H, hd, dtype=torch.bfloat16, device=q.device)
         part_o = torch.empty(B, H, n_splits, hd, dtype=torch.float32, device=q.device)
         part_ml = torch.empty(B, H, n_splits, 2, dtype=torch.float32, device=q.device)
@@ -1044,7 +962,11 @@ class HipOps:
 
     @staticmethod
     def _decode_splits(n_keys: int) -> int:
-        """attention_decode's rule (see there): one split per wave, whole workgroups of four, at most one per 64-key block, at most 32."""
+        """Splits of a decode attention over n_keys keys: one per WAVE of the streaming kernel, whole workgroups of four, at most one per
+        64-key block, at most 32.  Measured on MI355X (tools/experiments/attn_decode_bench.py, round 6: the kernel keeps the next 32-key
+        half's requests in flight while it reduces the current one): 32 is best from 8 k to 131 k keys at batch 1-3 (29.5 / 78.7 / 102 /
+        384 us at 1 x 8 k / 3 x 8 k / 32 k / 131 k; 64 splits: 31.7 / 81.3 / 107 / 385; the load-then-reduce loop of rounds 3-5 wanted 64
+        and took 36.8 / 94.5 / 118 / 428)."""
         return min(((n_keys + 63) // 64 + 3) // 4 * 4, 32)
 
     def attention_decode_prefix(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, own_pos: torch.Tensor,
@@ -1057,10 +979,7 @@ class HipOps:
         B, Tq, H, hd = q.shape
         if Tq != 1 or hd != 128:
             raise RuntimeError("attention_decode_prefix: expects [B,1,H,128] queries")
-        for t, nm in ((q, "q"), (k, "k"), (v, "v"), (k_store, "k_store"), (v_store, "v_store")):
-            if not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1 or t.dim() != 4:
-                raise RuntimeError(f"attention_decode_prefix {nm}: need a 4-d ROCm bf16 tensor with a dense last dim")
-            self._check_address(t.data_ptr(), f"attention_decode_prefix {nm}")
+        self._need_strided("attention_decode_prefix", 4, q=q, k=k, v=v, k_store=k_store, v_store=v_store)
         R, P_cap = k_store.shape[:2]
         if k.shape[0] < B or v.shape != k.shape or tuple(k.shape[2:]) != (H, hd) or v_store.shape != k_store.shape or tuple(k_store.shape[2:]) != (H, hd) \
                 or R < 1 or P_cap < 1:
@@ -1097,16 +1016,6 @@ class HipOps:
                          M, w.shape[0], K, float(eps))
             return y
         return self.linear(self.rmsnorm(x, None, scale, eps), w, b, mfma=mfma)
-
-    @staticmethod
-    def pack_gate_weights(w12: torch.Tensor) -> torch.Tensor:
-        """[W1; W2] ([2 I, K]) -> the row order evo_mlp_gate_mfma_bf16 wants: blocks of 64 rows = rows 32 q .. 32 q + 31 of W1
-        followed by the same rows of W2, so that an output tile of the dense layer holds z1 and z2 of the same gated columns."""
-        I2, K = w12.shape
-        I = I2 // 2
-        if I % 32:
-            raise ValueError(f"pack_gate_weights: inner size {I} is not a multiple of 32")
-        return torch.stack([w12[:I].view(I // 32, 32, K), w12[I:].view(I // 32, 32, K)], 1).reshape(I2, K).contiguous()
 
     def mlp_gate_fused_ok(self, x: torch.Tensor, w12g: Optional[torch.Tensor]) -> bool:
         """The one-launch form of the gated MLP's first half (csrc/gemm.hip, gated epilogue) takes prefill-sized batches."""

@@ -203,7 +203,7 @@ class DecodePool:
 
     def _count_prefix_streams(self) -> None:
         """The store rows one step streams: per workgroup tile of the grouped kernel, the distinct rows among its slots."""
-        gr = int(getattr(self.model.ops, "attn_group_rows", 4))
+        gr = int(self.model.ops.attn_group_rows)
         self.stats["prefix_streams"] += sum(len({r for r in self._slot_row[t:t + gr] if r >= 0}) for t in range(0, self.n_slots, gr))
 
     def _allocate_history(self, n_tokens: int) -> None:

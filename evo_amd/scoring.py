@@ -15,6 +15,7 @@ from typing import List, NamedTuple, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from .backend import Backend
 from .tokenizer import CharLevelTokenizer
 
 
@@ -70,7 +71,7 @@ def _fused_tail_ok(model, input_ids) -> bool:
     ops = getattr(model, "ops", None) if hasattr(model, "hidden_states") else None
     if not getattr(model, "has_own_unembed", True) or not isinstance(getattr(getattr(model, "unembed", None), "weight", None), torch.Tensor):
         return False                    # model.unembed replaced (e.g. by an identity module): model(ids) returns what it makes
-    return (ops is not None and getattr(ops, "name", "") == "hip-gfx950" and hasattr(ops, "unembed_logprob")
+    return (isinstance(ops, Backend) and ops.name == "hip-gfx950" and ops.supports("unembed_logprob")
             and ops.unembed_logprob_ok(model.unembed.weight.new_empty(1, model.hidden_size), model.unembed.weight))
 
 
@@ -185,7 +186,7 @@ def score_profile_device(model, input_ids: torch.Tensor, token_ids):
     EVO_AMD_FUSED_TAIL=0) takes model(ids) -> an fp32 log-softmax where the logits live -> gather / index_select."""
     ids = profile_token_ids(token_ids)
     B, T = input_ids.shape
-    if _fused_tail_ok(model, input_ids) and hasattr(model.ops, "unembed_profile"):
+    if _fused_tail_ok(model, input_ids) and model.ops.supports("unembed_profile"):
         with torch.no_grad():
             hid = model.hidden_states(input_ids)                       # [B*T, D] final-norm output
             tgt = torch.full((B, T), -1, dtype=torch.int64, device=hid.device)
@@ -429,7 +430,7 @@ def score_variants(reference: str, variants: Sequence[str], model, tokenizer: Ch
         lp_ref = np.concatenate(parts)[:Tr - 1]
         kvs = dict(cache["mha"].key_value_memory_dict)
         vt = {}
-        if hasattr(model.ops, "attention_prefix_vt"):                  # one V^T plane per attention layer, every checkpoint reads its first columns
+        if model.ops.supports("attention_prefix_vt"):                  # one V^T plane per attention layer, every checkpoint reads its first columns
             vt = {i: model.ops.attention_prefix_vt(kv[0, :plan.checkpoints[-1], 1]) for i, kv in kvs.items()}
         shared = SharedPrefix(kv=kvs, vt=vt)
     delta = np.zeros(N, dtype=np.float64)

@@ -45,6 +45,11 @@ class InferenceParams:
     # set by StripedHyena.prefill_ragged: device int64 [B], the tokens of every row of a right-padded batch that are real.  KV rows behind
     # lengths[b] hold pad keys (a per-row-position decode overwrites them as it appends); a scalar seqlen_offset cannot describe such a cache
     lengths: Optional[Tensor] = None
+    # set for the duration of a single-token step (DecodePool, the captured decode step): device int64, one position PER ROW (or one for all)
+    # -- rotary, the KV append and the decode attention read it instead of the scalar seqlen_offset
+    pos_tensor: Optional[Tensor] = None
+    # (cos, sin) of pos_tensor for all attention layers of ONE step, on backends without "rope_append_decode" (StripedHyena.hidden_states)
+    _rot_dyn: Optional[tuple] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen

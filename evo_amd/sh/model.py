@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from ..ops import HipOps                                 # (its static host rules and pure tensor functions; no library is loaded by the import)
+from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
 from .cache import InferenceParams, RecurrentInferenceParams
 from .utils import dotdict
 
@@ -146,9 +146,15 @@ class StripedHyena(nn.Module):
             else:
                 blocks.append(_HyenaBlock(D, self.inner_size, self.state_size, self.short_filter_length))
         self.blocks = nn.ModuleList(blocks)
-        self._ops = ops
+        self._ops = Backend.adopt(ops)
         self._packed = False
         self._rot_cache: Dict[Tuple[int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._norms_folded = False                                 # fold_norms_: ONE weight set, the parameters are the folded weights
+        self._dgraph = self._dgraph_warm = None                    # the captured decode step and the caches whose first step ran eagerly
+        self.decode_graph_replays = 0
+        self._tail_ix = self._rows = self._inv_freq_dev = None     # small index tensors: _tail_split_index, _row_index, _inv_freq
+        # debugging / parity hook: a list that receives the residual stream entering every block, or only the listed ones (num_layers = the final stream)
+        self.block_taps = self.block_tap_idxs = None
 
     # ------------------------------------------------------------------ state-dict / dtype / device
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = True):
@@ -162,7 +168,7 @@ class StripedHyena(nn.Module):
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for StripedHyena: missing keys {missing}, "
                                f"unexpected keys {unexpected}")
-        if getattr(self, "_norms_folded", False):
+        if self._norms_folded:
             raise RuntimeError("load_state_dict on a model that holds one folded weight set (fold_norms_): build a fresh StripedHyena")
         for k, t in state_dict.items():
             if k not in own or k == "unembed.weight":
@@ -204,7 +210,7 @@ class StripedHyena(nn.Module):
         return self._ops
 
     def _pack(self):
-        if getattr(self, "_norms_folded", False):
+        if self._norms_folded:
             raise RuntimeError("this StripedHyena holds ONE folded weight set (fold_norms_): its derived tensors cannot be rebuilt from the "
                                "parameters -- moving / re-typing / re-loading needs a fresh model")
         self._pack_impl()
@@ -263,12 +269,12 @@ class StripedHyena(nn.Module):
         first use -- not covered by this call's out-of-memory check: `release_unused_weight_copies()` drops whichever set the current
         routing does not read, `fold_norms_()` keeps ONE weight set for good (14.5 GB)."""
         with torch.inference_mode(False), torch.no_grad():
-            if not self._packed and not getattr(self, "_norms_folded", False):
+            if not self._packed and not self._norms_folded:
                 self._pack()
             if prefill:
-                nf = getattr(self.ops, "fuse_norm", False) and hasattr(self.ops, "fold_norm_scale") and self.blocks[0].mlp._w12g_ok
+                nf = self.ops.fuse_norm and self.blocks[0].mlp._w12g_ok
                 for blk in self.blocks:
-                    if getattr(self, "_norms_folded", False):
+                    if self._norms_folded:
                         pass                                     # (one weight set: nothing to derive but the operand tables)
                     elif nf:                                   # the norm-folded copies the prefill launches read (see _nf_ok)
                         self._folded(blk.mlp, "_w12g_f", blk.mlp._w12, blk.post_norm.scale, gate=True)
@@ -278,7 +284,7 @@ class StripedHyena(nn.Module):
                             self._folded(blk.inner_mha_cls, "_wqkv_f", blk.inner_mha_cls.Wqkv.weight, blk.pre_norm.scale)
                     else:
                         self._gate_pack(blk, 1 << 20)
-                    if isinstance(blk, _HyenaBlock) and hasattr(self.ops, "hyena_ct") and self._table_ok(blk):
+                    if isinstance(blk, _HyenaBlock) and self.ops.supports("hyena_ct") and self._table_ok(blk):
                         self._mfma_table(blk)
         return self
 
@@ -294,7 +300,7 @@ class StripedHyena(nn.Module):
         One-way: `state_dict()` afterwards returns the folded, unit-scale equivalent (l1 / l2 un-grouped on demand); moving the model to
         another device / dtype or loading another state dict needs a fresh model.  A serving deployment calls
         `model.to(device).prepare().fold_norms_()` once after loading."""
-        if getattr(self, "_norms_folded", False):
+        if self._norms_folded:
             return self
         ops = self.ops
         with torch.inference_mode(False), torch.no_grad():
@@ -303,8 +309,8 @@ class StripedHyena(nn.Module):
             for blk in self.blocks:
                 mlp = blk.mlp
                 inner = mlp.l1.weight.shape[0]
-                w12f = HipOps.fold_norm_scale(mlp._w12, blk.post_norm.scale.data)
-                if mlp._w12g_ok and hasattr(ops, "pack_gate_weights"):
+                w12f = Backend.fold_norm_scale(mlp._w12, blk.post_norm.scale.data)
+                if mlp._w12g_ok and ops.supports("norm_fold"):     # (a backend with the folded launches reads l1 | l2 in the grouped order)
                     mlp._w12g = ops.pack_gate_weights(w12f)          # the ONLY copy of l1 | l2 from here on
                     mlp._w12 = None
                     mlp._l12_shape = (inner, w12f.shape[1])
@@ -319,11 +325,11 @@ class StripedHyena(nn.Module):
                 mlp._w12g_f = None
                 del w12f
                 if isinstance(blk, _HyenaBlock):
-                    blk.projections.weight.data = HipOps.fold_norm_scale(blk.projections.weight.data, blk.pre_norm.scale.data)
+                    blk.projections.weight.data = Backend.fold_norm_scale(blk.projections.weight.data, blk.pre_norm.scale.data)
                     blk._wp_f = None
                 else:
                     mha = blk.inner_mha_cls
-                    mha.Wqkv.weight.data = HipOps.fold_norm_scale(mha.Wqkv.weight.data, blk.pre_norm.scale.data)
+                    mha.Wqkv.weight.data = Backend.fold_norm_scale(mha.Wqkv.weight.data, blk.pre_norm.scale.data)
                     mha._wqkv_f = None
                 blk.pre_norm.scale.data = torch.ones_like(blk.pre_norm.scale.data)
                 blk.post_norm.scale.data = torch.ones_like(blk.post_norm.scale.data)
@@ -338,11 +344,9 @@ class StripedHyena(nn.Module):
         regrouped copy goes, otherwise the folded ones; whatever is dropped is rebuilt on the next call that needs it.  Returns the bytes
         released.  (`fold_norms_()` is the permanent form: one weight set.)"""
         before = self.resident_bytes()
-        fold = getattr(self.ops, "fuse_norm", False)
-        for blk in self.blocks:
-            if getattr(self, "_norms_folded", False):
-                break
-            if fold and getattr(blk.mlp, "_w12g_f", None) is not None:
+        fold = self.ops.fuse_norm
+        for blk in ([] if self._norms_folded else self.blocks):
+            if fold and blk.mlp._w12g_f is not None:
                 blk.mlp._w12g = None
             if not fold:
                 blk.mlp._w12g_f = None
@@ -354,7 +358,7 @@ class StripedHyena(nn.Module):
 
     def state_dict(self, *args, **kwargs):
         sd = super().state_dict(*args, **kwargs)
-        if getattr(self, "_norms_folded", False):
+        if self._norms_folded:
             prefix = kwargs.get("prefix", args[1] if len(args) > 1 else "")
             for i, blk in enumerate(self.blocks):
                 mlp = blk.mlp
@@ -408,27 +412,20 @@ class StripedHyena(nn.Module):
         hit = self._rot_cache.get(key)
         if hit is not None:
             return hit
-        hd = self.head_dim
-        inv_freq = 1.0 / (self.rotary_base ** (torch.arange(0, hd, 2, dtype=torch.float32, device=device) / hd))
-        t = torch.arange(pos0, pos0 + T, dtype=torch.float32, device=device)
-        if self.rotary_scaling != 1.0:
-            t = t / self.rotary_scaling
-        freqs = torch.outer(t, inv_freq)
-        cos = torch.cos(freqs).to(torch.bfloat16).float().contiguous()
-        sin = torch.sin(freqs).to(torch.bfloat16).float().contiguous()
+        hit = self._rotary_dyn(torch.arange(pos0, pos0 + T, dtype=torch.float32, device=device))
         if len(self._rot_cache) > 8:               # a decode step reuses its table for all attention layers
             self._rot_cache.clear()
-        self._rot_cache[key] = (cos, sin)
-        return cos, sin
+        self._rot_cache[key] = hit
+        return hit
 
     def _row_index(self, B: int, device) -> torch.Tensor:
-        hit = getattr(self, "_rows", None)
+        hit = self._rows
         if hit is None or hit.numel() < B or hit.device != torch.device(device):
             hit = self._rows = torch.arange(max(B, 8), dtype=torch.int64, device=device)
         return hit[:B]
 
     def _inv_freq(self, dev) -> torch.Tensor:
-        inv = getattr(self, "_inv_freq_dev", None)
+        inv = self._inv_freq_dev
         if inv is None or inv.device != torch.device(dev):
             hd = self.head_dim
             inv = 1.0 / (self.rotary_base ** (torch.arange(0, hd, 2, dtype=torch.float32, device=dev) / hd))
@@ -436,9 +433,8 @@ class StripedHyena(nn.Module):
         return inv
 
     def _rotary_dyn(self, pos: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Same table for positions held in device memory (int64 [n]: one per decode stream) -- no host read,
-        graph-capturable.  Returns cos, sin [n, hd/2]."""
-        hd = self.head_dim
+        """The table for positions held in device memory ([n]; int64: one per decode stream) -- no host read, graph-capturable.
+        Returns cos, sin [n, hd/2]."""
         inv = self._inv_freq(pos.device)
         t = pos.to(torch.float32)
         if self.rotary_scaling != 1.0:
@@ -448,39 +444,38 @@ class StripedHyena(nn.Module):
                 torch.sin(freqs).to(torch.bfloat16).float().contiguous())
 
     # ------------------------------------------------------------------ blocks
-    DECODE_ROWS = HipOps.DECODE_ROWS          # batches this small take the fused single-token launches (HipOps.fused_rows_ok)
+    DECODE_ROWS = Backend.DECODE_ROWS         # batches this small take the fused single-token launches (Backend.fused_rows_ok)
 
     def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False):
-        """x += y @ w^T (the mixer's output projection); returns the bias still to be added (folded into the next
-        RMSNorm pass for prefill-sized batches, into this launch for decode-sized ones)."""
-        # round 4: the bias rides in the dense layer's epilogue at every batch size (x <- bf16(x + y W^T + b): one rounding where the
-        # reference rounds twice); the post-mixer RMSNorm then reads x only (rmsnorm_kernel<false>: 4 D instead of 6 D bytes per token)
+        """x += y @ w^T + bias, the mixer's output projection (bias in the dense layer's epilogue: one rounding where the reference rounds twice)."""
         if y.dim() == 4:                                     # the Hyena operator's blocked output (ops.hyena_ct)
             self.ops.linear_residual_yblk_(x2d, y, w, bias=bias)
-            return None
-        self.ops.linear_residual_(x2d, y, w, mfma=mfma, bias=bias)
+        else:
+            self.ops.linear_residual_(x2d, y, w, mfma=mfma, bias=bias)
+
+    def _finish_block(self, blk, x2d, y, w, bias, nf, mask=None, mfma=False):
+        """Every block's end: x += y @ w^T + bias, then x += MLP(x).  `nf` (_nf_ok): returns the NEXT block's `rs`; else None.  `mask`: [B T, 1]."""
+        if nf:
+            return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, y, w, bias))
+        self._mixer_out_(blk, x2d, y, w, bias, mfma=mfma)
+        self._mlp_residual_(blk, x2d, mask)
         return None
 
-    # ---- RMSNorm folded into the dense layers around it (round 5; csrc/gemm.hip NF, include/evo_mi355x.h) ---------------------------
-    # The dense layer that writes the residual stream (mixer output projection, l3) also emits every row's 1 / (rms + eps) -- `rs` below,
-    # handed from block to block --, and the layer that consumes the norm (Hyena projections, Wqkv, l1 | l2) reads the stream itself and
-    # applies rs in its epilogue, with the norm's scale vector folded into a copy of its weight.  What remains of the 65 RMSNorm
-    # passes of a forward: block 0's pre-norm (the embedding has no dense layer in front of it) and the final norm.
+    # ---- RMSNorm folded into the dense layers around it (csrc/gemm.hip NF; DESIGN.md): `rs` = every row's 1 / (rms + eps), block to block
     def _nf_ok(self, M: int, mask) -> bool:
-        ops = self.ops
-        D = self.hidden_size
-        if mask is not None or not getattr(ops, "fuse_norm", False) or not hasattr(ops, "nf_shape_ok"):
+        ops, D = self.ops, self.hidden_size
+        if mask is not None or not ops.fuse_norm or not ops.supports("norm_fold"):
             return False
         m0 = self.blocks[0].mlp
         ipad = (m0._w12 if m0._w12 is not None else m0._w12g).shape[0] // 2
         return (ops.nf_shape_ok(M, D, D) and ops.nf_shape_ok(M, 3 * D, D) and ops.nf_shape_ok(M, 2 * ipad, D) and ops.nf_shape_ok(M, D, ipad)
-                and getattr(self.blocks[0].mlp, "_w12g_ok", False) and getattr(ops, "mlp_gate_fused", False))
+                and m0._w12g_ok and ops.mlp_gate_fused)
 
     def _folded(self, owner, name: str, w: torch.Tensor, g: torch.Tensor, gate: bool = False) -> torch.Tensor:
         """bf16(W diag(g)) of a norm-consuming layer (for l1 | l2: in the gated launch's row order), built on first use / by prepare()."""
-        if getattr(self, "_norms_folded", False):            # one weight set: the parameters ARE the folded weights (fold_norms_)
+        if self._norms_folded:                               # one weight set: the parameters ARE the folded weights (fold_norms_)
             return owner._w12g if gate else w.data
-        hit = getattr(owner, name, None)
+        hit = getattr(owner, name)
         if hit is None or hit.device != w.device:
             with torch.inference_mode(False), torch.no_grad():
                 hit = self.ops.fold_norm_scale(w.data, g.data)
@@ -498,8 +493,7 @@ class StripedHyena(nn.Module):
     def _mlp_residual_rs_(self, blk, x2d, rs_post):
         """The block's MLP on the raw stream (post-norm as a row factor in the gated launch), residual added in place; returns the NEXT
         pre-norm's row factors (l3's epilogue statistic)."""
-        ops = self.ops
-        mlp = blk.mlp
+        ops, mlp = self.ops, blk.mlp
         w12g_f = self._folded(mlp, "_w12g_f", mlp._w12, blk.post_norm.scale, gate=True)
         a = ops.mlp_gate_rs(x2d, rs_post, w12g_f, mlp._w12, blk.post_norm.scale, self.eps)
         return ops.linear_residual_stats_(x2d, a, mlp._w3, None, self.eps)
@@ -507,44 +501,32 @@ class StripedHyena(nn.Module):
     def _gate_pack(self, blk, M: int):
         """The regrouped l1 | l2 weight of the one-launch gated MLP, built the first time a prefill-sized batch needs it."""
         mlp = blk.mlp
-        if mlp._w12g is None and mlp._w12 is not None and M >= 256 and getattr(mlp, "_w12g_ok", False) and getattr(self.ops, "mlp_gate_fused", False) \
-                and hasattr(self.ops, "pack_gate_weights"):
+        if mlp._w12g is None and mlp._w12 is not None and M >= 256 and mlp._w12g_ok and self.ops.mlp_gate_fused:
             mlp._w12g = self.ops.pack_gate_weights(mlp._w12)
         return mlp._w12g
 
-    def _mlp_residual_(self, blk, x2d, bias, mask=None):
+    def _mlp_residual_(self, blk, x2d, mask=None):
+        """x += MLP(post_norm(x)), in place; `mask` (flat [B T, 1]): upstream's (mixer out + u) * padding_mask first."""
         ops = self.ops
         self._gate_pack(blk, x2d.shape[0])
-        if mask is not None:                                             # upstream: (mixer out + u) * padding_mask
-            if bias is not None:
-                x2d.add_(bias)
-                bias = None
+        if mask is not None:
             x2d.mul_(mask)
             n2 = ops.rmsnorm(x2d, None, blk.post_norm.scale, self.eps)
             a = ops.mlp_gate(n2, blk.mlp._w12, w12g=blk.mlp._w12g)
-            ops.linear_residual_(x2d, a, blk.mlp._w3)
-            return
-        if bias is None:                                                 # decode: norm + l1/l2 + gate in one launch
+        else:                                                            # norm + l1 / l2 + gate in one launch where the rows allow
             a = ops.mlp_gate(x2d, blk.mlp._w12, blk.post_norm.scale, self.eps, w12g=blk.mlp._w12g)
-        else:
-            n2 = ops.rmsnorm(x2d, bias, blk.post_norm.scale, self.eps)   # x += bias (in place); n2 = norm(x)
-            a = ops.mlp_gate(n2, blk.mlp._w12, w12g=blk.mlp._w12g)
         ops.linear_residual_(x2d, a, blk.mlp._w3)
 
     def _mfma_hyena_ok(self, B: int, T: int) -> bool:
         """The single-pass matrix-core operator (csrc/hyena_ct.hip) serves every parallel (T > 1) Hyena call without a padding mask on
         the HIP backend -- scoring, cached prefill with carry-in / end state, sequence-parallel shards -- when the shape fits its launch
         contract; masks and very short inputs take the modal kernels.  (Shape part only: _hyena_ct_ok adds the tensors' checks.)"""
-        ops = self.ops
-        D, H = self.hidden_size, self.num_heads
-        if not getattr(ops, "hyena_mfma", False) or not hasattr(ops, "hyena_ct") or D != H * 128:
-            return False
-        return T >= 32 and B * T >= 256
+        return bool(T >= 32 and B * T >= 256 and self.hidden_size == self.num_heads * 128 and self.ops.hyena_mfma and self.ops.supports("hyena_ct"))
 
     def _mfma_table(self, blk):
         """The MFMA operand table of a Hyena block's filter (evo_amd/hyena_tables.py), built on first use."""
         f = blk.filter
-        if getattr(f, "_mfma_tab", None) is None or f._mfma_tab.device != blk.projections.weight.device:
+        if f._mfma_tab is None or f._mfma_tab.device != blk.projections.weight.device:
             from ..hyena_tables import mfma_operand_table
             f._mfma_tab = mfma_operand_table(f._poles, f._residues, f.D.data)
         return f._mfma_tab
@@ -554,122 +536,127 @@ class StripedHyena(nn.Module):
         modes cancel to ~1 % amplify the splits' 2^-16 to a bf16 rounding; such a layer runs the modal kernels -- fp32 states, every regime.)
         Decided once per layer from the poles / residues alone; `ops.hyena_table_guard = False` skips the check (tests of the guard itself)."""
         f = blk.filter
-        if not getattr(self.ops, "hyena_table_guard", True):
+        if not self.ops.hyena_table_guard:
             return True
-        if getattr(f, "_tab_prec", None) is None:
-            from ..hyena_tables import table_precision
+        from ..hyena_tables import TABLE_TOL, table_precision
+        if f._tab_prec is None:
             f._tab_prec = float(table_precision(f._poles, f._residues, f.D.data).max())
-        from ..hyena_tables import TABLE_TOL
         return f._tab_prec <= TABLE_TOL
 
     def _hyena_ct_ok(self, x2d, blk, B, T) -> bool:
-        ops = self.ops
-        w = blk.projections.weight
-        return (getattr(ops, "hyena_ct_flag", False) and hasattr(ops, "hyena_ct") and x2d.is_cuda and w.dtype == torch.bfloat16
+        ops, w = self.ops, blk.projections.weight
+        return (ops.hyena_ct_flag and ops.supports("hyena_ct") and x2d.is_cuda and w.dtype == torch.bfloat16
                 and w.is_contiguous() and ops.zt_shape_ok(B, T, w.shape[0], w.shape[1]))
 
     def _hyena_block(self, i, blk, x2d, B, T, cache: Optional[RecurrentInferenceParams], mask=None, rs=None):
-        """`mask` = (flat [B*T,1] bf16, [B,T] uint8) of upstream's padding_mask, or None: the projections output, the FIR
-        output and the mixer output + residual are multiplied by it, as upstream's ParallelGatedConvBlock /
-        engine.parallel_fir do [UPSTREAM-RECALLED; evo never passes one, SURVEY 8b]."""
-        ops = self.ops
-        D, H = self.hidden_size, self.num_heads
-        f = blk.filter
+        """One Hyena block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  Three routes: the decode step,
+        the channel-major operator, the modal form.  `mask` = (flat [B*T,1] bf16, [B,T] uint8) of upstream's
+        padding_mask, or None: the projections output, the FIR output and the mixer output + residual are multiplied by it, as upstream's
+        ParallelGatedConvBlock / engine.parallel_fir do [UPSTREAM-RECALLED; evo never passes one, SURVEY 8b]."""
         have_state = cache is not None and i in cache.fir_state_dict
-        K1 = self.short_filter_length - 1
-        lens = getattr(cache, "lengths", None) if cache is not None and T > 1 else None     # set by prefill_ragged: per-row end states
+        lens = cache.lengths if cache is not None and T > 1 else None     # set by prefill_ragged: per-row end states
         if lens is not None and (have_state or mask is not None):
             raise ValueError("a ragged prefill (lengths) starts at t = 0 without a padding mask: no resumed prefill, no mask")
-        if have_state and T == 1:                 # decode: norm + projections + FIR/modal step + gate in one launch
-            y = ops.hyena_decode_fused(x2d, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias,
-                                       cache.fir_state_dict[i], cache.state_dict[i], f._fir_w, f.short_filter_bias,
-                                       f._poles, f._residues, f.D, H)
+        nf = False
+        if have_state and T == 1:
+            y = self._hyena_decode_step(blk, x2d, cache.fir_state_dict[i], cache.state_dict[i])
         elif mask is None and self._mfma_hyena_ok(B, T) and self._hyena_ct_ok(x2d, blk, B, T) and self._table_ok(blk):
-            # the whole operator in ONE pass on the matrix cores (csrc/hyena_ct.hip) -- scoring and cached prefill (carry-in state + FIR
-            # history in, end state out) alike.
-            # z CHANNEL-MAJOR.  The pre-norm writes its rows in z^T's position order (HipOps.zt_layout: batch
-            # rows padded to a multiple of 64 positions, or -- T = 512 k + r, the bench shapes -- unpadded rows of 512 k positions with
-            # the last r tokens of every row in a tail block), the projection's dense layer runs with swapped operands (result = z^T, the weight as it is -- no
-            # regrouped copy) and the operator loads a lane's eight steps of a channel as 16 contiguous bytes straight into
-            # registers (no window in LDS); y BLOCKED: the operator stores whole cache lines and the output projection's dense layer
-            # gathers them -- no row-major y exists on this path.
-            table = self._mfma_table(blk)
             nf = self._nf_ok(B * T, mask)
-            pb = None if blk.projections.bias is None else blk.projections.bias.data
-            # T = 512 k + 1 (a BOS token in front of 2^k nucleotides), scoring: the one token behind the whole tiles of every row does not
-            # go through the operator as a ragged tile (one valid step at a full tile's issue time: 8 of 136 tile steps at 8 x 8,193) but
-            # through the fused single-token launch of the decode path, from the operator's end state (ops.hyena_tail_split)
-            Tm, _, _, r_tail = ops.zt_layout(B, T)
-            split = (cache is None and r_tail == 1 and getattr(ops, "hyena_tail_split", False) and HipOps.fused_rows_ok(B, D)
-                     and pb is not None)
-            if nf and rs is not None and ops.zt_stream_rows_ok(B, T):
-                # pre-norm folded: the projection reads the stream itself (z^T layouts without pad positions inside the main area: no padded copy either)
-                wp_f = self._folded(blk, "_wp_f", blk.projections.weight, blk.pre_norm.scale)
-                zt = ops.linear_t_rs(x2d, rs, wp_f, pb, blk.projections.weight.data, blk.pre_norm.scale, self.eps, B, T, tail=not split)
-            else:
-                xp = ops.rmsnorm_rows(x2d, blk.pre_norm.scale, self.eps, B, T)
-                zt = ops.linear_t(xp, blk.projections.weight.data, pb, B, T, tail=not split)
-            yb = ops.yblk_empty(B * T, D, zt.device)
-            if split:
-                y, state = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, want_state=True, poles=f._poles, y_blk=yb,
-                                        main_only=True)
-                ix = self._tail_split_index(B, T, zt.device)
-                fir = zt[ix["zblk"], :, 256 - K1:].contiguous()                         # [B, 3 D, 2]: steps Tm - 2, Tm - 1 of every row, oldest first
-                x_tail = x2d.view(B, T, D)[:, Tm].contiguous()                          # the raw stream's rows (the launch norms them itself)
-                y_tail = ops.hyena_decode_fused(x_tail, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias, fir, state,
-                                                f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, H)
-                yb[ix["yblk"], :, ix["yrow"], :] = y_tail.view(B, D // 16, 16)          # rows b T + Tm of the blocked y
-            elif cache is None:
-                y = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, y_blk=yb)
-            elif lens is not None:
-                # ragged batch: y everywhere as usual; state and FIR history at every row's OWN last token (csrc/hyena_ragged.hip)
-                y = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, y_blk=yb)
-                cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at_zt(zt, B, T, lens, f._fir_w, f.short_filter_bias, f._poles, H)
-            else:
-                halo = s0 = None
-                if have_state:              # continue a cached prefix with more than one token
-                    halo = cache.fir_state_dict[i].transpose(1, 2).contiguous()
-                    s0 = cache.state_dict[i]
-                y, state = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, z_halo=halo, s0=s0,
-                                        want_state=True, poles=f._poles, y_blk=yb)
-                cache.fir_state_dict[i] = ops.zt_rows(zt, B, T, T - K1, K1).transpose(1, 2).contiguous()   # [B, 3D, 2]
-                cache.state_dict[i] = state
-            if nf:
-                return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias))
-            self._mlp_residual_(blk, x2d, self._mixer_out_(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias), None)
-            return None
+            y = self._hyena_channel_major(i, blk, x2d, B, T, cache, lens, rs, nf)
         else:
-            z = ops.norm_linear(x2d, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias)   # [B*T, 3D]
-            if mask is not None:
-                z.mul_(mask[0])
-            z3 = z.view(B, T, 3 * D)
-            halo = s0 = None
-            if have_state:                      # continue a cached prefix with more than one token
-                halo = cache.fir_state_dict[i].transpose(1, 2).contiguous()
-                s0 = cache.state_dict[i]
-            kw = {} if mask is None else {"mask": mask[1]}
-            y3, state = ops.hyena_prefill(z3, f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, H,
-                                          z_halo=halo, s0=s0, want_state=cache is not None and lens is None, **kw)
-            y = y3.view(B * T, D)
-            if lens is not None:
-                cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at(z3, lens, f._fir_w, f.short_filter_bias, f._poles, H)
-            elif cache is not None:
-                tail = z3[:, -K1:, :]
-                if halo is not None and T < K1:
-                    tail = torch.cat([halo[:, T:], tail], dim=1)
-                elif T < K1:
-                    tail = torch.cat([z3.new_zeros(B, K1 - T, 3 * D), tail], dim=1)
-                cache.fir_state_dict[i] = tail.transpose(1, 2).contiguous()      # [B, 3D, 2]
-                cache.state_dict[i] = state
-        self._mlp_residual_(blk, x2d, self._mixer_out_(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias),
-                            None if mask is None else mask[0])
-        return None
+            y = self._hyena_modal(i, blk, x2d, B, T, cache, lens, mask)
+        return self._finish_block(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf, None if mask is None else mask[0])
+
+    def _hyena_decode_step(self, blk, x, fir_state, iir_state):
+        """One token per row: norm + projections + FIR / modal step + gate in one launch; the two states advance in place."""
+        f = blk.filter
+        return self.ops.hyena_decode_fused(x, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias, fir_state, iir_state,
+                                           f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, self.num_heads)
+
+    @staticmethod
+    def _carry_in(cache, i):
+        """(halo [B, 2, 3 D], s0) of the cached prefix layer i continues with more than one token, (None, None) at t = 0."""
+        if cache is None or i not in cache.fir_state_dict:
+            return None, None
+        return cache.fir_state_dict[i].transpose(1, 2).contiguous(), cache.state_dict[i]
+
+    def _hyena_z(self, blk, x2d, rs, B, T, tail=True, zt=True, nf=False):
+        """How a Hyena block's projection z comes about -> (normed, project).  The pre-norm pass, if the form has one, is launched HERE;
+        `project()` -- to be called exactly ONCE -- launches the projection and returns z: sp.py puts its halo rows' launches in between.
+          1. zt, nf, rs given, zt_stream_rows_ok: the swapped-operand dense layer reads the stream itself, rs in its epilogue  -> z^T
+          2. zt: the pre-norm writes its rows in z^T's position order (rmsnorm_rows), then the swapped-operand layer          -> z^T
+          3. otherwise: norm, then the plain dense layer -> token-major z [B, T, 3 D]; `normed` = the normalised rows (else None)
+        z^T: channel-major [blocks, 3 D, 256] (Backend.zt_layout; `tail=False` leaves its tail block out); the weight is read as it is."""
+        ops = self.ops
+        w, scale = blk.projections.weight.data, blk.pre_norm.scale
+        pb = None if blk.projections.bias is None else blk.projections.bias.data
+        if zt and nf and rs is not None and ops.zt_stream_rows_ok(B, T):
+            return None, lambda: ops.linear_t_rs(x2d, rs, self._folded(blk, "_wp_f", blk.projections.weight, scale), pb, w, scale, self.eps,
+                                                 B, T, tail=tail)
+        if zt:
+            xp = ops.rmsnorm_rows(x2d, scale, self.eps, B, T)
+            return None, lambda: ops.linear_t(xp, w, pb, B, T, tail=tail)
+        n1 = ops.rmsnorm(x2d, None, scale, self.eps)
+        return n1, lambda: ops.linear(n1, w, pb).view(B, T, w.shape[0])
+
+    def _hyena_channel_major(self, i, blk, x2d, B, T, cache, lens, rs, nf):
+        """The whole operator in ONE pass on the matrix cores (csrc/hyena_ct.hip) -- scoring and cached prefill (carry-in state + FIR
+        history in, end state out) alike -- on z^T (_hyena_z: a lane's eight steps of a channel are 16 contiguous bytes, no window in LDS).
+        Returns y BLOCKED: the operator stores whole cache lines and the output projection gathers them -- no row-major y on this route."""
+        ops = self.ops
+        D, H, f = self.hidden_size, self.num_heads, blk.filter
+        K1 = self.short_filter_length - 1
+        table = self._mfma_table(blk)
+        # tail split (T = 512 k + 1 scoring, ops.hyena_tail_split): the one token behind every row's whole tiles takes the fused single-token
+        # launch from the operator's end state, not a ragged tile (HipOps.hyena_ct, main_only)
+        Tm, _, _, r_tail = ops.zt_layout(B, T)
+        split = (cache is None and r_tail == 1 and ops.hyena_tail_split and Backend.fused_rows_ok(B, D) and blk.projections.bias is not None)
+        zt = self._hyena_z(blk, x2d, rs, B, T, tail=not split, nf=nf)[1]()
+        yb = ops.yblk_empty(B * T, D, zt.device)
+        if split:
+            _, state = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, want_state=True, poles=f._poles, y_blk=yb, main_only=True)
+            ix = self._tail_split_index(B, T, zt.device)
+            fir = zt[ix["zblk"], :, 256 - K1:].contiguous()                         # [B, 3 D, 2]: steps Tm - 2, Tm - 1 of every row, oldest first
+            x_tail = x2d.view(B, T, D)[:, Tm].contiguous()                          # the raw stream's rows (the launch norms them itself)
+            yb[ix["yblk"], :, ix["yrow"], :] = self._hyena_decode_step(blk, x_tail, fir, state).view(B, D // 16, 16)   # rows b T + Tm of the blocked y
+        elif cache is None or lens is not None:
+            ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, y_blk=yb)
+            if lens is not None:             # ragged batch: state and FIR history at every row's OWN last token (csrc/hyena_ragged.hip)
+                cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at_zt(zt, B, T, lens, f._fir_w, f.short_filter_bias, f._poles, H)
+        else:
+            halo, s0 = self._carry_in(cache, i)
+            _, cache.state_dict[i] = ops.hyena_ct(zt, B, T, f._fir_w, f.short_filter_bias, table, H, z_halo=halo, s0=s0, want_state=True,
+                                                  poles=f._poles, y_blk=yb)
+            cache.fir_state_dict[i] = ops.zt_rows(zt, B, T, T - K1, K1).transpose(1, 2).contiguous()   # [B, 3D, 2]
+        return yb
+
+    def _hyena_modal(self, i, blk, x2d, B, T, cache, lens, mask):
+        """The three-launch modal form on token-major z (fp32 states, every regime).  Returns y [B T, D]."""
+        ops = self.ops
+        D, H, f = self.hidden_size, self.num_heads, blk.filter
+        K1 = self.short_filter_length - 1
+        z = ops.norm_linear(x2d, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias)   # [B*T, 3D]
+        if mask is not None:
+            z.mul_(mask[0])
+        z3 = z.view(B, T, 3 * D)
+        halo, s0 = self._carry_in(cache, i)
+        y3, state = ops.hyena_prefill(z3, f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, H, z_halo=halo, s0=s0,
+                                      want_state=cache is not None and lens is None, mask=None if mask is None else mask[1])
+        if lens is not None:
+            cache.state_dict[i], cache.fir_state_dict[i] = ops.hyena_state_at(z3, lens, f._fir_w, f.short_filter_bias, f._poles, H)
+        elif cache is not None:
+            tail = z3[:, -K1:, :]
+            if T < K1:                           # (a one-token prefill of a fresh cache; with state, one token is the decode step)
+                tail = torch.cat([z3.new_zeros(B, K1 - T, 3 * D), tail], dim=1)
+            cache.fir_state_dict[i] = tail.transpose(1, 2).contiguous()      # [B, 3D, 2]
+            cache.state_dict[i] = state
+        return y3.view(B * T, D)
 
     def _tail_split_index(self, B: int, T: int, device):
         """Index tensors of the tail-split routing (_hyena_block), cached per (B, T): the z^T block holding the last two main steps of every
         batch row, and block / row of the blocked y for the rows b T + Tm."""
         key = (B, T, str(device))
-        cur = getattr(self, "_tail_ix", None)
+        cur = self._tail_ix
         if cur is None or cur[0] != key:
             Tm = self.ops.zt_layout(B, T)[0]
             b = torch.arange(B, device=device)
@@ -694,6 +681,8 @@ class StripedHyena(nn.Module):
         return kv
 
     def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None):
+        """One attention block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  After Wqkv, by the cache:
+        per-row decode step (pos_tensor), shared-prefix attention, scalar-offset decode step, causal attention."""
         ops = self.ops
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         mha = blk.inner_mha_cls
@@ -706,69 +695,53 @@ class StripedHyena(nn.Module):
         else:
             qkv = ops.norm_linear(x2d, blk.pre_norm.scale, self.eps, mha.Wqkv.weight, mha.Wqkv.bias, mfma=True).view(B, T, 3, H, hd)
         off = int(cache.seqlen_offset) if cache is not None else 0
-        pos = getattr(cache, "pos_tensor", None) if cache is not None else None
-        if T > 1 and cache is not None and getattr(cache, "lengths", None) is not None \
-                and (off != 0 or mask is not None or getattr(cache, "shared_prefix", None) is not None):
+        pos = cache.pos_tensor if cache is not None else None
+        shared = cache.shared_prefix if cache is not None else None
+        if T > 1 and cache is not None and cache.lengths is not None and (off != 0 or mask is not None or shared is not None):
             raise ValueError("a ragged prefill (lengths) starts at t = 0 with keys of its own: no resumed prefill, no mask, no shared_prefix")
         q = qkv[:, :, 0]
-        # round 6: the rotary kernel folds softmax_scale * log2(e) into its one rounding of q and the attention kernels take scores as
-        # exponents (ops.attn_prescale; csrc/attn_w64.hip PRE: no per-score multiply) -- q is never cached, so K / V and the KV cache are untouched
-        pre = bool(getattr(ops, "attn_prescale", False)) and hasattr(ops, "attn_q_scale")
-        rk = {"q_scale": ops.attn_q_scale(hd)} if pre else {}
-        ak = {"prescaled": True} if pre else {}
+        # ops.attn_prescale: the rotary kernel folds softmax_scale * log2(e) into its one rounding of q, the attention kernels take scores as exponents
+        pre = bool(ops.attn_prescale)
+        q_scale = ops.attn_q_scale(hd) if pre else 1.0
         if pos is not None and T == 1:
-            # position-independent decode step (hipGraph replay, continuous batching): one position PER ROW, in
-            # device memory.  The rotary kernel indexes its table by token, so the B rows are presented as one
-            # sequence of B tokens with the per-row table.
+            # one position PER ROW, in device memory (hipGraph replay, continuous batching); behind a prompt store the append goes to the row's OWN index
             kv = cache.key_value_memory_dict[i][:B]
-            store = getattr(cache, "prompt_store", None)
-            if store is not None:
-                # the rows continue prompts held ONCE in a store (DecodePool share_prompt_kv): rotary at the absolute position, the append
-                # at the row's own index, attention over the store row's keys and then the row's own
-                if hasattr(ops, "rope_append_decode") and pos.numel() == B:
-                    ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, widx=store.own_pos, **rk)
-                else:
-                    cos, sin = getattr(cache, "_rot_dyn", None) or self._rotary_dyn(pos)
-                    ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, **rk)
-                    kv[self._row_index(B, x2d.device), store.own_pos] = qkv[:, 0, 1:3]
-                skv = store.kv[i]
-                a = ops.attention_decode_prefix(q, kv[:, :, 0], kv[:, :, 1], store.own_pos, skv[:, :, 0], skv[:, :, 1], store.row,
-                                                store.length, **ak).view(B, D)
+            store = cache.prompt_store
+            widx = store.own_pos if store is not None else None
+            if ops.supports("rope_append_decode") and pos.numel() == B:
+                # rotary at each row's position + the KV append in one launch (no per-step cos / sin table)
+                ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, q_scale=q_scale, widx=widx)
             else:
-                if hasattr(ops, "rope_append_decode") and pos.numel() == B:
-                    # rotary at each row's position + the KV append in one launch (no per-step cos / sin table)
-                    ops.rope_append_decode(qkv, kv, pos, self._inv_freq(x2d.device), self.rotary_scaling, **rk)
-                else:
-                    cos, sin = getattr(cache, "_rot_dyn", None) or self._rotary_dyn(pos)
-                    ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, **rk)
-                    kv[self._row_index(B, x2d.device), pos] = qkv[:, 0, 1:3]
-                a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, **ak).view(B, D)
+                # the rotary kernel indexes its table by token, so the B rows are presented as one sequence of B tokens with the per-row table
+                cos, sin = cache._rot_dyn or self._rotary_dyn(pos)
+                ops.rope_(qkv.view(1, B, 3, H, hd), cos, sin, q_scale=q_scale)
+                kv[self._row_index(B, x2d.device), pos if widx is None else widx] = qkv[:, 0, 1:3]
+            if store is not None:
+                skv = store.kv[i]
+                a = ops.attention_decode_prefix(q, kv[:, :, 0], kv[:, :, 1], widx, skv[:, :, 0], skv[:, :, 1], store.row, store.length,
+                                                prescaled=pre)
+            else:
+                a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, prescaled=pre)
         else:
             cos, sin = self._rotary(off, T, x2d.device)
-            ops.rope_(qkv, cos, sin, **rk)
-            shared = getattr(cache, "shared_prefix", None) if cache is not None else None
+            ops.rope_(qkv, cos, sin, q_scale=q_scale)
             if shared is not None:
-                # every row continues the first `off` tokens of ONE reference (score_variants): its keys / values are read from the
-                # reference's own buffer, the rows' own from qkv -- no per-row KV buffer exists
+                # every row continues the first `off` tokens of ONE reference (score_variants), read from its own buffer: no per-row KV buffer
                 kvr = shared.kv[i]
-                a = ops.attention_prefix(q, qkv[:, :, 1], qkv[:, :, 2], kvr[0, :off, 0], kvr[0, :off, 1], vt_pre=shared.vt.get(i), **ak).view(B * T, D)
+                a = ops.attention_prefix(q, qkv[:, :, 1], qkv[:, :, 2], kvr[0, :off, 0], kvr[0, :off, 1], vt_pre=shared.vt.get(i), prescaled=pre)
             else:
                 if cache is not None:
                     kv = self._kv_buffer(cache, i, B, off + T, qkv)
                     kv[:B, off:off + T].copy_(qkv[:, :, 1:3])
-                    k = kv[:B, : off + T, 0]
-                    v = kv[:B, : off + T, 1]
+                    k, v = kv[:B, : off + T, 0], kv[:B, : off + T, 1]
                 else:
                     k, v = qkv[:, :, 1], qkv[:, :, 2]
                 if T == 1 and cache is not None:
-                    a = ops.attention_decode(q, k, v, **ak).view(B, D)      # split-K over the KV cache
+                    a = ops.attention_decode(q, k, v, prescaled=pre)      # split-K over the KV cache
                 else:
-                    a = ops.attention(q, k, v, off, **ak).view(B * T, D)
-        if nf:
-            return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, a, mha.out_proj.weight, mha.out_proj.bias))
-        self._mlp_residual_(blk, x2d, self._mixer_out_(blk, x2d, a, mha.out_proj.weight, mha.out_proj.bias, mfma=True),
-                            None if mask is None else mask[0])
-        return None
+                    a = ops.attention(q, k, v, off, prescaled=pre)
+        return self._finish_block(blk, x2d, a.view(B * T, D), mha.out_proj.weight, mha.out_proj.bias, nf, None if mask is None else mask[0],
+                                  mfma=True)
 
     # ------------------------------------------------------------------ forward
     max_rows_per_pass = 160 * 1024     # rows (B T) of one stateless pass; larger batches run in row groups (hidden_states)
@@ -788,7 +761,7 @@ class StripedHyena(nn.Module):
 
         def fits(p):
             r = (p * T) % 256                                # (grouping is decided for the 7B width, where up to DECODE_ROWS rows fit)
-            return r == 0 or HipOps.fused_rows_ok(r, 4096)
+            return r == 0 or Backend.fused_rows_ok(r, 4096)
 
         if B <= cap and (fits(B) or B * T < 65536):
             return [B]
@@ -832,10 +805,9 @@ class StripedHyena(nn.Module):
         if padding_mask is not None:
             pm = padding_mask.to(self.device) != 0
             mask = (pm.reshape(B * T, 1).to(h.dtype), pm.to(torch.uint8).contiguous())
-        mha_c = inference_params_dict["mha"] if inference_params_dict is not None else None
-        hy_c = inference_params_dict["hyena"] if inference_params_dict is not None else None
-        dyn = T == 1 and mha_c is not None and getattr(mha_c, "pos_tensor", None) is not None
-        if dyn and not hasattr(ops, "rope_append_decode"):   # (fallback path) one rotary table per decode step for all layers
+        mha_c, hy_c = (inference_params_dict["mha"], inference_params_dict["hyena"]) if inference_params_dict is not None else (None, None)
+        dyn = T == 1 and mha_c is not None and mha_c.pos_tensor is not None
+        if dyn and not ops.supports("rope_append_decode"):   # (fallback path) one rotary table per decode step for all layers
             mha_c._rot_dyn = self._rotary_dyn(mha_c.pos_tensor)
         try:
             self._run_blocks(h, B, T, mha_c, hy_c, mask)
@@ -851,8 +823,7 @@ class StripedHyena(nn.Module):
         block i has finished (StripedHyena.embeddings pools the streams it asked for there)."""
         stop = self.num_layers if stop is None else stop
         rs = None
-        taps = getattr(self, "block_taps", None)     # debugging / parity hook: residual stream entering every block
-        tap_idxs = getattr(self, "block_tap_idxs", None)   # ... or only the listed ones (index num_layers = the final stream)
+        taps, tap_idxs = self.block_taps, self.block_tap_idxs
         for i in range(stop):
             blk = self.blocks[i]
             if taps is not None and (tap_idxs is None or i in tap_idxs):
@@ -948,14 +919,11 @@ class StripedHyena(nn.Module):
             import warnings
             warnings.warn("padding_mask is ignored when inference_params_dict is given (as in upstream's stateful_forward)")
             padding_mask = None
-        if padding_mask is not None:
-            h = self.hidden_states(x, inference_params_dict, padding_mask)
-            return self._unembed_output(h, B, T), inference_params_dict
-        if T == 1 and inference_params_dict is not None and self._graph_eligible(inference_params_dict):
+        if T == 1 and inference_params_dict is not None and self._graph_eligible(inference_params_dict):     # (a cache: no mask, above)
             logits = self._graph_decode_step(x, inference_params_dict)
             if logits is not None:
                 return logits, inference_params_dict
-        h = self.hidden_states(x, inference_params_dict)
+        h = self.hidden_states(x, inference_params_dict, padding_mask)
         return self._unembed_output(h, B, T), inference_params_dict
 
     @torch.no_grad()
@@ -1017,7 +985,7 @@ class StripedHyena(nn.Module):
         import os
         if not self.decode_graph or os.environ.get("EVO_AMD_DECODE_GRAPH", "1") == "0":
             return False
-        if getattr(self.ops, "name", "") != "hip-gfx950" or getattr(self.ops, "timer", None) is not None:
+        if self.ops.name != "hip-gfx950" or self.ops.timer is not None:
             return False
         if not self.has_own_unembed:          # the captured step bakes in the engine's unembedding weight
             return False
@@ -1030,7 +998,7 @@ class StripedHyena(nn.Module):
         mha, hy = ipd["mha"], ipd["hyena"]
         B = x.shape[0]
         off = int(mha.seqlen_offset)
-        st = getattr(self, "_dgraph", None)
+        st = self._dgraph
         cap = min(mha.key_value_memory_dict[i].shape[1] for i in self.attn_layer_idxs) if self.attn_layer_idxs else 1 << 62
         # The captured graph is bound to the ADDRESSES of the KV, modal-state and FIR-state tensors.  `st` keeps strong
         # references to the cache objects and to every captured tensor and compares by identity: a later cache can then
@@ -1047,7 +1015,7 @@ class StripedHyena(nn.Module):
                     self._kv_buffer(mha, i, B, off + 1 + 4096, mha.key_value_memory_dict[i])
         try:
             if st is None:
-                warm = getattr(self, "_dgraph_warm", None)
+                warm = self._dgraph_warm
                 if warm is None or warm[0] is not mha or warm[1] is not hy or warm[2] != B:
                     self._dgraph_warm = (mha, hy, B)  # first step with these caches runs eagerly (warms M=B GEMMs)
                     return None
@@ -1082,7 +1050,7 @@ class StripedHyena(nn.Module):
             if st["next"] != off:
                 st["pos"].fill_(off)
             st["graph"].replay()
-            self.decode_graph_replays = getattr(self, "decode_graph_replays", 0) + 1
+            self.decode_graph_replays += 1
             st["next"] = off + 1
             return st["logits"].clone()
         except Exception as e:  # noqa: BLE001   capture is an optimisation: fall back to eager HIP launches
@@ -1096,8 +1064,7 @@ class StripedHyena(nn.Module):
         """Drop the captured decode step and the strong references it holds to the cache objects and to every KV / modal /
         FIR state tensor it was captured on (6.4 GB of KV cache after a 131k-context generation).  Called at the end of
         `Generator.generate` / `DecodePool.generate`; a later decode step on a live cache simply captures again."""
-        self._dgraph = None
-        self._dgraph_warm = None
+        self._dgraph = self._dgraph_warm = None
 
     # upstream names, kept for callers that reach for them
     def stateless_forward(self, x, padding_mask=None):

@@ -307,38 +307,26 @@ class SequenceParallelScorer:
 
     # ------------------------------------------------------------------ blocks
     def _hyena_block(self, blk, x2d, B, Tloc, Tl, T, rs=None):
-        """`rs`: 1 / (rms + eps) of every row of x2d from the epilogue of the dense layer that wrote it (round 6: the shards fold their
-        RMSNorm passes into the dense layers exactly as the single-GPU forward does, sh/model.py `_nf_ok`), or None: this block norms for
-        itself.  Returns the next block's `rs` (or None)."""
+        """`rs`: 1 / (rms + eps) of every row of x2d from the epilogue of the dense layer that wrote it (the shards fold their RMSNorm passes
+        into the dense layers exactly as the single-GPU forward does, sh/model.py `_nf_ok`), or None.  Returns the next block's `rs`."""
         m, ops = self.m, self.m.ops
         D, H = m.hidden_size, m.num_heads
         f = blk.filter
-        # The single-pass matrix-core operator (csrc/hyena_ct.hip, the kernel of the scoring path) serves both stages when the shards fit
-        # its launch contract: stage 1 = its state-only walk (end state from a zero carry), stage 2 = the full pass seeded with the
-        # carried state, on CHANNEL-MAJOR z^T written by the projection's dense layer (the weight as it is: no regrouped copy per rank;
-        # the halo rows travel in the REFERENCE's column order).  Other backends / shapes: the modal three-launch form (seg_state +
-        # carry_scan, then carry_add + apply) on token-major z.
+        # The channel-major route (sh/model.py) serves both stages when the shards fit the operator's contract: stage 1 = its state-only walk,
+        # stage 2 = the full pass seeded with the carried state.  Otherwise the modal form (seg_state + carry_scan, carry_add + apply).
         # The choice must be the SAME on every rank -- it is a function of (B, Tl, t_min = the last shard's length, world) only; the
         # launches run per row group (nb_max / nb_min rows), so the contract is evaluated on BOTH extremes.
         t_min = T - (self.world - 1) * Tl
-        G_ = max(1, min(self.row_groups, B))
-        nb_max, nb_min = (B + G_ - 1) // G_, max(1, B // G_)
-        ztm = getattr(ops, "hyena_mfma", False) and getattr(ops, "hyena_ct_flag", False) and hasattr(ops, "hyena_ct") \
-            and m._mfma_hyena_ok(nb_max, Tl) and m._mfma_hyena_ok(nb_min, t_min) and m._mfma_hyena_ok(nb_max, t_min) \
+        G = max(1, min(self.row_groups, B))
+        nb_max, nb_min = (B + G - 1) // G, max(1, B // G)
+        ztm = m._mfma_hyena_ok(nb_max, Tl) and m._mfma_hyena_ok(nb_min, t_min) and m._mfma_hyena_ok(nb_max, t_min) \
             and m._mfma_hyena_ok(nb_min, Tl) and ops.zt_shape_ok(B, Tl, 3 * D, D) and ops.zt_shape_ok(B, t_min, 3 * D, D) and t_min >= 2 \
             and m._table_ok(blk)                              # (the filter fits the operand tables: a property of the weights, the same on every rank)
         w_p, b_p = blk.projections.weight.data, (None if blk.projections.bias is None else blk.projections.bias.data)
         table = m._mfma_table(blk) if ztm else None
         # norms folded into the dense layers (a rank-local choice: no collective depends on it -- the last, shorter shard may differ)
         nf = ztm and m._nf_ok(B * Tloc, None)
-        stream_rows = nf and rs is not None and ops.zt_stream_rows_ok(B, Tloc)   # the projection reads the residual stream itself
-        xp = n1 = None
-        if stream_rows:
-            pass
-        elif ztm:
-            xp = ops.rmsnorm_rows(x2d, blk.pre_norm.scale, m.eps, B, Tloc)      # rows in z^T's position order
-        else:
-            n1 = ops.rmsnorm(x2d, None, blk.pre_norm.scale, m.eps)
+        n1, project = m._hyena_z(blk, x2d, rs, B, Tloc, zt=ztm, nf=nf)           # (the pre-norm pass, if this form has one: model.py)
         # (1) halo: the shard's last two rows go to the next rank.  They are projected on their own first (2B rows:
         #     the weight-streaming kernel) so that the send/recv flies under the big projection GEMM.
         halo, halo_w, tail = None, _Done(), None
@@ -354,13 +342,7 @@ class SequenceParallelScorer:
                 halo, halo_w = self._shift(tail)
             else:                                            # (last rank only, see check_geometry: nobody reads it)
                 halo, halo_w = self._shift(x2d.new_zeros(B, 2, 3 * D))
-        if stream_rows:
-            wp_f = m._folded(blk, "_wp_f", blk.projections.weight, blk.pre_norm.scale)
-            z = ops.linear_t_rs(x2d, rs, wp_f, b_p, w_p, blk.pre_norm.scale, m.eps, B, Tloc)
-        elif ztm:
-            z = ops.linear_t(xp, w_p, b_p, B, Tloc)          # z^T [blocks, 3 D, 256]
-        else:
-            z = ops.linear(n1, w_p, b_p).view(B, Tloc, 3 * D)
+        z = project()                                        # z^T [blocks, 3 D, 256] (ztm) or token-major [B, Tloc, 3 D]
         if tail is not None:
             # the two rows the next rank convolves with came out of the weight-streaming kernel, this rank's own copy of them
             # out of the tile GEMM (another summation order: up to one bf16 ulp apart) -- use the SENT values here too, so
@@ -376,7 +358,6 @@ class SequenceParallelScorer:
         if halo is not None:
             halo = halo.contiguous()
         # (2)-(5), pipelined over groups of batch rows
-        G = max(1, min(self.row_groups, B))
         bounds = [(g * B) // G for g in range(G + 1)]
         st1, ends, works = [None] * G, [None] * G, [None] * G
         for g in range(G):
@@ -411,16 +392,7 @@ class SequenceParallelScorer:
                 y[b0:b1] = yg
             else:
                 y = yg
-        if nf:
-            # output projection with the post-norm's statistic out of its epilogue, gated MLP with the factor in its epilogue, l3 with the
-            # NEXT block's statistic: no RMSNorm pass, no gate kernel (sh/model.py: _mixer_out_rs_ / _mlp_residual_rs_)
-            return m._mlp_residual_rs_(blk, x2d, m._mixer_out_rs_(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias))
-        if ztm:
-            ops.linear_residual_yblk_(x2d, y, blk.out_filter_dense.weight, bias=blk.out_filter_dense.bias)
-        else:
-            ops.linear_residual_(x2d, y.view(B * Tloc, D), blk.out_filter_dense.weight, bias=blk.out_filter_dense.bias)
-        m._mlp_residual_(blk, x2d, None)                     # (the bias went into the output projection's epilogue, as in model.py)
-        return None
+        return m._finish_block(blk, x2d, y if ztm else y.view(B * Tloc, D), blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf)
 
     def _attn_block(self, blk, x2d, B, Tloc, Tl, t0, T, rs=None):
         m, ops = self.m, self.m.ops
@@ -431,23 +403,17 @@ class SequenceParallelScorer:
             wqkv_f = m._folded(mha, "_wqkv_f", mha.Wqkv.weight, blk.pre_norm.scale)
             qkv = ops.linear_rs(x2d, rs, wqkv_f, mha.Wqkv.bias, mha.Wqkv.weight, blk.pre_norm.scale, m.eps).view(B, Tloc, 3, H, hd)
         else:
-            n1 = ops.rmsnorm(x2d, None, blk.pre_norm.scale, m.eps)
-            qkv = ops.linear(n1, mha.Wqkv.weight, mha.Wqkv.bias, mfma=True).view(B, Tloc, 3, H, hd)
+            qkv = ops.linear(ops.rmsnorm(x2d, None, blk.pre_norm.scale, m.eps), mha.Wqkv.weight, mha.Wqkv.bias, mfma=True).view(B, Tloc, 3, H, hd)
         cos, sin = m._rotary(t0, Tloc, x2d.device)
-        pre = bool(getattr(ops, "attn_prescale", False)) and hasattr(ops, "attn_q_scale")     # (sh/model.py _attn_block)
-        self._ak = {"prescaled": True} if pre else {}
-        ops.rope_(qkv, cos, sin, **({"q_scale": ops.attn_q_scale(hd)} if pre else {}))
+        pre = bool(ops.attn_prescale)                        # q carries softmax_scale * log2(e) out of the rotary kernel (sh/model.py _attn_block)
+        ops.rope_(qkv, cos, sin, q_scale=ops.attn_q_scale(hd) if pre else 1.0)
         if self.attn_mode != "allgather" and H % self.world == 0 and hasattr(self.comm, "all_to_all"):
-            a = self._attn_ulysses(qkv, B, Tloc, Tl, T)
+            a = self._attn_ulysses(qkv, B, Tloc, Tl, T, pre)
         else:
-            a = self._attn_allgather(qkv, B, Tloc, Tl, t0)
-        if nf:
-            return m._mlp_residual_rs_(blk, x2d, m._mixer_out_rs_(blk, x2d, a.view(B * Tloc, D), mha.out_proj.weight, mha.out_proj.bias))
-        ops.linear_residual_(x2d, a.view(B * Tloc, D), mha.out_proj.weight, mfma=True, bias=mha.out_proj.bias)
-        m._mlp_residual_(blk, x2d, None)
-        return None
+            a = self._attn_allgather(qkv, B, Tloc, Tl, t0, pre)
+        return m._finish_block(blk, x2d, a.view(B * Tloc, D), mha.out_proj.weight, mha.out_proj.bias, nf, mfma=True)
 
-    def _attn_ulysses(self, qkv, B, Tloc, Tl, T):
+    def _attn_ulysses(self, qkv, B, Tloc, Tl, T, prescaled=False):
         """Batch rows travel in `attn_row_groups` groups: ONE all-to-all and ONE attention launch (rows x H/R heads) per group
         and direction; group g+1's exchange flies under group g's attention, its return exchange under group g+1's."""
         ops, R = self.m.ops, self.world
@@ -475,7 +441,7 @@ class SequenceParallelScorer:
                 full = self._buf(("a2a_full", g), (nb, R, Tl, 3, Hr, hd), qkv)
                 full.copy_(recv.permute(1, 0, 2, 3, 4, 5))
                 full = full.view(nb, R * Tl, 3, Hr, hd)
-            o = ops.attention(full[:, :T, 0], full[:, :T, 1], full[:, :T, 2], 0, **self._ak)   # [nb, T, Hr, hd], this rank's heads
+            o = ops.attention(full[:, :T, 0], full[:, :T, 1], full[:, :T, 2], 0, prescaled=prescaled)   # [nb, T, Hr, hd], this rank's heads
             ret = self._buf(("a2a_ret", g), (R, nb, Tl, Hr, hd), o)
             if R * Tl == T:
                 ret.copy_(o.view(nb, R, Tl, Hr, hd).permute(1, 0, 2, 3, 4))
@@ -494,7 +460,7 @@ class SequenceParallelScorer:
             a[b0:b1].view(b1 - b0, Tloc, R, Hr, hd).copy_(recv[:, :, :Tloc].permute(1, 2, 0, 3, 4))
         return a
 
-    def _attn_allgather(self, qkv, B, Tloc, Tl, t0):
+    def _attn_allgather(self, qkv, B, Tloc, Tl, t0, prescaled=False):
         ops = self.m.ops
         H, hd = self.m.num_heads, self.m.head_dim
         # K,V per batch row, padded to Tl tokens, gathered asynchronously: [R, Tl, 2, H, hd] == tokens 0..R*Tl-1
@@ -514,7 +480,7 @@ class SequenceParallelScorer:
         for b in range(B):
             works[b].wait()
             kvg = bufs[b].view(self.world * Tl, 2, H, hd)[:n_keys]
-            a[b:b + 1] = ops.attention(qkv[b:b + 1, :, 0], kvg[None, :, 0], kvg[None, :, 1], t0, **self._ak)
+            a[b:b + 1] = ops.attention(qkv[b:b + 1, :, 0], kvg[None, :, 0], kvg[None, :, 1], t0, prescaled=prescaled)
         return a
 
     # ------------------------------------------------------------------ forward / scoring
@@ -570,7 +536,7 @@ class SequenceParallelScorer:
         tgt = ids_full[:, t0 + 1: t0 + 1 + n].to(h.device)
         hn = h if n == Tloc else h.view(B, Tloc, -1)[:, :n].reshape(B * n, -1).contiguous()
         emb = m.unembed.weight
-        if hasattr(ops, "unembed_logprob_ok") and ops.unembed_logprob_ok(hn, emb):
+        if ops.supports("unembed_logprob") and ops.unembed_logprob_ok(hn, emb):
             lp, _ = ops.unembed_logprob(hn, emb, tgt.reshape(-1))
         else:
             lp, _ = ops.logprob_entropy(ops.linear(hn, emb, None), tgt.reshape(-1))

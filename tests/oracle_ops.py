@@ -5,10 +5,13 @@ import math
 
 import torch
 
+from evo_amd.backend import Backend
 from oracle import stripedhyena_ref as R
 
 
-class OracleOps:
+class OracleOps(Backend):
+    """The required part of the backend contract (evo_amd/backend.py) and nothing else: every routing flag keeps its default (off), so
+    the host code takes the modal routes; q is never prescaled."""
     name = "oracle-cpu"
 
     def __init__(self, act=torch.float64):
@@ -57,11 +60,13 @@ class OracleOps:
         iir_state.copy_(ns.to(iir_state.dtype))
         return self._o(y)
 
-    def rope_(self, qkv, cos, sin):
+    def rope_(self, qkv, cos, sin, q_scale=1.0):
+        assert q_scale == 1.0
         qkv.copy_(self._o(R.op_rope(qkv, cos, sin)))
         return qkv
 
-    def attention(self, q, k, v, q_pos0):
+    def attention(self, q, k, v, q_pos0, prescaled=False):
+        assert not prescaled
         return self._o(R.op_attention(q, k, v, q_pos0))
 
     def norm_linear(self, x, scale, eps, w, b=None, mfma=False):
@@ -92,7 +97,8 @@ class OracleOps:
         y, _ = R.op_hyena(z, fir_w, fir_b, poles, residues, dskip, n_heads, z_halo, s0)
         return self._o(y)
 
-    def attention_decode(self, q, k, v, pos=None, n_splits=None):
+    def attention_decode(self, q, k, v, pos=None, n_splits=None, prescaled=False):
+        assert not prescaled
         if pos is None or pos.numel() == 1:
             Tk = k.shape[1] if pos is None else int(pos.item()) + 1
             return self._o(R.op_attention(q, k[:, :Tk], v[:, :Tk], Tk - 1))

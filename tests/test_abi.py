@@ -84,8 +84,8 @@ def test_c_abi_reads_no_environment():
 
 
 def test_binding_refuses_misaligned_addresses():
-    """include/evo_mi355x.h, Conventions: bf16 / f32 / c64 data 16-byte aligned and no more, integer vectors at their element's alignment.  HipOps._need and the hand-rolled checks of
-    attention / attention_decode / rope_append_decode / pool_rows go through this one helper, which takes an address: no GPU needed."""
+    """include/evo_mi355x.h, Conventions: bf16 / f32 / c64 data 16-byte aligned and no more, integer vectors at their element's alignment.  HipOps._need, the attention launches' operand check
+    (_need_strided) and the hand-rolled checks of attention_decode / rope_append_decode / pool_rows go through this one helper, which takes an address: no GPU needed."""
     chk = evo_ops.HipOps._check_address
     for addr in (0, 16, 0x7f0000000010, 0x7f0000000200, 48):                                    # 16 (mod 32) is legal: nothing more is asked
         chk(addr, "x")
@@ -98,8 +98,10 @@ def test_binding_refuses_misaligned_addresses():
     al = evo_ops.HipOps._align_of                                                                # floating-point data: 16; integer vectors: the element
     assert [al(d) for d in (torch.bfloat16, torch.float32, torch.complex64, torch.int64, torch.int32, torch.uint8)] == [16, 16, 16, 8, 4, 1]
     import inspect
-    for name in ("_need", "attention", "attention_decode", "rope_append_decode", "pool_rows"):   # the check is wired into every place the issue names
+    for name in ("_need", "_need_strided", "attention_decode", "rope_append_decode", "pool_rows"):   # the check is wired into every place the issue names
         assert "_check_address(" in inspect.getsource(getattr(evo_ops.HipOps, name)), name
+    for name in ("attention", "attention_prefix", "attention_decode", "attention_decode_prefix"):   # (their q / k / v operands: one helper)
+        assert "self._need_strided(" in inspect.getsource(getattr(evo_ops.HipOps, name)), name
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")

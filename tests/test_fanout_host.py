@@ -37,7 +37,9 @@ class FanoutOracleOps(OracleOps):
         super().__init__(act)
         self.prefix_calls = 0
 
-    def attention_decode_prefix(self, q, k, v, own_pos, k_store, v_store, pre_row, pre_len, n_splits=None, n_pre_splits=None):
+    def attention_decode_prefix(self, q, k, v, own_pos, k_store, v_store, pre_row, pre_len, n_splits=None, n_pre_splits=None,
+                                prescaled=False):
+        assert not prescaled
         self.prefix_calls += 1
         rows = []
         for b in range(q.shape[0]):
