@@ -7,7 +7,11 @@
 // suffix sum here, so the survivors are a prefix) and the CDF walk.  Sums are fp32 in a FIXED order (8 sequential terms per lane,
 // then a Hillis-Steele scan / butterfly over the lanes), so a row's token is bit-identical from run to run.  No float atomics.
 // The random number of a row is Philox4x32-10 keyed by the seed, counter = (stream id, draw count): a function of the sample and
-// the draw, not of the slot or the step.  Entry point and contract: include/evo_mi355x.h.
+// the draw, not of the slot or the step.  Entry points and contracts: include/evo_mi355x.h.
+// Two kernels share the draw (sample_draw_row): sample_rows_kernel (evo_sample_rows_f32) records it and advances the count;
+// sample_rows_ctl_kernel (evo_sample_rows_ctl_f32) also decides that the row's job is over -- stop token,
+// in-frame stop pattern at the end of the recorded tokens, own length limit -- clears the row's `active` byte and writes `length` /
+// `finish`: lane 0, plain stores, a look-back of at most 7 cells into the row's own token history.
 #include "common.h"
 #include "../../include/evo_mi355x.h"
 
@@ -45,17 +49,16 @@ __device__ __forceinline__ int sample_wave_sum_i(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(64) void sample_rows_kernel(const void* __restrict__ logits, int logits_f32, int64_t ld,
-                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
-                                                         const float* __restrict__ temperature, const uint8_t* __restrict__ allow,
-                                                         uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ stream_id,
-                                                         int64_t* count, const uint8_t* __restrict__ active, int64_t* ids_out,
-                                                         float* logprob_out, int64_t* hist_ids, float* hist_logits, int64_t hist_len) {
-    __shared__ uint64_t keys[EVO_SAMPLE_V];
-    __shared__ float raw[EVO_SAMPLE_V];
+// The draw of one row by one wave, shared by both kernels below: token and its log-probability under the unfiltered row (every lane
+// returns the same pair).  With `hist_row` the row's 512 f32 logits are also stored there.  `keys` / `raw`: the workgroup's LDS.
+struct SampleDraw { int tok; float logprob; };
+
+__device__ __forceinline__ SampleDraw sample_draw_row(const void* __restrict__ logits, int logits_f32, int64_t ld, int64_t s,
+                                                      const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                      const float* __restrict__ temperature, const uint8_t* __restrict__ allow,
+                                                      uint32_t seed_lo, uint32_t seed_hi, int64_t sid, int64_t cnt, float* hist_row,
+                                                      uint64_t* keys, float* raw) {
     const int lane = threadIdx.x;
-    const int64_t s = blockIdx.x;
-    if (active && !active[s]) return;                                 // (the whole wave: before any barrier)
 
     // ---- the row: ids lane * 8 .. lane * 8 + 7
     float x[8];
@@ -69,11 +72,8 @@ __global__ __launch_bounds__(64) void sample_rows_kernel(const void* __restrict_
         x[0] = bf_lo(v.x); x[1] = bf_hi(v.x); x[2] = bf_lo(v.y); x[3] = bf_hi(v.y);
         x[4] = bf_lo(v.z); x[5] = bf_hi(v.z); x[6] = bf_lo(v.w); x[7] = bf_hi(v.w);
     }
-    const int64_t cnt = count ? count[s] : 0;
-    const int64_t sid = stream_id ? stream_id[s] : s;
-    const bool hist_ok = cnt >= 0 && cnt < hist_len;                  // (hist_len = 0 without history)
-    if (hist_logits && hist_ok) {
-        f32x4_t* h = (f32x4_t*)(hist_logits + (s * hist_len + cnt) * EVO_SAMPLE_V) + 2 * lane;
+    if (hist_row) {
+        f32x4_t* h = (f32x4_t*)hist_row + 2 * lane;
         h[0] = f32x4_t{x[0], x[1], x[2], x[3]};
         h[1] = f32x4_t{x[4], x[5], x[6], x[7]};
     }
@@ -185,11 +185,98 @@ __global__ __launch_bounds__(64) void sample_rows_kernel(const void* __restrict_
         pos = min(sample_wave_sum_i(c), n_keep - 1);                  // first position whose inclusive CDF exceeds u
     }
     const int tok = EVO_SAMPLE_V - 1 - (int)(uint32_t)keys[pos];      // 0 <= pos < 512, 0 <= tok < 512
-    if (lane == 0) {
-        ids_out[s] = tok;
-        logprob_out[s] = raw[tok] - lse;
-        if (hist_ids && hist_ok) hist_ids[s * hist_len + cnt] = tok;
+    return SampleDraw{tok, raw[tok] - lse};
+}
+
+__global__ __launch_bounds__(64) void sample_rows_kernel(const void* __restrict__ logits, int logits_f32, int64_t ld,
+                                                         const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                         const float* __restrict__ temperature, const uint8_t* __restrict__ allow,
+                                                         uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ stream_id,
+                                                         int64_t* count, const uint8_t* __restrict__ active, int64_t* ids_out,
+                                                         float* logprob_out, int64_t* hist_ids, float* hist_logits, int64_t hist_len) {
+    __shared__ uint64_t keys[EVO_SAMPLE_V];
+    __shared__ float raw[EVO_SAMPLE_V];
+    const int64_t s = blockIdx.x;
+    if (active && !active[s]) return;                                 // (the whole wave: before any barrier)
+    const int64_t cnt = count ? count[s] : 0;
+    const int64_t sid = stream_id ? stream_id[s] : s;
+    const bool hist_ok = cnt >= 0 && cnt < hist_len;                  // (hist_len = 0 without history)
+    const SampleDraw d = sample_draw_row(logits, logits_f32, ld, s, top_k, top_p, temperature, allow, seed_lo, seed_hi, sid, cnt,
+                                         (hist_logits && hist_ok) ? hist_logits + (s * hist_len + cnt) * EVO_SAMPLE_V : nullptr, keys, raw);
+    if (threadIdx.x == 0) {
+        ids_out[s] = d.tok;
+        logprob_out[s] = d.logprob;
+        if (hist_ids && hist_ok) hist_ids[s * hist_len + cnt] = d.tok;
         if (count) count[s] = cnt + 1;
+    }
+}
+
+// The same draw with job control (specification: evo_amd/sh/sample.py finish_reason / sample_ctl): the row decides
+// by itself that its job is over -- a stop token, an in-frame stop pattern at the end of its recorded tokens, or its own length limit --
+// and clears its `active` byte, so the launches that follow skip it and the host learns of it from `length` whenever it cares to look.
+// The patterns travel in the launch's arguments (at most 8 x 8 ids): no pattern memory on the device, fixed in a captured graph.
+struct SampleStops {
+    int32_t seq[EVO_SAMPLE_MAX_STOP_SEQ][EVO_SAMPLE_MAX_STOP_LEN];
+    int32_t len[EVO_SAMPLE_MAX_STOP_SEQ];
+    int32_t n_seq;
+};
+
+__global__ __launch_bounds__(64) void sample_rows_ctl_kernel(const void* __restrict__ logits, int logits_f32, int64_t ld,
+                                                             const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
+                                                             const float* __restrict__ temperature, const uint8_t* __restrict__ allow,
+                                                             uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ stream_id,
+                                                             int64_t* count, uint8_t* active, int64_t* ids_out, float* logprob_out,
+                                                             int64_t* hist_ids, float* hist_logits, float* hist_logprob, int64_t hist_len,
+                                                             const int64_t* __restrict__ limit, const uint8_t* __restrict__ stop_mask,
+                                                             const SampleStops stops, int64_t stop_frame, int64_t* length,
+                                                             uint8_t* finish) {
+    __shared__ uint64_t keys[EVO_SAMPLE_V];
+    __shared__ float raw[EVO_SAMPLE_V];
+    const int64_t s = blockIdx.x;
+    if (!active[s]) return;                                           // (the whole wave: before any barrier)
+    const int64_t cnt = count[s];
+    const int64_t lim = limit[s];
+    // nothing left to draw, or no cell left to record it in: the job ends here, by length, with no read of the logits or the history
+    if (cnt < 0 || cnt >= lim || (hist_len > 0 && cnt >= hist_len)) {
+        if (threadIdx.x == 0) {
+            active[s] = 0;
+            length[s] = cnt;
+            finish[s] = 3;
+        }
+        return;
+    }
+    const int64_t sid = stream_id ? stream_id[s] : s;
+    const SampleDraw d = sample_draw_row(logits, logits_f32, ld, s, top_k, top_p, temperature, allow, seed_lo, seed_hi, sid, cnt,
+                                         hist_logits ? hist_logits + (s * hist_len + cnt) * EVO_SAMPLE_V : nullptr, keys, raw);
+    if (threadIdx.x == 0) {
+        const int tok = d.tok;
+        const int64_t n = cnt + 1;                                    // tokens recorded once this one is
+        ids_out[s] = tok;
+        logprob_out[s] = d.logprob;
+        if (hist_ids) hist_ids[s * hist_len + cnt] = tok;             // (0 <= cnt < hist_len: checked above)
+        if (hist_logprob) hist_logprob[s * hist_len + cnt] = d.logprob;
+        count[s] = n;
+        int reason = 0;
+        if (stop_mask && ((stop_mask[tok >> 3] >> (tok & 7)) & 1u)) {
+            reason = 1;
+        } else if (stops.n_seq > 0 && n % stop_frame == 0) {
+            // the last `len` tokens against pattern q, newest first: the new token from its register, the others from the cells
+            // cnt - 1 ... cnt - len + 1 >= 0 of this row, which earlier launches on this stream wrote; a pattern longer than n reads nothing
+            const int64_t* h = hist_ids + s * hist_len;
+            for (int q = 0; q < stops.n_seq && !reason; ++q) {
+                const int len = stops.len[q];
+                if (len > n) continue;
+                bool same = stops.seq[q][len - 1] == tok;
+                for (int i = 1; i < len && same; ++i) same = h[cnt - i] == (int64_t)stops.seq[q][len - 1 - i];
+                if (same) reason = 2;
+            }
+        }
+        if (!reason && n >= lim) reason = 3;
+        if (reason) {
+            active[s] = 0;
+            length[s] = n;
+            finish[s] = (uint8_t)reason;
+        }
     }
 }
 
@@ -205,5 +292,39 @@ extern "C" int evo_sample_rows_f32(const void* logits, int64_t logits_f32, int64
     hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, logits, (int)(logits_f32 != 0), ld, top_k,
                        top_p, temperature, (const uint8_t*)allow, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, count, active,
                        ids_out, logprob_out, hist_ids, hist_logits, hist_len);
+    return evo_launch_status();
+}
+
+extern "C" int evo_sample_rows_ctl_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,
+                                       const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
+                                       uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
+                                       float* hist_logprob, int64_t hist_len, const int64_t* limit, const void* stop_mask,
+                                       const int32_t* stop_seq, const int32_t* stop_seq_len, int64_t n_seq, int64_t stop_frame,
+                                       int64_t* length, uint8_t* finish, int64_t S, int64_t V, void* stream) {
+    if (!logits || !top_k || !top_p || !temperature || !ids_out || !logprob_out) return -1;
+    if (!count || !active || !limit || !length || !finish) return -1;
+    if (S < 1 || S > 0x7fffffff || V != EVO_SAMPLE_V || ld < V || ld % 8 != 0) return -1;
+    if (((uintptr_t)logits & 15) || ((uintptr_t)hist_logits & 15)) return -1;
+    const bool any_hist = hist_ids || hist_logits || hist_logprob;
+    if (any_hist && hist_len < 1) return -1;
+    if (!any_hist) hist_len = 0;
+    if (stop_frame < 1 || n_seq < 0 || n_seq > EVO_SAMPLE_MAX_STOP_SEQ) return -1;
+    if (n_seq > 0 && (!stop_seq || !stop_seq_len || !hist_ids)) return -1;
+    SampleStops stops;
+    for (int q = 0; q < EVO_SAMPLE_MAX_STOP_SEQ; ++q) {
+        stops.len[q] = 0;
+        for (int i = 0; i < EVO_SAMPLE_MAX_STOP_LEN; ++i) stops.seq[q][i] = -1;
+    }
+    stops.n_seq = (int32_t)n_seq;
+    for (int q = 0; q < n_seq; ++q) {                                 // host arrays: read here, before the launch
+        const int32_t len = stop_seq_len[q];
+        if (len < 1 || len > EVO_SAMPLE_MAX_STOP_LEN) return -1;
+        stops.len[q] = len;
+        for (int i = 0; i < len; ++i) stops.seq[q][i] = stop_seq[q * EVO_SAMPLE_MAX_STOP_LEN + i];
+    }
+    hipLaunchKernelGGL(sample_rows_ctl_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, logits, (int)(logits_f32 != 0), ld,
+                       top_k, top_p, temperature, (const uint8_t*)allow, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, count, active,
+                       ids_out, logprob_out, hist_ids, hist_logits, hist_logprob, hist_len, limit, (const uint8_t*)stop_mask, stops,
+                       stop_frame, length, finish);
     return evo_launch_status();
 }

@@ -66,10 +66,12 @@ _SIGNATURES = {
     "evo_rope_append_decode_at_bf16": ([_PTR] * 4 + [_F32] + [_I64] * 7 + [_F32, _PTR, _PTR], _c.c_int),
     "evo_hyena_state_at_zt": ([_PTR] * 8 + [_I64] * 8 + [_PTR], _c.c_int),
     "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
+    "evo_sample_rows_ctl_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 8 + [_I64] + [_PTR] * 4 + [_I64, _I64, _PTR, _PTR,
+                                                                                                                         _I64, _I64, _PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 16        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 17        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
                         # `prefix_streams` counter is computed from it on the host)
 
@@ -1272,6 +1274,81 @@ class HipOps(Backend):
                                                 top_p.data_ptr(), temperature.data_ptr(), _ptr(allow), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                 _ptr(stream), _ptr(count), _ptr(active), ids_out.data_ptr(), logprob_out.data_ptr(),
                                                 _ptr(hist_ids), _ptr(hist_logits), hist_len, S, V, _stream()), "evo_sample_rows_f32")
+        return ids_out, logprob_out
+
+    @staticmethod
+    def pack_stop_sequences(patterns) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Stop patterns as id lists (at most 8 of 1 to 8 tokens) -> (int32 [n_seq, 8], int32 [n_seq]) HOST tensors: `sample_rows_ctl`
+        hands them to the launch by value."""
+        from .sh.sample import pack_stop_sequences
+        return pack_stop_sequences(patterns)
+
+    def sample_rows_ctl(self, logits: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, temperature: torch.Tensor, seed: int,
+                        count: torch.Tensor, active: torch.Tensor, limit: torch.Tensor, length: torch.Tensor, finish: torch.Tensor,
+                        stream: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                        ids_out: Optional[torch.Tensor] = None, logprob_out: Optional[torch.Tensor] = None,
+                        hist_ids: Optional[torch.Tensor] = None, hist_logits: Optional[torch.Tensor] = None,
+                        hist_logprob: Optional[torch.Tensor] = None, stop_mask: Optional[torch.Tensor] = None, stop_seq=None,
+                        stop_frame: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`sample_rows` with job control (csrc/sample.hip; specification: sh/sample.py finish_reason / sample_ctl): the same draw, then the
+        row ends its own job -- a token of `stop_mask` (64 bytes of `pack_allow_mask`), an in-frame stop pattern (`stop_seq`: the pair of
+        `pack_stop_sequences`) at the end of its recorded tokens, or `limit` [S] int64 reached -- by clearing its byte of `active` [S] bool
+        and writing `length` [S] int64 and `finish` [S] uint8 (1 stop token, 2 stop sequence, 3 length).  hist_ids [S, L] int64,
+        hist_logits [S, L, 512] f32 and hist_logprob [S, L] f32 are each optional.  One launch, nothing read back: capturable."""
+        if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2 or not logits.is_cuda:
+            raise RuntimeError("sample_rows_ctl: logits must be a [S, 512] bf16 or f32 device matrix")
+        S, V = logits.shape
+        if logits.stride(1) != 1 or logits.stride(0) % 8 or logits.stride(0) < V or logits.data_ptr() % 16:
+            logits = logits.contiguous()
+        dev = logits.device
+
+        def need(t, dtype, shape, what, required=False):
+            if t is None and not required:
+                return
+            if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f"sample_rows_ctl: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        need(top_k, torch.int32, (S,), "top_k", True)
+        need(top_p, torch.float32, (S,), "top_p", True)
+        need(temperature, torch.float32, (S,), "temperature", True)
+        need(stream, torch.int64, (S,), "stream")
+        need(count, torch.int64, (S,), "count", True)
+        need(active, torch.bool, (S,), "active", True)
+        need(limit, torch.int64, (S,), "limit", True)
+        need(length, torch.int64, (S,), "length", True)
+        need(finish, torch.uint8, (S,), "finish", True)
+        need(allow, torch.uint8, (64,), "allow")
+        need(stop_mask, torch.uint8, (64,), "stop_mask")
+        if ids_out is None:
+            ids_out = torch.empty(S, dtype=torch.int64, device=dev)
+        if logprob_out is None:
+            logprob_out = torch.empty(S, dtype=torch.float32, device=dev)
+        need(ids_out.view(-1), torch.int64, (S,), "ids_out")
+        need(logprob_out, torch.float32, (S,), "logprob_out")
+        hist_len = 0
+        for h in (hist_ids, hist_logits, hist_logprob):
+            if h is not None:
+                hist_len = int(h.shape[1])
+        if hist_len:
+            need(hist_ids, torch.int64, (S, hist_len), "hist_ids")
+            need(hist_logits, torch.float32, (S, hist_len, V), "hist_logits")
+            need(hist_logprob, torch.float32, (S, hist_len), "hist_logprob")
+        seq_ptr = len_ptr = None
+        n_seq = 0
+        if stop_seq is not None and len(stop_seq[1]):
+            seq, seq_len = stop_seq
+            if seq.dtype != torch.int32 or seq_len.dtype != torch.int32 or seq.is_cuda or seq_len.is_cuda or not seq.is_contiguous() \
+                    or tuple(seq.shape) != (seq_len.numel(), 8):
+                raise RuntimeError("sample_rows_ctl: stop_seq must be the host pair of pack_stop_sequences")
+            if hist_ids is None:
+                raise RuntimeError("sample_rows_ctl: stop sequences need hist_ids")
+            n_seq, seq_ptr, len_ptr = int(seq_len.numel()), seq.data_ptr(), seq_len.data_ptr()
+        with self._t("sample_rows_ctl"):
+            _check(self.lib.evo_sample_rows_ctl_f32(
+                logits.data_ptr(), int(logits.dtype == torch.float32), logits.stride(0), top_k.data_ptr(), top_p.data_ptr(),
+                temperature.data_ptr(), _ptr(allow), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(stream), count.data_ptr(), active.data_ptr(),
+                ids_out.data_ptr(), logprob_out.data_ptr(), _ptr(hist_ids), _ptr(hist_logits), _ptr(hist_logprob), hist_len,
+                limit.data_ptr(), _ptr(stop_mask), seq_ptr, len_ptr, n_seq, int(stop_frame), length.data_ptr(), finish.data_ptr(), S, V,
+                _stream()), "evo_sample_rows_ctl_f32")
         return ids_out, logprob_out
 
 

@@ -30,6 +30,12 @@ many keys that row holds and the slot's own index are device vectors, so the cap
 `prefill_batch=N` > 1 (opt-in): when a prompt needs a prefill, the distinct prompts among the jobs the idle slots are
 about to take -- at most N, and at most `prefill_max_tokens` padded positions -- are prefilled in ONE forward of the right-padded batch
 (`StripedHyena.prefill_ragged`); each slot is installed from its prompt's row of that batch.  With the default 1 nothing changes by a bit.
+
+Jobs that end on their own (opt-in): with `stop_tokens`, `stop_sequences` / `stop_frame`, one `n_tokens` per prompt or
+`return_logits=False`, `generate` runs on the sampler launch `evo_sample_rows_ctl_f32`: the row itself ends its job (stop token, in-frame
+stop pattern, own limit) and goes inactive on the device.  The host knows the step by which a slot must have ended (its limit) and, with a
+stop rule, reads one [S] vector of lengths every `poll_every` steps to learn who ended sooner; it fetches rows [:length] of the finished
+slots' histories (tokens, log-probabilities, logits only when asked for), releases their store rows and re-fills them.
 """
 from __future__ import annotations
 
@@ -41,15 +47,18 @@ import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
 from .sh.cache import PromptStore
-from .sh.sample import allowed_mask, sample
+from .sh.sample import FINISH_LENGTH, FINISH_NAMES, FINISH_STOP_TOKEN, allowed_mask, sample, stop_patterns
 
 
 class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
-                 prefill_max_tokens: int = 32768):
+                 prefill_max_tokens: int = 32768, poll_every: int = 8):
         self.model = model
+        self.poll_every = int(poll_every)
+        if self.poll_every < 1:
+            raise ValueError("poll_every must be >= 1")
         self.prefill_batch, self.prefill_max_tokens = int(prefill_batch), int(prefill_max_tokens)
         if self.prefill_batch < 1:
             raise ValueError("prefill_batch must be >= 1")
@@ -81,7 +90,9 @@ class DecodePool:
         self.device_sampler = seed is not None or allowed_tokens is not None
         self.seed = 0 if seed is None else int(seed)
         self.allow_mask = None if allowed_tokens is None else allowed_mask(tokenizer, allowed_tokens)
-        self.hist_ids = self.hist_logits = None
+        self.hist_ids = self.hist_logits = self.hist_logprob = None
+        self._ctl = None                                             # job control: the stop rule of the running generate()
+        self._graph_key = None                                       # what the captured step's sampler launch was captured with
 
     # ------------------------------------------------------------------ cache rows
     def _allocate(self, capacity: int) -> None:
@@ -127,14 +138,20 @@ class DecodePool:
         self.s_active = torch.zeros(S, dtype=torch.bool, device=dev)
         self.s_logprob = torch.zeros(S, dtype=torch.float32, device=dev)
         self.s_allow = None if self.allow_mask is None else m.ops.pack_allow_mask(self.allow_mask, dev)
-        self.hist_ids = self.hist_logits = None
+        self.s_stop_mask = torch.zeros(64, dtype=torch.uint8, device=dev)     # the stop tokens of the running rule: a captured launch keeps this address
+        self.hist_ids = self.hist_logits = self.hist_logprob = None
+        # job control: limit in, length (-1 while the job runs) and finish out
+        self.s_limit = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.s_length = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        self.s_finish = torch.zeros(S, dtype=torch.uint8, device=dev)
 
-    def _allocate_shared(self, p_max: int, n_tokens: int, n_sample_per_prompt: int) -> None:
+    def _allocate_shared(self, p_max: int, n_tokens: int, n_sample_per_prompt: int, rows: Optional[int] = None) -> None:
         """share_prompt_kv: own caches of `n_tokens` rows per slot and a store of R rows of the longest prompt's length.  Jobs run in
         order and have one length, so the live jobs are a window of at most S consecutive jobs: they touch at most ceil(S / n) + 1
-        prompts (and never more than S)."""
+        prompts (and never more than S).  `rows` (job control): jobs of unequal length break the window -- job 0 may outlive jobs 1 ... 40 --
+        so the caller asks for min(S, number of prompts) rows: one per live slot, or one per prompt."""
         m, S, dev = self.model, self.n_slots, self.device
-        R = min(S, -(-S // int(n_sample_per_prompt)) + 1)
+        R = min(S, -(-S // int(n_sample_per_prompt)) + 1) if rows is None else int(rows)
         st = self.store
         if st is not None and self.capacity >= n_tokens and self.store_cap >= p_max and len(self.store_refs) >= R:
             self._store_prompt = [None] * len(self.store_refs)       # prompt indices belong to one job list
@@ -208,9 +225,10 @@ class DecodePool:
 
     def _allocate_history(self, n_tokens: int) -> None:
         """Device-resident record of every slot's current job: tokens [S, L] and the f32 logits that produced them [S, L, V]."""
-        if self.hist_ids is not None and self.hist_ids.shape[1] >= n_tokens:
+        if self.hist_ids is not None and self.hist_logits is not None and self.hist_ids.shape[1] >= n_tokens:
             return
         S, dev = self.n_slots, self.device
+        self.hist_logprob = None
         self.hist_ids = torch.zeros(S, n_tokens, dtype=torch.int64, device=dev)
         self.hist_logits = torch.zeros(S, n_tokens, self.model.vocab_size, dtype=torch.float32, device=dev)
         self._graph = None
@@ -305,8 +323,22 @@ class DecodePool:
                                    ids_out=self.ids[rows], logprob_out=self.s_logprob[rows], hist_ids=self.hist_ids[rows],
                                    hist_logits=self.hist_logits[rows])
 
+    def _sample_rows_ctl(self, logits: torch.Tensor, rows: slice) -> None:
+        """The sampler launch of the job-control path: the same draw, and a row that ends its job clears its own `s_active`."""
+        c = self._ctl
+        self.model.ops.sample_rows_ctl(logits, self.s_top_k[rows], self.s_top_p[rows], self.s_temperature[rows], self.seed,
+                                       count=self.s_count[rows], active=self.s_active[rows], limit=self.s_limit[rows],
+                                       length=self.s_length[rows], finish=self.s_finish[rows], stream=self.s_stream[rows],
+                                       allow=self.s_allow, ids_out=self.ids[rows], logprob_out=self.s_logprob[rows],
+                                       hist_ids=self.hist_ids[rows], hist_logits=None if self.hist_logits is None else self.hist_logits[rows],
+                                       hist_logprob=self.hist_logprob[rows], stop_mask=c["stop_mask"], stop_seq=c["stop_seq"],
+                                       stop_frame=c["stop_frame"])
+
     def _step_sample_eager(self) -> None:
-        self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
+        if self._ctl is not None:
+            self._sample_rows_ctl(self._step_eager(), slice(0, self.n_slots))
+        else:
+            self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
         self._advance()
 
     def _step_sampled(self) -> None:
@@ -326,18 +358,49 @@ class DecodePool:
                 return None
             self._graph[0].replay()
 
+    def _prefill_for(self, pi: int, jobs, slot_job, encoded, cached_prefill: Dict[int, tuple]) -> None:
+        """Prompt `pi` needs a prefill: it, and with `prefill_batch` > 1 the prompts admitted with it, land in `cached_prefill` as
+        (last-position logits [V] f32, caches, row of those caches)."""
+        cached_prefill.clear()                               # keep one prefill's caches alive at a time (every earlier prompt's copies are installed)
+        group = [pi]
+        if self.prefill_batch > 1:
+            # the jobs the idle slots (this one included) will take: copies of a prompt are adjacent, so none of them has a prefill yet
+            n_idle = sum(1 for q in slot_job if q is None)
+            group = self._prefill_group([pi] + [jobs[k][1] for k in range(min(n_idle - 1, len(jobs)))],
+                                        [e.shape[1] for e in encoded])
+            self.stats["prefill_prompts"] += len(group)
+        if len(group) == 1:
+            cached_prefill[pi] = self._prefill(encoded[pi]) + (0,)
+        else:
+            lg, tmp_b = self._prefill_ragged(encoded, group)
+            for r, q in enumerate(group):
+                cached_prefill[q] = (lg[r], tmp_b, r)
+
     # ------------------------------------------------------------------ the job
-    def generate(self, prompts: Sequence[str], n_tokens: int = 1000, n_sample_per_prompt: int = 1,
+    def generate(self, prompts: Sequence[str], n_tokens=1000, n_sample_per_prompt: int = 1,
                  prepend_bos: bool = False, sampling: Optional[Sequence[Optional[dict]]] = None,
-                 streams: Optional[Sequence[int]] = None) \
+                 streams: Optional[Sequence[int]] = None, stop_tokens=None, stop_sequences=None, stop_frame: int = 1,
+                 return_logits: bool = True) \
             -> Tuple[List[str], List[float], List[int]]:
         """Returns (generated strings, mean log-likelihood scores, index of the prompt each came from), in job
         order: prompt 0's samples first.  `sampling` (device sampler only): one dict of `top_k` / `top_p` / `temperature`
         per prompt (or None) overriding the pool's own settings for that prompt's samples; `streams`: the random-stream id of
-        every output (default: its index, `prompt index * n_sample_per_prompt + copy`), for a job that is a re-ordered part of another."""
+        every output (default: its index, `prompt index * n_sample_per_prompt + copy`), for a job that is a re-ordered part of another.
+
+        Job control (any of these moves the sampler onto the device, seed 0 without a seed): `n_tokens` as a sequence
+        is one length limit per prompt; `stop_tokens` (ids, or a string through the tokenizer) end a job and are trimmed from its string;
+        `stop_sequences` (strings or id lists, at most 8 of 1 to 8 tokens) end it when they end at a multiple of `stop_frame` tokens,
+        counted from the first generated one, and stay in its string; `return_logits=False` keeps no logits at all.  The run leaves
+        `last_lengths`, `last_finish` ("stop_token" | "stop_sequence" | "length"), `last_logprobs`; `last_ids` holds -1 beyond a job's length."""
+        if (not isinstance(n_tokens, (int, np.integer)) or stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1
+                or not return_logits):
+            return self._generate_ctl(prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
+                                      stop_frame, return_logits)
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         if hasattr(m, "eval"):
             m.eval()
+        if self._graph_key is not None:                              # the captured step ends with the job-control launch: capture anew
+            self._graph, self._graph_key, self._ctl = None, None, None
         n_tokens = int(n_tokens)
         if n_tokens < 1 or int(n_sample_per_prompt) < 1:
             raise ValueError("n_tokens and n_sample_per_prompt must be >= 1")
@@ -373,20 +436,7 @@ class DecodePool:
         def fill(slot: int) -> None:
             j, pi = jobs.popleft()
             if pi not in cached_prefill:
-                cached_prefill.clear()                               # keep one prefill's caches alive at a time (every earlier prompt's copies are installed)
-                group = [pi]
-                if self.prefill_batch > 1:
-                    # the jobs the idle slots (this one included) will take: copies of a prompt are adjacent, so none of them has a prefill yet
-                    n_idle = sum(1 for q in slot_job if q is None)
-                    group = self._prefill_group([pi] + [jobs[k][1] for k in range(min(n_idle - 1, len(jobs)))],
-                                                [e.shape[1] for e in encoded])
-                    self.stats["prefill_prompts"] += len(group)
-                if len(group) == 1:
-                    cached_prefill[pi] = self._prefill(encoded[pi]) + (0,)
-                else:
-                    lg, tmp_b = self._prefill_ragged(encoded, group)
-                    for r, q in enumerate(group):
-                        cached_prefill[q] = (lg[r], tmp_b, r)
+                self._prefill_for(pi, jobs, slot_job, encoded, cached_prefill)
             last_logits, tmp, row = cached_prefill[pi]
             P = encoded[pi].shape[1]
             kw = {"row": row} if row else {}                         # (row 0 of a B = 1 prefill: the call as it always was)
@@ -473,6 +523,8 @@ class DecodePool:
                 self._release_shared(ended)
 
         self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
+        for name in ("last_lengths", "last_finish", "last_logprobs"):    # (an earlier job-control run's: they would describe that run)
+            self.__dict__.pop(name, None)
         seqs = list(tok.detokenize_batch(out_ids))
         lp = logits_to_logprobs(out_logits, out_ids).float().numpy()   # the reference's shifted pairing
         scores = [float(np.mean(lp[j])) for j in range(n_jobs)]
@@ -480,17 +532,231 @@ class DecodePool:
         return seqs, scores, owner
 
 
+    # ------------------------------------------------------------------ the job, with jobs that end on their own
+    def _allocate_history_ctl(self, n_tokens: int, return_logits: bool) -> None:
+        """Tokens [S, L] and their log-probabilities [S, L] on the device; the f32 logits [S, L, V] only when they are asked for."""
+        S, dev = self.n_slots, self.device
+        if self.hist_ids is None or self.hist_ids.shape[1] < n_tokens:
+            self.hist_ids = torch.zeros(S, n_tokens, dtype=torch.int64, device=dev)
+            self.hist_logits = self.hist_logprob = None
+            self._graph = None
+        L = self.hist_ids.shape[1]
+        if self.hist_logprob is None:
+            self.hist_logprob = torch.zeros(S, L, dtype=torch.float32, device=dev)
+            self._graph = None
+        if not return_logits:
+            if self.hist_logits is not None:
+                self.hist_logits = None                              # (an earlier job's: this one records none)
+                self._graph = None
+        elif self.hist_logits is None:
+            self.hist_logits = torch.zeros(S, L, self.model.vocab_size, dtype=torch.float32, device=dev)
+            self._graph = None
+
+    def _generate_ctl(self, prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
+                      stop_frame, return_logits):
+        """`generate` on the job-control path: the sampler launch (`evo_sample_rows_ctl_f32`) ends a row's job on the device.  The host
+        knows the step by which a slot MUST have finished (its limit) and, with a stop rule, reads the [S] lengths every `poll_every`
+        steps to learn which slots finished sooner; a finished slot's history rows [:length] are fetched, its store row released, the
+        slot re-filled."""
+        m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+        if hasattr(m, "eval"):
+            m.eval()
+        n_spp = int(n_sample_per_prompt)
+        prompts = list(prompts)
+        if isinstance(n_tokens, (int, np.integer)):
+            limits = [int(n_tokens)] * len(prompts)
+        else:
+            limits = [int(n) for n in n_tokens]
+            if len(limits) != len(prompts):
+                raise ValueError("n_tokens: one limit, or one per prompt")
+        if any(n < 1 for n in limits) or n_spp < 1:
+            raise ValueError("n_tokens and n_sample_per_prompt must be >= 1")
+        if int(stop_frame) < 1:
+            raise ValueError("stop_frame must be >= 1")
+        patterns = stop_patterns(tok, stop_sequences)
+        stop_set = None
+        if stop_tokens is not None and len(stop_tokens):
+            stop_set = allowed_mask(tok, stop_tokens)
+            if self.allow_mask is not None and bool((stop_set & ~self.allow_mask).any()):
+                raise ValueError("stop_tokens: a stop token outside allowed_tokens could never be drawn")
+        for p in patterns:
+            if self.allow_mask is not None and not all(bool(self.allow_mask[t]) for t in p):
+                raise ValueError("stop_sequences: a pattern with a token outside allowed_tokens could never be drawn")
+        if not prompts:
+            return [], [], []
+        if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
+            raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
+        if not hasattr(m.ops, "sample_rows_ctl"):
+            raise RuntimeError("stop rules and per-prompt lengths need a compute backend with sample_rows_ctl; this model's backend has none")
+        encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
+        if sampling is not None:
+            sampling = list(sampling)
+            if len(sampling) != len(prompts) or any(d is not None and set(d) - {"top_k", "top_p", "temperature"} for d in sampling):
+                raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
+        if streams is not None and len(streams) != len(prompts) * n_spp:
+            raise ValueError("streams: one id per output")
+        has_stop = stop_set is not None or bool(patterns)
+        L = max(limits)
+        was_device = self.device_sampler
+        self.device_sampler = True                                   # (as with allowed_tokens alone: no seed means seed 0)
+        try:
+            if self.share_prompt_kv:
+                self._allocate_shared(max(e.shape[1] for e in encoded), L, n_spp, rows=min(S, len(prompts)))
+            else:
+                self._allocate(max(e.shape[1] for e in encoded) + L)
+            if not hasattr(self, "s_limit"):
+                self._allocate_sampler_state()
+            self._allocate_history_ctl(L, return_logits)
+            # everything the captured launch reads by address is per-pool state; the rule is copied INTO it.  What travels by value --
+            # the patterns, the frame, whether there is a stop mask at all -- is the key the captured step is kept under
+            if stop_set is not None:
+                self.s_stop_mask.copy_(m.ops.pack_allow_mask(stop_set, dev))
+            self._ctl = {"stop_mask": None if stop_set is None else self.s_stop_mask,
+                         "stop_seq": m.ops.pack_stop_sequences(patterns) if patterns else None, "stop_frame": int(stop_frame)}
+            key = ("ctl", tuple(map(tuple, patterns)), int(stop_frame), stop_set is not None)
+            if key != self._graph_key:
+                self._graph, self._graph_key = None, key
+            for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps"):
+                self.stats.setdefault(name, 0)
+            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits)
+        finally:
+            self.device_sampler = was_device
+
+    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits):
+        m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+        L = max(limits)
+        jobs = deque((pi * n_spp + c, pi) for pi in range(len(prompts)) for c in range(n_spp))
+        n_jobs = len(jobs)
+        out_ids = torch.full((n_jobs, L), -1, dtype=torch.long)
+        out_logprobs = torch.zeros(n_jobs, L, dtype=torch.float32)
+        out_logits = torch.zeros(n_jobs, L, m.vocab_size, dtype=torch.float32) if return_logits else None
+        out_len, out_fin = [0] * n_jobs, [0] * n_jobs
+        slot_job: List[Optional[int]] = [None] * S
+        slot_n = [0] * S                                             # tokens the slot's job has if it is still running
+        slot_limit = [0] * S
+        cached_prefill: Dict[int, tuple] = {}
+
+        def fill(slot: int) -> None:
+            j, pi = jobs.popleft()
+            if pi not in cached_prefill:
+                self._prefill_for(pi, jobs, slot_job, encoded, cached_prefill)
+            last_logits, tmp, row = cached_prefill[pi]
+            P = encoded[pi].shape[1]
+            kw = {"row": row} if row else {}
+            if self.share_prompt_kv:
+                self._install_shared(slot, pi, tmp, P, **kw)
+            else:
+                self._install(slot, tmp, P, **kw)
+            cfg = (sampling[pi] if sampling is not None else None) or {}
+            self.s_top_k[slot] = int(cfg.get("top_k", self.top_k))
+            self.s_top_p[slot] = float(cfg.get("top_p", self.top_p))
+            self.s_temperature[slot] = float(cfg.get("temperature", self.temperature))
+            self.s_stream[slot] = j if streams is None else int(streams[j])
+            self.s_count[slot] = 0
+            self.s_limit[slot] = limits[pi]
+            self.s_length[slot] = -1
+            self.s_finish[slot] = 0
+            self.s_active[slot] = True
+            self._sample_rows_ctl(last_logits[None], slice(slot, slot + 1))      # the first token; with limit 1 (or a stop) also the last
+            self.pos[slot] = P
+            slot_job[slot], slot_n[slot], slot_limit[slot] = j, 1, limits[pi]
+
+        def fetch(slots: List[int], lengths: Optional[List[int]]) -> None:
+            """Finished slots: rows [:length] of their histories leave the device, the slots go idle.  `lengths` None: every one of them
+            ran to its limit (no stop rule: nothing to ask the device)."""
+            idx = torch.tensor(slots, dtype=torch.int64, device=dev)
+            if self.share_prompt_kv:
+                self._release_shared(slots)
+            if lengths is None:
+                lengths, fins = [slot_limit[s] for s in slots], [FINISH_LENGTH] * len(slots)
+            else:
+                fins = self.s_finish[idx].cpu().tolist()
+            n_max = max(lengths)
+            ids_cpu, lp_cpu = self.hist_ids[idx, :n_max].cpu(), self.hist_logprob[idx, :n_max].cpu()
+            lg_cpu = self.hist_logits[idx, :n_max].cpu() if return_logits else None
+            for r, s in enumerate(slots):
+                j, n = slot_job[s], int(lengths[r])
+                out_ids[j, :n], out_logprobs[j, :n] = ids_cpu[r, :n], lp_cpu[r, :n]
+                if return_logits:
+                    out_logits[j, :n] = lg_cpu[r, :n]
+                out_len[j], out_fin[j] = n, int(fins[r])
+                self.stats["length_ends" if fins[r] == FINISH_LENGTH else "stop_ends"] += 1
+                self.stats["idle_slot_steps"] += slot_n[s] - n
+                self.stats["tokens"] -= slot_n[s] - n                # (steps a finished slot sat through generate nothing)
+                slot_job[s] = None
+
+        done, since_poll = 0, 0
+        while done < n_jobs:
+            filled = False
+            for s in range(S):
+                if slot_job[s] is None and jobs:
+                    fill(s)
+                    filled = True
+                    if slot_limit[s] == 1 and not has_stop:
+                        fetch([s], None)
+                        done += 1
+            active = [s for s in range(S) if slot_job[s] is not None]
+            if not active:
+                continue
+            # Under a stop rule a job may end on its first token, which fill() drew: after a round of fills the host looks before it
+            # steps (the fetch that emptied those slots has synchronised anyway).  due: slots whose job has ended by now for sure.
+            look = has_stop and filled
+            due = [s for s in active if slot_n[s] >= slot_limit[s]]
+            if not look and not due:
+                if self.share_prompt_kv:
+                    self._count_prefix_streams()
+                self._step_sampled()
+                since_poll += 1
+                for s in active:
+                    slot_n[s] += 1
+                self.stats["tokens"] += len(active)
+                due = [s for s in active if slot_n[s] >= slot_limit[s]]
+            if not has_stop:
+                finished, lengths = due, None                         # lengths are the limits: the host knows without reading
+            elif look or due or since_poll >= self.poll_every or not jobs:
+                # the one read: [S] lengths, -1 while a job runs.  With nothing left to admit the host looks after every step: no step
+                # may run with every row already ended
+                polled = self.s_length.cpu().tolist()
+                self.stats["polls"] += 1
+                since_poll = 0
+                finished = [s for s in active if polled[s] >= 0]
+                lengths = [polled[s] for s in finished]
+                if any(s not in finished for s in due):
+                    raise RuntimeError("decode pool: a slot ran past its limit without ending on the device")
+            else:
+                finished = []
+            if finished:
+                fetch(finished, lengths)
+                done += len(finished)
+
+        self.last_ids, self.last_logits, self.last_logprobs = out_ids, out_logits, out_logprobs
+        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES[f] for f in out_fin]
+        seqs, scores = [], []
+        for j in range(n_jobs):
+            n = out_len[j] - (1 if out_fin[j] == FINISH_STOP_TOKEN else 0)      # a stop token is trimmed, a stop sequence stays
+            seqs.append(tok.detokenize(out_ids[j, :n].tolist()))
+            scores.append(float(np.mean(out_logprobs[j, :out_len[j]].numpy().astype(np.float64))))
+        owner = [pi for pi in range(len(prompts)) for _ in range(n_spp)]
+        return seqs, scores, owner
+
+
 def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, temp: float = 0.7, top_k: int = 4,
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
-                prefill_batch: int = 1):
+                prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
+                poll_every: int = 8):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
     samples of a prompt read one stored copy of its K/V.  `prefill_batch` > 1: up to that many prompts admitted
-    together are prefilled in one forward, right-padded."""
+    together are prefilled in one forward, right-padded.  `n_tokens` as a sequence (one limit per prompt),
+    `stop_tokens`, `stop_sequences` / `stop_frame` and `return_logits=False`: jobs that end on their own (see
+    `DecodePool.generate`)."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
-                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch)
+                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every)
+    ctl = {}
+    if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
+        ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
-                                        prepend_bos=prepend_bos)
+                                        prepend_bos=prepend_bos, **ctl)
     return [prompts[i] for i in owner], seqs, scores

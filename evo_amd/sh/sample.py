@@ -150,3 +150,92 @@ def sample_seeded(logits: torch.Tensor, top_k: int, top_p: float, temperature: f
     pos = torch.minimum(pos, n_kept - 1) if top_k != 1 else torch.zeros_like(pos)
     tok = order.gather(-1, pos[:, None])[:, 0]
     return tok[0] if single else tok
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Job control: the written specification of the epilogue of `evo_sample_rows_ctl_f32` (csrc/sample.hip).
+# A row with `cnt` tokens recorded draws its token exactly as `sample_seeded` does, records it at position cnt (n = cnt + 1 tokens
+# then), and ends for the FIRST reason that holds: the token is a stop token; n is a multiple of `stop_frame` and the last tokens
+# (the new one included) spell a stop pattern no longer than n; n >= limit.  The token that ends a job is part of it.
+
+FINISH_RUNNING, FINISH_STOP_TOKEN, FINISH_STOP_SEQUENCE, FINISH_LENGTH = 0, 1, 2, 3
+FINISH_NAMES = {FINISH_STOP_TOKEN: "stop_token", FINISH_STOP_SEQUENCE: "stop_sequence", FINISH_LENGTH: "length"}
+MAX_STOP_SEQUENCES = 8
+MAX_STOP_SEQUENCE_LEN = 8
+
+
+def stop_patterns(tokenizer, stop_sequences):
+    """Strings (through `tokenizer`) or id lists -> a list of id lists.  At most 8 patterns of 1 to 8 tokens each; anything else is a
+    ValueError."""
+    if stop_sequences is None:
+        return []
+    if isinstance(stop_sequences, str):
+        stop_sequences = [stop_sequences]
+    pats = []
+    for p in stop_sequences:
+        if isinstance(p, torch.Tensor):
+            p = p.tolist()
+        ids = [int(t) for t in tokenizer.tokenize(p)] if isinstance(p, str) else [int(t) for t in p]
+        if not 1 <= len(ids) <= MAX_STOP_SEQUENCE_LEN:
+            raise ValueError(f"stop_sequences: a pattern has 1 to {MAX_STOP_SEQUENCE_LEN} tokens, got {len(ids)}")
+        if any(not 0 <= t < VOCAB_BITS for t in ids):
+            raise ValueError(f"stop_sequences: a token id of {ids} is outside [0, {VOCAB_BITS})")
+        pats.append(ids)
+    if len(pats) > MAX_STOP_SEQUENCES:
+        raise ValueError(f"stop_sequences: at most {MAX_STOP_SEQUENCES} patterns, got {len(pats)}")
+    return pats
+
+
+def pack_stop_sequences(patterns):
+    """Id lists (see `stop_patterns`) -> (int32 [n_seq, 8] padded with -1, int32 [n_seq]) on the host: what the C entry takes."""
+    pats = stop_patterns(None, patterns)
+    seq = torch.full((len(pats), MAX_STOP_SEQUENCE_LEN), -1, dtype=torch.int32)
+    for q, p in enumerate(pats):
+        seq[q, : len(p)] = torch.tensor(p, dtype=torch.int32)
+    return seq, torch.tensor([len(p) for p in pats], dtype=torch.int32)
+
+
+def finish_reason(ids, limit: int, stop_tokens=(), stop_sequences=(), stop_frame: int = 1) -> int:
+    """`ids`: every token the row has recorded, the new one last (n = len(ids) >= 1).  -> FINISH_* (0: the row goes on).
+    `stop_tokens`: a set of ids or a bool mask [512]; `stop_sequences`: id lists."""
+    if int(stop_frame) < 1:
+        raise ValueError("stop_frame must be >= 1")
+    ids = [int(t) for t in ids]
+    n, tok = len(ids), ids[-1]
+    if isinstance(stop_tokens, torch.Tensor):
+        is_stop = bool(stop_tokens[tok])
+    else:
+        is_stop = stop_tokens is not None and tok in stop_tokens
+    if is_stop:
+        return FINISH_STOP_TOKEN
+    if n % int(stop_frame) == 0:
+        for p in stop_sequences or ():
+            p = [int(t) for t in p]
+            if len(p) <= n and ids[n - len(p):] == p:                # a pattern longer than n reads nothing
+                return FINISH_STOP_SEQUENCE
+    if n >= int(limit):
+        return FINISH_LENGTH
+    return FINISH_RUNNING
+
+
+def stop_point(ids, limit: int, stop_tokens=(), stop_sequences=(), stop_frame: int = 1):
+    """Where the rule ends a job whose tokens WOULD be `ids` (at least min(limit, len(ids)) of them): (length, finish).  finish is 0
+    when `ids` runs out first."""
+    ids = [int(t) for t in ids]
+    for n in range(1, len(ids) + 1):
+        r = finish_reason(ids[:n], limit, stop_tokens, stop_sequences, stop_frame)
+        if r:
+            return n, r
+    return len(ids), FINISH_RUNNING
+
+
+def sample_ctl(logits: torch.Tensor, top_k: int, top_p: float, temperature: float, seed: int, stream: int, history, limit: int,
+               allowed=None, stop_tokens=(), stop_sequences=(), stop_frame: int = 1, hist_len=None):
+    """One launch of the control kernel for one ACTIVE row: logits [V], `history` = the cnt tokens recorded so far ->
+    (token or None, tokens recorded now, finish).  A row with cnt >= limit -- or, with a history of `hist_len` cells, cnt >= hist_len --
+    ends with FINISH_LENGTH without drawing: token None, the count unchanged."""
+    cnt = len(history)
+    if cnt >= int(limit) or (hist_len is not None and cnt >= int(hist_len)):
+        return None, cnt, FINISH_LENGTH
+    tok = int(sample_seeded(logits, top_k, top_p, temperature, seed, stream, cnt, allowed))
+    return tok, cnt + 1, finish_reason(list(history) + [tok], limit, stop_tokens, stop_sequences, stop_frame)

@@ -71,8 +71,10 @@ extern "C" {
  *      read one K/V of it) and evo_rope_append_decode_at_bf16 (the decode rotary + append with the cache row given apart from the
  *      position) added; no signature changed.
  *  16: evo_hyena_state_at_zt added (the Hyena end state and FIR history at every row's OWN last token: ragged batched prefill); no
- *      signature changed. */
-#define EVO_ABI_VERSION 16
+ *      signature changed.
+ *  17: evo_sample_rows_ctl_f32 added (the seeded sampler with job control: stop tokens, in-frame stop patterns and per-row length
+ *      limits decided on the device); no signature changed. */
+#define EVO_ABI_VERSION 17
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -528,6 +530,45 @@ int evo_sample_rows_f32(const void* logits, int64_t logits_f32, int64_t ld, cons
                         const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
                         const uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
                         int64_t hist_len, int64_t S, int64_t V, void* stream);
+
+/* ---- seeded sampling with job control: the row itself decides that its job is over ---------------------------------
+ * no reference counterpart in the pooled form; the single-stream rule it generalises is the reference's stop at EOS
+ *                                                            [REF evo/generation.py:136-139; semantic_design/semantic_design.py:121-179]
+ * Call site: DecodePool's job-control path (evo_amd/pool.py: _sample_rows_ctl, the last node of the captured pooled step and the
+ * one-row launch that draws a job's first token from its prefill's logits).  Written specification: evo_amd/sh/sample.py
+ * finish_reason / sample_ctl.  One launch, no host reads, no allocation, plain vector stores, no float atomics: capturable.
+ * The draw is evo_sample_rows_f32's own device code: on the same inputs token, logprob_out, hist_ids and hist_logits are bit-identical.
+ * Everything evo_sample_rows_f32 takes means what it means there, except:
+ *   count, active   required.  active [S] device bytes is now in/out: the kernel clears a row's byte when its job ends
+ *   hist_ids [S, hist_len] int64, hist_logits [S, hist_len, 512] f32 (16-byte aligned), hist_logprob [S, hist_len] f32: each one
+ *               optional on its own; what is given is recorded at [s, count[s]] (hist_logprob: the value of logprob_out)
+ *   limit       [S] device int64: the job's length limit
+ *   stop_mask   64 device bytes in allow's layout or NULL: the stop tokens
+ *   stop_seq    HOST int32 [n_seq, 8], stop_seq_len HOST int32 [n_seq], 0 <= n_seq <= 8, every length in 1 ... 8: the stop patterns.
+ *               They are read before the launch and travel in its arguments (a captured graph keeps the patterns it was captured with)
+ *   stop_frame  >= 1
+ *   length      [S] device int64, finish [S] device bytes: written only when a job ends
+ * Per active row, with cnt = count[s]:
+ *   cnt < 0, cnt >= limit[s], or (with any history) cnt >= hist_len: active[s] = 0, length[s] = cnt, finish[s] = 3; nothing is drawn,
+ *   neither the logits nor the history are read, count stays.
+ *   Otherwise the token is drawn and recorded, n = count[s] = cnt + 1, and the FIRST reason that holds ends the job:
+ *     1  the token's bit is set in stop_mask
+ *     2  n % stop_frame == 0 and for some pattern p of length l <= n the last l recorded tokens (the new one included) equal p.  Lane 0
+ *        compares the new token and then hist_ids[s, cnt - 1 ... cnt - l + 1] (>= 0: a pattern longer than n reads nothing), which earlier
+ *        launches on the same stream wrote
+ *     3  n >= limit[s]
+ *   and then active[s] = 0, length[s] = n, finish[s] = the reason.  The token that ends a job is part of it.
+ * Inactive rows write nothing.  Returns -1 for everything evo_sample_rows_f32 refuses, a null count / active / limit / length / finish,
+ * n_seq outside 0 ... 8, n_seq > 0 with a null stop_seq / stop_seq_len / hist_ids, a pattern length outside 1 ... 8, stop_frame < 1, or
+ * a history with hist_len < 1. */
+#define EVO_SAMPLE_MAX_STOP_SEQ 8
+#define EVO_SAMPLE_MAX_STOP_LEN 8
+int evo_sample_rows_ctl_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,
+                            const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
+                            uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
+                            float* hist_logprob, int64_t hist_len, const int64_t* limit, const void* stop_mask,
+                            const int32_t* stop_seq, const int32_t* stop_seq_len, int64_t n_seq, int64_t stop_frame,
+                            int64_t* length, uint8_t* finish, int64_t S, int64_t V, void* stream);
 
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:

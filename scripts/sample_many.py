@@ -4,6 +4,11 @@
 generations of `--n-tokens` each, CSV out with the reference's columns (UUID, Prompt, Generated Sequence, Score).
 
     python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --n-sample-per-prompt 8 --n-slots 16
+
+Jobs that end on their own: `--n-tokens` becomes a limit, a generation ends at its first in-frame stop codon
+
+    python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT \
+        --stop-sequences TAA,TAG,TGA --stop-frame 3 --scores-only --extra-columns
 """
 import argparse
 import csv
@@ -45,6 +50,14 @@ def main(argv=None):
                                                                    "private copy per decode stream (long prompts, many samples)")
     ap.add_argument("--prefill-batch", type=int, default=1, help="prefill up to N prompts admitted together in one forward, right-padded "
                                                                  "(default 1: every prompt alone)")
+    ap.add_argument("--stop-tokens", default=None, help='characters that end a generation and are trimmed from it, e.g. "N"')
+    ap.add_argument("--stop-sequences", default=None, help="comma-separated patterns of 1-8 characters (at most 8) that end a generation and "
+                                                           "stay in it, e.g. TAA,TAG,TGA")
+    ap.add_argument("--stop-frame", type=int, default=1, help="a stop sequence counts only when it ends at a multiple of this many generated "
+                                                              "tokens (3: in-frame codons)")
+    ap.add_argument("--scores-only", action="store_true", help="keep no logits, on the device or on the host: the scores come from the "
+                                                               "sampler's own log-probabilities")
+    ap.add_argument("--extra-columns", action="store_true", help="append Length and Finish (stop_token | stop_sequence | length) to the CSV")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -58,15 +71,27 @@ def main(argv=None):
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
                       temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
                       share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch)
+    ctl = {}                                                  # any of these moves the job onto the job-control path
+    if args.stop_tokens:
+        ctl["stop_tokens"] = args.stop_tokens
+    if args.stop_sequences:
+        ctl["stop_sequences"] = [p for p in args.stop_sequences.split(",") if p]
+    if args.stop_frame != 1:
+        ctl["stop_frame"] = args.stop_frame
+    if args.scores_only:
+        ctl["return_logits"] = False
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
-                                        prepend_bos=args.prepend_bos)
-    rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] for s, sc, o in zip(seqs, scores, owner)
+                                        prepend_bos=args.prepend_bos, **ctl)
+    extra = [[]] * len(seqs)
+    if args.extra_columns:                                    # (without any of the options above every job runs to --n-tokens)
+        extra = [[str(n), f] for n, f in zip(pool.last_lengths, pool.last_finish)] if ctl else [[str(args.n_tokens), "length"]] * len(seqs)
+    rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] + x for s, sc, o, x in zip(seqs, scores, owner, extra)
             if s.strip() and not math.isnan(sc)]              # the reference drops empty / NaN-scored generations
     with open(args.output_csv, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["UUID", "Prompt", "Generated Sequence", "Score"])
+        w.writerow(["UUID", "Prompt", "Generated Sequence", "Score"] + (["Length", "Finish"] if args.extra_columns else []))
         w.writerows(rows)
-    print(f"{len(rows)} generations of {args.n_tokens} tokens from {len(prompts)} prompts -> {args.output_csv} "
+    print(f"{len(rows)} generations of {'at most ' if ctl else ''}{args.n_tokens} tokens from {len(prompts)} prompts -> {args.output_csv} "
           f"({pool.stats['steps']} pooled steps, {pool.stats['prefills']} prefills)")
     return rows
 

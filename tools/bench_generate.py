@@ -4,7 +4,11 @@ state + KV cache, 1 x MI355X.  Reports prefill time and decode ms/token (total m
     python tools/bench_generate.py [--new 256] [--batch 1] [--no-graph]
 Pool mode with --seed: the same job with the host sampler (the default path) and with the device sampler (csrc/sample.hip), alternated
 in one process -- tok/s, ms/step and the repeat-to-repeat spread of both, optionally as one JSON line (--json).
-    python tools/bench_generate.py --pool 8,32 --jobs 64 --seed 1 --repeats 3 --json profiles/sample_bench_line.json"""
+    python tools/bench_generate.py --pool 8,32 --jobs 64 --seed 1 --repeats 3 --json profiles/sample_bench_line.json
+Pool mode with a stop rule (--stop-tokens / --stop-sequences): the same job at fixed length (today's path) and with jobs
+that end on their own, alternated in one process, for every --poll-every value -- pooled steps, seconds, jobs/s, device and host bytes.
+    python tools/bench_generate.py --model evo-1-8k-base --pool 32 --jobs 64 --prompt 2048 --new 1024 --seed 1 --allowed-tokens ACGT \
+        --stop-sequences TAA,TAG,TGA --stop-frame 3 --poll-every 1,4,8,16 --temperature 8 --json profiles/stop_bench_line.json"""
 import argparse
 import json
 import os
@@ -60,6 +64,52 @@ def sampler_ab(args, model, tok, prompts, slot_counts, dev):
             f.write(line + "\n")
 
 
+def stop_ab(args, model, tok, prompts, n_slots, dev):
+    """Fixed length (evo_sample_rows_f32) against jobs that end on their own (evo_sample_rows_ctl_f32), alternated: fixed, stop, fixed, ..."""
+    from evo_amd.pool import DecodePool
+    rule = dict(stop_frame=args.stop_frame, return_logits=not args.scores_only)
+    if args.stop_tokens:
+        rule["stop_tokens"] = args.stop_tokens
+    if args.stop_sequences:
+        rule["stop_sequences"] = [p for p in args.stop_sequences.split(",") if p]
+    polls = [int(v) for v in str(args.poll_every).split(",")]
+    mk = lambda **kw: DecodePool(model, tok, n_slots=n_slots, top_k=4, top_p=1.0, temperature=args.temperature, device=dev,
+                                 use_graph=not args.no_graph, seed=args.seed or 0, allowed_tokens=args.allowed_tokens, **kw)
+    pools = {"fixed": mk()}
+    pools.update({f"stop_poll{p}": mk(poll_every=p) for p in polls})
+    result = {"model": args.model, "jobs": len(prompts), "prompt_nt": [min(map(len, prompts)), max(map(len, prompts))], "limit": args.new,
+              "slots": n_slots, "temperature": args.temperature, "allowed_tokens": args.allowed_tokens, "rule": {k: v for k, v in rule.items()},
+              "graph": not args.no_graph, "repeats": args.repeats, "runs": {}}
+    times, info = {k: [] for k in pools}, {}
+    for rep in range(args.repeats + 1):                              # rep 0 = warm-up (allocations, graph capture), not kept
+        for name, pool in pools.items():
+            pool.stats = {k: 0 for k in pool.stats}
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            pool.generate(prompts, n_tokens=args.new, **({} if name == "fixed" else rule))
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            hist = sum(t.numel() * t.element_size() for t in (pool.hist_ids, pool.hist_logits, getattr(pool, "hist_logprob", None)) if t is not None)
+            host = sum(t.numel() * t.element_size() for t in (pool.last_ids, pool.last_logits, getattr(pool, "last_logprobs", None)) if t is not None)
+            info[name] = dict(pool.stats, device_history_bytes=hist, host_result_bytes=host, device_peak_bytes=torch.cuda.max_memory_allocated())
+            if name != "fixed":
+                info[name]["mean_length"] = round(float(np.mean(pool.last_lengths)), 1)
+            if rep:
+                times[name].append(dt)
+            print(f"[stop A/B slots={n_slots} {name} rep{rep}{' (warm-up)' if not rep else ''}] {dt * 1e3:.0f} ms, {pool.stats['steps']} steps, "
+                  f"{len(prompts) / dt:.2f} jobs/s", flush=True)
+    for name, ts in times.items():
+        med = float(np.median(ts))
+        result["runs"][name] = dict(info[name], seconds=[round(t, 4) for t in ts], median_s=round(med, 4), jobs_per_s=round(len(prompts) / med, 3),
+                                    spread=round((max(ts) - min(ts)) / med, 4))
+    line = json.dumps(result)
+    print(line)
+    if args.json:
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prompt", type=int, default=8192)
@@ -72,6 +122,14 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="pool mode: A/B of the host sampler against the seeded device sampler")
     ap.add_argument("--repeats", type=int, default=3, help="timed repeats per sampler in the A/B (after one warm-up each)")
     ap.add_argument("--json", default=None, help="A/B: write the result line to this file")
+    ap.add_argument("--allowed-tokens", default=None, help="pool mode with a stop rule: characters that may be drawn")
+    ap.add_argument("--stop-tokens", default=None, help="pool mode: characters that end a job (A/B against the fixed-length job)")
+    ap.add_argument("--stop-sequences", default=None, help="pool mode: comma-separated stop patterns, e.g. TAA,TAG,TGA")
+    ap.add_argument("--stop-frame", type=int, default=1)
+    ap.add_argument("--scores-only", action="store_true", help="stop A/B: the job-control runs keep no logits")
+    ap.add_argument("--poll-every", default="8", help="stop A/B: the poll intervals to compare, e.g. 1,4,8,16")
+    ap.add_argument("--temperature", type=float, default=0.7, help="stop A/B: sampling temperature (synthetic weights repeat their last "
+                                                                   "token at 0.7; a high value spreads the draws)")
     args = ap.parse_args()
     slot_counts = [int(v) for v in str(args.pool).split(",") if int(v) > 0]
     args.pool = slot_counts[0] if slot_counts else 0
@@ -88,6 +146,8 @@ def main():
         from evo_amd.pool import DecodePool
         lens = [int(args.prompt * (0.5 + 0.5 * (j % 5) / 4)) for j in range(args.jobs)]
         prompts = ["".join(rng.choice(list("ACGT"), size=n)) for n in lens]
+        if args.stop_tokens or args.stop_sequences:
+            return stop_ab(args, model, tok, prompts, args.pool, dev)
         if args.seed is not None:
             return sampler_ab(args, model, tok, prompts, slot_counts, dev)
         pool = DecodePool(model, tok, n_slots=args.pool, top_k=4, top_p=1.0, temperature=0.7, device=dev,
