@@ -68,10 +68,14 @@ _SIGNATURES = {
     "evo_sample_rows_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 7 + [_I64] * 3 + [_PTR], _c.c_int),
     "evo_sample_rows_ctl_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 8 + [_I64] + [_PTR] * 4 + [_I64, _I64, _PTR, _PTR,
                                                                                                                          _I64, _I64, _PTR], _c.c_int),
+    "evo_sample_rows_dfa_f32": ([_PTR, _I64, _I64, _PTR, _PTR, _PTR, _PTR, _c.c_uint64] + [_PTR] * 8 + [_I64] + [_PTR] * 4 + [_I64, _I64, _PTR, _PTR,
+                                                                                                                         _PTR, _I64, _PTR, _I64,
+                                                                                                                         _PTR, _PTR, _I64, _I64,
+                                                                                                                         _PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 17        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 18        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
                         # `prefix_streams` counter is computed from it on the host)
 
@@ -1295,8 +1299,32 @@ class HipOps(Backend):
         `pack_stop_sequences`) at the end of its recorded tokens, or `limit` [S] int64 reached -- by clearing its byte of `active` [S] bool
         and writing `length` [S] int64 and `finish` [S] uint8 (1 stop token, 2 stop sequence, 3 length).  hist_ids [S, L] int64,
         hist_logits [S, L, 512] f32 and hist_logprob [S, L] f32 are each optional.  One launch, nothing read back: capturable."""
+        return self._sample_rows_ctl("sample_rows_ctl", "evo_sample_rows_ctl_f32", None, logits, top_k, top_p, temperature, seed, count, active,
+                                     limit, length, finish, stream, allow, ids_out, logprob_out, hist_ids, hist_logits, hist_logprob,
+                                     stop_mask, stop_seq, stop_frame)
+
+    def sample_rows_dfa(self, logits: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, temperature: torch.Tensor, seed: int,
+                        count: torch.Tensor, active: torch.Tensor, limit: torch.Tensor, length: torch.Tensor, finish: torch.Tensor,
+                        dfa_alphabet: torch.Tensor, dfa_next: torch.Tensor, dfa_base: torch.Tensor, dfa_state: torch.Tensor,
+                        stream: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                        ids_out: Optional[torch.Tensor] = None, logprob_out: Optional[torch.Tensor] = None,
+                        hist_ids: Optional[torch.Tensor] = None, hist_logits: Optional[torch.Tensor] = None,
+                        hist_logprob: Optional[torch.Tensor] = None, stop_mask: Optional[torch.Tensor] = None, stop_seq=None,
+                        stop_frame: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`sample_rows_ctl` under a per-row token automaton (csrc/sample.hip; specification: sh/sample.py sample_dfa).
+        `dfa_alphabet`: HOST int32 [1 ... 8] distinct token ids; `dfa_next`: device int32 [n_states, 8] (>= 0 next state relative to the
+        row's base, -2 accept, other negative values forbidden); `dfa_base` [S] device int64 (the table row of the row's state 0; < 0: the row
+        is unconstrained); `dfa_state` [S] device int32, in/out.  A row draws from the tokens its state permits (and `allow`), the token moves
+        its state; finish 4 = the constraint is complete, 5 = a dead end (nothing drawn).  One launch, nothing read back: capturable."""
+        return self._sample_rows_ctl("sample_rows_dfa", "evo_sample_rows_dfa_f32", (dfa_alphabet, dfa_next, dfa_base, dfa_state), logits, top_k,
+                                     top_p, temperature, seed, count, active, limit, length, finish, stream, allow, ids_out, logprob_out,
+                                     hist_ids, hist_logits, hist_logprob, stop_mask, stop_seq, stop_frame)
+
+    def _sample_rows_ctl(self, me, entry, dfa, logits, top_k, top_p, temperature, seed, count, active, limit, length, finish, stream, allow,
+                         ids_out, logprob_out, hist_ids, hist_logits, hist_logprob, stop_mask, stop_seq, stop_frame):
+        """The argument checks and the call of both control entries (`dfa`: None, or the four automaton operands of `sample_rows_dfa`)."""
         if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2 or not logits.is_cuda:
-            raise RuntimeError("sample_rows_ctl: logits must be a [S, 512] bf16 or f32 device matrix")
+            raise RuntimeError(f"{me}: logits must be a [S, 512] bf16 or f32 device matrix")
         S, V = logits.shape
         if logits.stride(1) != 1 or logits.stride(0) % 8 or logits.stride(0) < V or logits.data_ptr() % 16:
             logits = logits.contiguous()
@@ -1306,7 +1334,7 @@ class HipOps(Backend):
             if t is None and not required:
                 return
             if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-                raise RuntimeError(f"sample_rows_ctl: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+                raise RuntimeError(f"{me}: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
         need(top_k, torch.int32, (S,), "top_k", True)
         need(top_p, torch.float32, (S,), "top_p", True)
         need(temperature, torch.float32, (S,), "temperature", True)
@@ -1338,17 +1366,32 @@ class HipOps(Backend):
             seq, seq_len = stop_seq
             if seq.dtype != torch.int32 or seq_len.dtype != torch.int32 or seq.is_cuda or seq_len.is_cuda or not seq.is_contiguous() \
                     or tuple(seq.shape) != (seq_len.numel(), 8):
-                raise RuntimeError("sample_rows_ctl: stop_seq must be the host pair of pack_stop_sequences")
+                raise RuntimeError(f"{me}: stop_seq must be the host pair of pack_stop_sequences")
             if hist_ids is None:
-                raise RuntimeError("sample_rows_ctl: stop sequences need hist_ids")
+                raise RuntimeError(f"{me}: stop sequences need hist_ids")
             n_seq, seq_ptr, len_ptr = int(seq_len.numel()), seq.data_ptr(), seq_len.data_ptr()
-        with self._t("sample_rows_ctl"):
-            _check(self.lib.evo_sample_rows_ctl_f32(
+        extra = ()
+        if dfa is not None:
+            alphabet, nxt, base, state = dfa
+            if not isinstance(alphabet, torch.Tensor) or alphabet.dtype != torch.int32 or alphabet.is_cuda or alphabet.dim() != 1 \
+                    or not alphabet.is_contiguous() or not 1 <= alphabet.numel() <= 8:
+                raise RuntimeError(f"{me}: dfa_alphabet must be a host int32 vector of 1 to 8 token ids")
+            ids = alphabet.tolist()
+            if len(set(ids)) != len(ids) or any(not 0 <= t < 512 for t in ids):
+                raise RuntimeError(f"{me}: dfa_alphabet must hold distinct token ids in [0, 512)")
+            if not isinstance(nxt, torch.Tensor) or nxt.dim() != 2 or not 1 <= nxt.shape[0] <= 1 << 27 or nxt.data_ptr() % 16:
+                raise RuntimeError(f"{me}: dfa_next must be a 16-byte aligned [n_states, 8] matrix of 1 to 2^27 states")
+            need(nxt, torch.int32, (nxt.shape[0], 8), "dfa_next", True)
+            need(base, torch.int64, (S,), "dfa_base", True)
+            need(state, torch.int32, (S,), "dfa_state", True)
+            extra = (alphabet.data_ptr(), int(alphabet.numel()), nxt.data_ptr(), int(nxt.shape[0]), base.data_ptr(), state.data_ptr())
+        with self._t(me):
+            _check(getattr(self.lib, entry)(
                 logits.data_ptr(), int(logits.dtype == torch.float32), logits.stride(0), top_k.data_ptr(), top_p.data_ptr(),
                 temperature.data_ptr(), _ptr(allow), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(stream), count.data_ptr(), active.data_ptr(),
                 ids_out.data_ptr(), logprob_out.data_ptr(), _ptr(hist_ids), _ptr(hist_logits), _ptr(hist_logprob), hist_len,
-                limit.data_ptr(), _ptr(stop_mask), seq_ptr, len_ptr, n_seq, int(stop_frame), length.data_ptr(), finish.data_ptr(), S, V,
-                _stream()), "evo_sample_rows_ctl_f32")
+                limit.data_ptr(), _ptr(stop_mask), seq_ptr, len_ptr, n_seq, int(stop_frame), length.data_ptr(), finish.data_ptr(), *extra,
+                S, V, _stream()), entry)
         return ids_out, logprob_out
 
 

@@ -36,6 +36,11 @@ Jobs that end on their own (opt-in): with `stop_tokens`, `
 stop pattern, own limit) and goes inactive on the device.  The host knows the step by which a slot must have ended (its limit) and, with a
 stop rule, reads one [S] vector of lengths every `poll_every` steps to learn who ended sooner; it fetches rows [:length] of the finished
 slots' histories (tokens, log-probabilities, logits only when asked for), releases their store rows and re-fills them.
+
+Constrained generation (opt-in): `generate(constraints=...)` gives every prompt (or some of them) a `TokenConstraint`
+(evo_amd/constraints.py: an IUPAC template, a protein to encode, an open reading frame, concatenations).  The job-control path then ends
+with the launch `evo_sample_rows_dfa_f32`: a slot's state in its prompt's automaton decides what it may draw, the token moves the state,
+and completing the constraint ends the job -- all of it inside the captured step.
 """
 from __future__ import annotations
 
@@ -47,7 +52,10 @@ import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
 from .sh.cache import PromptStore
-from .sh.sample import FINISH_LENGTH, FINISH_NAMES, FINISH_STOP_TOKEN, allowed_mask, sample, stop_patterns
+from .sh.model import capture_graph
+from .constraints import TokenConstraint
+from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
+                        stop_patterns)
 
 
 class DecodePool:
@@ -144,6 +152,9 @@ class DecodePool:
         self.s_limit = torch.zeros(S, dtype=torch.int64, device=dev)
         self.s_length = torch.full((S,), -1, dtype=torch.int64, device=dev)
         self.s_finish = torch.zeros(S, dtype=torch.uint8, device=dev)
+        # constrained generation: the table row of the slot's state 0 (-1: the slot's job is free) and its state relative to that row
+        self.s_dfa_base = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        self.s_dfa_state = torch.zeros(S, dtype=torch.int32, device=dev)
 
     def _allocate_shared(self, p_max: int, n_tokens: int, n_sample_per_prompt: int, rows: Optional[int] = None) -> None:
         """share_prompt_kv: own caches of `n_tokens` rows per slot and a store of R rows of the longest prompt's length.  Jobs run in
@@ -308,7 +319,7 @@ class DecodePool:
                 torch.cuda.synchronize(self.device)
                 self.model._row_index(self.n_slots, self.device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with capture_graph(g):
                     out = self._step_eager()
                 self._graph = (g, out)
                 return first
@@ -326,13 +337,18 @@ class DecodePool:
     def _sample_rows_ctl(self, logits: torch.Tensor, rows: slice) -> None:
         """The sampler launch of the job-control path: the same draw, and a row that ends its job clears its own `s_active`."""
         c = self._ctl
-        self.model.ops.sample_rows_ctl(logits, self.s_top_k[rows], self.s_top_p[rows], self.s_temperature[rows], self.seed,
-                                       count=self.s_count[rows], active=self.s_active[rows], limit=self.s_limit[rows],
-                                       length=self.s_length[rows], finish=self.s_finish[rows], stream=self.s_stream[rows],
-                                       allow=self.s_allow, ids_out=self.ids[rows], logprob_out=self.s_logprob[rows],
-                                       hist_ids=self.hist_ids[rows], hist_logits=None if self.hist_logits is None else self.hist_logits[rows],
-                                       hist_logprob=self.hist_logprob[rows], stop_mask=c["stop_mask"], stop_seq=c["stop_seq"],
-                                       stop_frame=c["stop_frame"])
+        launch, dfa = self.model.ops.sample_rows_ctl, {}
+        if c["dfa"] is not None:                                     # constrained generation: the same launch under the slots' automata
+            launch = self.model.ops.sample_rows_dfa
+            dfa = dict(dfa_alphabet=c["dfa"]["alphabet"], dfa_next=c["dfa"]["next"], dfa_base=self.s_dfa_base[rows],
+                       dfa_state=self.s_dfa_state[rows])
+        launch(logits, self.s_top_k[rows], self.s_top_p[rows], self.s_temperature[rows], self.seed,
+               count=self.s_count[rows], active=self.s_active[rows], limit=self.s_limit[rows],
+               length=self.s_length[rows], finish=self.s_finish[rows], stream=self.s_stream[rows],
+               allow=self.s_allow, ids_out=self.ids[rows], logprob_out=self.s_logprob[rows],
+               hist_ids=self.hist_ids[rows], hist_logits=None if self.hist_logits is None else self.hist_logits[rows],
+               hist_logprob=self.hist_logprob[rows], stop_mask=c["stop_mask"], stop_seq=c["stop_seq"],
+               stop_frame=c["stop_frame"], **dfa)
 
     def _step_sample_eager(self) -> None:
         if self._ctl is not None:
@@ -352,7 +368,7 @@ class DecodePool:
                 torch.cuda.synchronize(self.device)
                 self.model._row_index(self.n_slots, self.device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with capture_graph(g):
                     self._step_sample_eager()
                 self._graph = (g, None)
                 return None
@@ -380,7 +396,7 @@ class DecodePool:
     def generate(self, prompts: Sequence[str], n_tokens=1000, n_sample_per_prompt: int = 1,
                  prepend_bos: bool = False, sampling: Optional[Sequence[Optional[dict]]] = None,
                  streams: Optional[Sequence[int]] = None, stop_tokens=None, stop_sequences=None, stop_frame: int = 1,
-                 return_logits: bool = True) \
+                 return_logits: bool = True, constraints=None) \
             -> Tuple[List[str], List[float], List[int]]:
         """Returns (generated strings, mean log-likelihood scores, index of the prompt each came from), in job
         order: prompt 0's samples first.  `sampling` (device sampler only): one dict of `top_k` / `top_p` / `temperature`
@@ -391,11 +407,15 @@ class DecodePool:
         is one length limit per prompt; `stop_tokens` (ids, or a string through the tokenizer) end a job and are trimmed from its string;
         `stop_sequences` (strings or id lists, at most 8 of 1 to 8 tokens) end it when they end at a multiple of `stop_frame` tokens,
         counted from the first generated one, and stay in its string; `return_logits=False` keeps no logits at all.  The run leaves
-        `last_lengths`, `last_finish` ("stop_token" | "stop_sequence" | "length"), `last_logprobs`; `last_ids` holds -1 beyond a job's length."""
+        `last_lengths`, `last_finish` ("stop_token" | "stop_sequence" | "length"), `last_logprobs`; `last_ids` holds -1 beyond a job's length.
+
+        Constrained generation (also on the job-control path): `constraints` is one `TokenConstraint` for every prompt, or
+        a list with one (or None: that prompt is free) per prompt.  It governs the GENERATED tokens: every sample starts in state 0, the
+        prompt is not walked.  A job ends with the token that completes its constraint (`last_finish` "constraint", kept in its string)."""
         if (not isinstance(n_tokens, (int, np.integer)) or stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1
-                or not return_logits):
+                or not return_logits or constraints is not None):
             return self._generate_ctl(prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                                      stop_frame, return_logits)
+                                      stop_frame, return_logits, constraints)
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         if hasattr(m, "eval"):
             m.eval()
@@ -552,8 +572,38 @@ class DecodePool:
             self.hist_logits = torch.zeros(S, L, self.model.vocab_size, dtype=torch.float32, device=dev)
             self._graph = None
 
+    def _constraints_of(self, constraints, n_prompts: int):
+        """`constraints` of generate() -> (one TokenConstraint or None per prompt, the distinct ones in order of first use).  Checked here,
+        before any device work: every constraint against the pool's allowed tokens, and one alphabet for all of them."""
+        per = [constraints] * n_prompts if isinstance(constraints, TokenConstraint) else list(constraints)
+        if len(per) != n_prompts or any(c is not None and not isinstance(c, TokenConstraint) for c in per):
+            raise ValueError("constraints: one TokenConstraint, or one (or None) per prompt")
+        distinct: List[TokenConstraint] = []
+        for c in per:
+            if c is not None and not any(c is d for d in distinct):
+                c.validate(self.allow_mask)
+                distinct.append(c)
+        if len({c.alphabet for c in distinct}) > 1:
+            raise ValueError("constraints: all constraints of one call must share one alphabet")
+        return per, distinct
+
+    def _upload_constraints(self, per, distinct):
+        """The distinct automata, concatenated once into ONE device table [total states, 8] (per-pool state: a table of the same size is
+        copied into the one the captured launch reads) -> (what the launch takes, the table row of every prompt's state 0; -1: free)."""
+        offsets, total = {}, 0
+        for c in distinct:
+            offsets[id(c)] = total
+            total += c.n_states
+        table = torch.from_numpy(np.concatenate([c.table for c in distinct]).astype(np.int32))
+        if getattr(self, "s_dfa_next", None) is None or tuple(self.s_dfa_next.shape) != tuple(table.shape):
+            self.s_dfa_next = table.to(self.device)
+        else:
+            self.s_dfa_next.copy_(table)
+        bases = [-1 if c is None else offsets[id(c)] for c in per]
+        return {"alphabet": torch.tensor(distinct[0].alphabet, dtype=torch.int32), "next": self.s_dfa_next}, bases
+
     def _generate_ctl(self, prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                      stop_frame, return_logits):
+                      stop_frame, return_logits, constraints=None):
         """`generate` on the job-control path: the sampler launch (`evo_sample_rows_ctl_f32`) ends a row's job on the device.  The host
         knows the step by which a slot MUST have finished (its limit) and, with a stop rule, reads the [S] lengths every `poll_every`
         steps to learn which slots finished sooner; a finished slot's history rows [:length] are fetched, its store row released, the
@@ -588,6 +638,9 @@ class DecodePool:
             raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
         if not hasattr(m.ops, "sample_rows_ctl"):
             raise RuntimeError("stop rules and per-prompt lengths need a compute backend with sample_rows_ctl; this model's backend has none")
+        per_prompt, distinct = self._constraints_of(constraints, len(prompts)) if constraints is not None else (None, [])
+        if distinct and not hasattr(m.ops, "sample_rows_dfa"):
+            raise RuntimeError("constraints need a compute backend with sample_rows_dfa; this model's backend has none")
         encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
         if sampling is not None:
             sampling = list(sampling)
@@ -595,7 +648,7 @@ class DecodePool:
                 raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
         if streams is not None and len(streams) != len(prompts) * n_spp:
             raise ValueError("streams: one id per output")
-        has_stop = stop_set is not None or bool(patterns)
+        has_stop = stop_set is not None or bool(patterns) or bool(distinct)      # (a job may end by completing its constraint: the host polls)
         L = max(limits)
         was_device = self.device_sampler
         self.device_sampler = True                                   # (as with allowed_tokens alone: no seed means seed 0)
@@ -611,18 +664,21 @@ class DecodePool:
             # the patterns, the frame, whether there is a stop mask at all -- is the key the captured step is kept under
             if stop_set is not None:
                 self.s_stop_mask.copy_(m.ops.pack_allow_mask(stop_set, dev))
+            dfa, bases = self._upload_constraints(per_prompt, distinct) if distinct else (None, None)
             self._ctl = {"stop_mask": None if stop_set is None else self.s_stop_mask,
-                         "stop_seq": m.ops.pack_stop_sequences(patterns) if patterns else None, "stop_frame": int(stop_frame)}
-            key = ("ctl", tuple(map(tuple, patterns)), int(stop_frame), stop_set is not None)
+                         "stop_seq": m.ops.pack_stop_sequences(patterns) if patterns else None, "stop_frame": int(stop_frame), "dfa": dfa}
+            # (the alphabet travels by value; the table is read by address and its size is an argument)
+            key = ("ctl", tuple(map(tuple, patterns)), int(stop_frame), stop_set is not None) \
+                + ((distinct[0].alphabet, dfa["next"].data_ptr(), int(dfa["next"].shape[0])) if distinct else ())
             if key != self._graph_key:
                 self._graph, self._graph_key = None, key
-            for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps"):
+            for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps") + (("constraint_ends",) if distinct else ()):
                 self.stats.setdefault(name, 0)
-            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits)
+            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, bases)
         finally:
             self.device_sampler = was_device
 
-    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits):
+    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, dfa_bases=None):
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         L = max(limits)
         jobs = deque((pi * n_spp + c, pi) for pi in range(len(prompts)) for c in range(n_spp))
@@ -656,6 +712,9 @@ class DecodePool:
             self.s_limit[slot] = limits[pi]
             self.s_length[slot] = -1
             self.s_finish[slot] = 0
+            if dfa_bases is not None:                                # the job starts in state 0 of its prompt's automaton
+                self.s_dfa_base[slot] = dfa_bases[pi]
+                self.s_dfa_state[slot] = 0
             self.s_active[slot] = True
             self._sample_rows_ctl(last_logits[None], slice(slot, slot + 1))      # the first token; with limit 1 (or a stop) also the last
             self.pos[slot] = P
@@ -671,6 +730,8 @@ class DecodePool:
                 lengths, fins = [slot_limit[s] for s in slots], [FINISH_LENGTH] * len(slots)
             else:
                 fins = self.s_finish[idx].cpu().tolist()
+                if FINISH_DEAD_END in fins:                          # (validate() rules it out for every reachable state)
+                    raise RuntimeError("decode pool: a constrained job reached a state that permits no token")
             n_max = max(lengths)
             ids_cpu, lp_cpu = self.hist_ids[idx, :n_max].cpu(), self.hist_logprob[idx, :n_max].cpu()
             lg_cpu = self.hist_logits[idx, :n_max].cpu() if return_logits else None
@@ -680,7 +741,7 @@ class DecodePool:
                 if return_logits:
                     out_logits[j, :n] = lg_cpu[r, :n]
                 out_len[j], out_fin[j] = n, int(fins[r])
-                self.stats["length_ends" if fins[r] == FINISH_LENGTH else "stop_ends"] += 1
+                self.stats[{FINISH_LENGTH: "length_ends", FINISH_CONSTRAINT: "constraint_ends"}.get(fins[r], "stop_ends")] += 1
                 self.stats["idle_slot_steps"] += slot_n[s] - n
                 self.stats["tokens"] -= slot_n[s] - n                # (steps a finished slot sat through generate nothing)
                 slot_job[s] = None
@@ -730,7 +791,7 @@ class DecodePool:
                 done += len(finished)
 
         self.last_ids, self.last_logits, self.last_logprobs = out_ids, out_logits, out_logprobs
-        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES[f] for f in out_fin]
+        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES_ALL[f] for f in out_fin]
         seqs, scores = [], []
         for j in range(n_jobs):
             n = out_len[j] - (1 if out_fin[j] == FINISH_STOP_TOKEN else 0)      # a stop token is trimmed, a stop sequence stays
@@ -744,19 +805,22 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
-                poll_every: int = 8):
+                poll_every: int = 8, constraints=None):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
     samples of a prompt read one stored copy of its K/V.  `prefill_batch` > 1: up to that many prompts admitted
     together are prefilled in one forward, right-padded.  `n_tokens` as a sequence (one limit per prompt),
     `stop_tokens`, `stop_sequences` / `stop_frame` and `return_logits=False`: jobs that end on their own (see
-    `DecodePool.generate`)."""
+    `DecodePool.generate`).  `constraints`: one `TokenConstraint` (evo_amd/constraints.py) for every prompt, or one (or None) per prompt --
+    constrained generation on the device."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
                       allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every)
     ctl = {}
     if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)
+    if constraints is not None:
+        ctl["constraints"] = constraints
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos, **ctl)
     return [prompts[i] for i in owner], seqs, scores

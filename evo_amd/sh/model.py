@@ -13,6 +13,7 @@ There is no CPU fallback here: with no `ops` injected and no usable HIP library 
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import weakref
 from typing import Dict, List, Optional, Tuple
@@ -23,6 +24,20 @@ import torch.nn as nn
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
 from .cache import InferenceParams, RecurrentInferenceParams
 from .utils import dotdict
+
+
+@contextlib.contextmanager
+def capture_graph(graph):
+    """`torch.cuda.graph(graph)` whose capture BEGINS outside inference mode, whatever mode the caller is in (decode steps run under
+    inference mode; the body of the `with` stays in the caller's mode).  torch creates the capture state of its random generator with the
+    first live graph, in the mode capture_begin runs in, and keeps it while any graph lives: created under inference mode it is an
+    inference tensor, and every later capture outside inference mode, anywhere in the process, fails on its in-place update for as long
+    as that graph lives.  Created here it is an ordinary tensor, which either mode may update.  Every capture of this package (the decode
+    graph below, the decode pool's step) goes through here, so that they agree."""
+    with contextlib.ExitStack() as stack:
+        with torch.inference_mode(False):
+            stack.enter_context(torch.cuda.graph(graph))
+        yield
 
 
 def _cfg(config, key, default):
@@ -1033,7 +1048,7 @@ class StripedHyena(nn.Module):
                 self._inv_freq(dev)
                 g = torch.cuda.CUDAGraph()
                 try:
-                    with torch.cuda.graph(g):
+                    with capture_graph(g):
                         h = self.hidden_states(st["ids"], ipd)
                         st["logits"] = self.ops.linear(h, self.unembed.weight, None).view(B, 1, self.vocab_size)
                         st["pos"].add_(1)

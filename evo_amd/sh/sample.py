@@ -239,3 +239,58 @@ def sample_ctl(logits: torch.Tensor, top_k: int, top_p: float, temperature: floa
         return None, cnt, FINISH_LENGTH
     tok = int(sample_seeded(logits, top_k, top_p, temperature, seed, stream, cnt, allowed))
     return tok, cnt + 1, finish_reason(list(history) + [tok], limit, stop_tokens, stop_sequences, stop_frame)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Constrained generation: the written specification of `evo_sample_rows_dfa_f32` (csrc/sample.hip).  A row stands in
+# state `state` of an automaton `table` [n_states, 8] over the tokens `alphabet` (at most 8): table[q][a] is what drawing alphabet[a] in
+# state q does -- >= 0 the next state, DFA_ACCEPT the constraint is complete, any other negative value forbidden.  The state's permitted
+# tokens, intersected with the global allow mask, are the allow set of the draw of `sample_ctl`; the drawn token moves the state.
+
+FINISH_CONSTRAINT, FINISH_DEAD_END = 4, 5
+FINISH_NAMES_ALL = {**FINISH_NAMES, FINISH_CONSTRAINT: "constraint", FINISH_DEAD_END: "dead_end"}
+DFA_ACCEPT = -2
+DFA_MAX_SYMBOLS = 8
+
+
+def dfa_allowed(table, state: int, alphabet, allowed=None) -> torch.Tensor:
+    """bool [512]: the tokens state `state` permits (a next state or DFA_ACCEPT on their symbol), and `allowed` (bool [512] or None)
+    permits too.  A state outside the table permits nothing."""
+    mask = torch.zeros(VOCAB_BITS, dtype=torch.bool)
+    if 0 <= int(state) < len(table):
+        for a, t in enumerate(alphabet):
+            nxt = int(table[int(state)][a])
+            if nxt >= 0 or nxt == DFA_ACCEPT:
+                mask[int(t)] = True
+    if allowed is not None:
+        mask &= torch.as_tensor(allowed, dtype=torch.bool)
+    return mask
+
+
+def sample_dfa(logits: torch.Tensor, top_k: int, top_p: float, temperature: float, seed: int, stream: int, history, limit: int, table,
+               state, alphabet, allowed=None, stop_tokens=(), stop_sequences=(), stop_frame: int = 1, hist_len=None, base: int = 0):
+    """One launch of the automaton kernel for one ACTIVE row -> (token or None, tokens recorded now, finish, new state).  `table` is the
+    whole device table, `base` the row of this row's state 0 (base < 0: the row is unconstrained -- `sample_ctl`, the state untouched),
+    `state` relative to it.  After `sample_ctl`'s own "nothing left to draw" check: a negative state, base + state outside the table or
+    an empty allow set is a dead end -- FINISH_DEAD_END, nothing drawn, count and state unchanged.  Otherwise the draw of `sample_ctl`
+    from the state's set; drawing an ACCEPT edge leaves the state and ends the job with FINISH_CONSTRAINT unless a stop token or an
+    in-frame stop pattern (which rank first) end it on the same token; the limit ranks last."""
+    cnt = len(history)
+    if int(base) < 0:
+        return sample_ctl(logits, top_k, top_p, temperature, seed, stream, history, limit, allowed, stop_tokens, stop_sequences,
+                          stop_frame, hist_len) + (state,)
+    if cnt >= int(limit) or (hist_len is not None and cnt >= int(hist_len)):
+        return None, cnt, FINISH_LENGTH, state
+    r = int(base) + int(state)
+    allow = dfa_allowed(table, r if int(state) >= 0 else -1, alphabet, allowed)
+    if not bool(allow.any()):
+        return None, cnt, FINISH_DEAD_END, state
+    tok = int(sample_seeded(logits, top_k, top_p, temperature, seed, stream, cnt, allow))
+    nxt = int(table[r][[int(t) for t in alphabet].index(tok)])
+    # reasons 1 and 2 first (no limit: it ranks behind the constraint), then acceptance, then the limit
+    fin = finish_reason(list(history) + [tok], cnt + 2, stop_tokens, stop_sequences, stop_frame)
+    if not fin and nxt == DFA_ACCEPT:
+        fin = FINISH_CONSTRAINT
+    if not fin and cnt + 1 >= int(limit):
+        fin = FINISH_LENGTH
+    return tok, cnt + 1, fin, (state if nxt == DFA_ACCEPT else nxt)

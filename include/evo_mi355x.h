@@ -73,8 +73,10 @@ extern "C" {
  *  16: evo_hyena_state_at_zt added (the Hyena end state and FIR history at every row's OWN last token: ragged batched prefill); no
  *      signature changed.
  *  17: evo_sample_rows_ctl_f32 added (the seeded sampler with job control: stop tokens, in-frame stop patterns and per-row length
- *      limits decided on the device); no signature changed. */
-#define EVO_ABI_VERSION 17
+ *      limits decided on the device); no signature changed.
+ *  18: evo_sample_rows_dfa_f32 added (the control sampler under a per-row token automaton: constrained generation); no signature
+ *      changed. */
+#define EVO_ABI_VERSION 18
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -569,6 +571,46 @@ int evo_sample_rows_ctl_f32(const void* logits, int64_t logits_f32, int64_t ld, 
                             float* hist_logprob, int64_t hist_len, const int64_t* limit, const void* stop_mask,
                             const int32_t* stop_seq, const int32_t* stop_seq_len, int64_t n_seq, int64_t stop_frame,
                             int64_t* length, uint8_t* finish, int64_t S, int64_t V, void* stream);
+
+/* ---- seeded sampling with job control under a per-row token automaton: constrained generation --------------------------
+ * no reference counterpart (the reference samples freely; a template, a fixed protein or an open reading frame is enforced there by
+ * sampling and discarding)                                  [REF evo/generation.py:162-167; semantic_design/semantic_design.py:121-179]
+ * Call site: DecodePool's job-control path when `constraints` is given (evo_amd/pool.py: _sample_rows_ctl, the last node of the captured
+ * pooled step and the one-row launch that draws a job's first token).  Written specification: evo_amd/sh/sample.py dfa_allowed /
+ * sample_dfa.  One launch, no host reads, no allocation, no LDS beyond the draw's, plain vector stores, no atomics: capturable.
+ * Every argument of evo_sample_rows_ctl_f32 up to `finish` means what it means there.  In addition:
+ *   dfa_alphabet HOST int32 [n_sym], 1 <= n_sym <= 8 distinct token ids in [0, 512): the symbols.  Read before the launch, they travel
+ *               in its arguments (a captured graph keeps the alphabet it was captured with)
+ *   dfa_next    device int32 [n_states, 8], 16-byte aligned, row pitch 8 always: row q, column a is what drawing dfa_alphabet[a] in
+ *               state q does: >= 0 the next state (relative to the row's base), EVO_DFA_ACCEPT (-2) the constraint is complete, -1 (or
+ *               any other negative value) forbidden.  Columns >= n_sym are ignored.  1 <= n_states <= 2^27
+ *   dfa_base    device int64 [S]: the table row of the row's state 0; < 0 = the row is unconstrained
+ *   dfa_state   device int32 [S], in/out: the row's state, relative to its base
+ * Per active row, after evo_sample_rows_ctl_f32's own "nothing left to draw" check (unchanged: finish 3, no draw):
+ *   dfa_base[s] < 0: exactly evo_sample_rows_ctl_f32; dfa_state[s] is neither read nor written.
+ *   Otherwise r = dfa_base[s] + dfa_state[s].  With dfa_state[s] < 0, r outside [0, n_states), or no token both permitted by row r
+ *   and by `allow`, the row is at a DEAD END: active[s] = 0, length[s] = cnt, finish[s] = 5; nothing is drawn, nothing else is read or
+ *   written, count and dfa_state stay.
+ *   Otherwise the token is drawn from {dfa_alphabet[a] : next[r][a] >= 0 or == EVO_DFA_ACCEPT} intersected with `allow`, by
+ *   evo_sample_rows_ctl_f32's own device code: on the same logits and counters token, logprob_out (under the UNFILTERED row) and the
+ *   histories are bit-identical to that entry called with this set packed as its 64 allow bytes.  Then lane 0, with a the symbol drawn
+ *   and nxt = next[r][a]: nxt == EVO_DFA_ACCEPT leaves dfa_state[s] and makes reason 4 a candidate; otherwise dfa_state[s] = nxt.
+ *   The FIRST reason that holds ends the job: 1 stop token, 2 in-frame stop pattern, 4 constraint accepted, 3 n >= limit[s]; then
+ *   active[s] = 0, length[s] = n, finish[s] = the reason.  The token that ends a job is part of it.
+ * Inactive rows write nothing.  dfa_base and dfa_state need only their element's alignment (one-element slices, as the other per-row
+ * vectors).  Returns -1 for everything evo_sample_rows_ctl_f32 refuses, a null dfa_alphabet / dfa_next / dfa_base / dfa_state, n_sym
+ * outside 1 ... 8, an alphabet id outside [0, 512) or given twice, n_states < 1 or > 2^27, or dfa_next not 16-byte aligned. */
+#define EVO_DFA_MAX_SYMBOLS 8
+#define EVO_DFA_MAX_STATES (1 << 27)
+#define EVO_DFA_ACCEPT (-2)
+int evo_sample_rows_dfa_f32(const void* logits, int64_t logits_f32, int64_t ld, const int32_t* top_k, const float* top_p,
+                            const float* temperature, const void* allow, uint64_t seed, const int64_t* stream_id, int64_t* count,
+                            uint8_t* active, int64_t* ids_out, float* logprob_out, int64_t* hist_ids, float* hist_logits,
+                            float* hist_logprob, int64_t hist_len, const int64_t* limit, const void* stop_mask,
+                            const int32_t* stop_seq, const int32_t* stop_seq_len, int64_t n_seq, int64_t stop_frame,
+                            int64_t* length, uint8_t* finish, const int32_t* dfa_alphabet, int64_t n_sym,
+                            const int32_t* dfa_next, int64_t n_states, const int64_t* dfa_base, int32_t* dfa_state,
+                            int64_t S, int64_t V, void* stream);
 
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:

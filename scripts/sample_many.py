@@ -9,6 +9,12 @@ Jobs that end on their own: `--n-tokens` becomes a limit,
 
     python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT \
         --stop-sequences TAA,TAG,TGA --stop-frame 3 --scores-only --extra-columns
+
+Constrained generation: every generation fills an IUPAC template, encodes a protein, or is an open reading frame
+
+    python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --template ATGNNNNNNRRYNNNTAA
+    python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --encode-protein MKLS*
+    python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --orf-min-codons 50
 """
 import argparse
 import csv
@@ -57,10 +63,23 @@ def main(argv=None):
                                                               "tokens (3: in-frame codons)")
     ap.add_argument("--scores-only", action="store_true", help="keep no logits, on the device or on the host: the scores come from the "
                                                                "sampler's own log-probabilities")
-    ap.add_argument("--extra-columns", action="store_true", help="append Length and Finish (stop_token | stop_sequence | length) to the CSV")
+    ap.add_argument("--extra-columns", action="store_true", help="append Length and Finish (stop_token | stop_sequence | constraint | length) "
+                                                                 "to the CSV")
+    ap.add_argument("--template", default=None, metavar="IUPAC", help="every generation fills this template of IUPAC nucleotide codes, "
+                                                                      "e.g. ATGNNNNNNRRYNNNTAA")
+    ap.add_argument("--encode-protein", default=None, metavar="SEQ", help="every generation is DNA that encodes this protein (one-letter "
+                                                                          "residues, * = a stop codon): the model chooses the codons")
+    ap.add_argument("--orf-min-codons", type=int, default=None, metavar="N", help="every generation is an open reading frame: ATG, no in-frame "
+                                                                                  "stop codon before codon N, then the first one ends it")
+    ap.add_argument("--then", choices=["end", "free"], default="end", help="what follows a completed --template / --encode-protein: the "
+                                                                           "generation ends (default) or goes on unconstrained")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
+    if sum(x is not None for x in (args.template, args.encode_protein, args.orf_min_codons)) > 1:
+        ap.error("at most one of --template, --encode-protein and --orf-min-codons")
+    if args.then != "end" and args.template is None and args.encode_protein is None:
+        ap.error("--then applies to --template and --encode-protein only (an open reading frame ends at its stop codon)")
 
     import evo_amd
     from evo_amd.pool import DecodePool
@@ -80,6 +99,12 @@ def main(argv=None):
         ctl["stop_frame"] = args.stop_frame
     if args.scores_only:
         ctl["return_logits"] = False
+    if args.template is not None:
+        ctl["constraints"] = evo_amd.iupac_template(args.template, then=args.then)
+    elif args.encode_protein is not None:
+        ctl["constraints"] = evo_amd.encode_protein(args.encode_protein, then=args.then)
+    elif args.orf_min_codons is not None:
+        ctl["constraints"] = evo_amd.open_reading_frame(args.orf_min_codons)
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
                                         prepend_bos=args.prepend_bos, **ctl)
     extra = [[]] * len(seqs)
