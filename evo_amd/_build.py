@@ -27,6 +27,7 @@ EXPORTS = [
     "evo_probe_copy_f4", "evo_probe_mfma_bf16", "evo_pool_rows_bf16", "evo_sample_rows_f32",
     "evo_attn_fwd_prefix_bf16", "evo_attn_prefix_vt_bf16", "evo_attn_decode_prefix_bf16", "evo_rope_append_decode_at_bf16",
     "evo_hyena_state_at_zt", "evo_sample_rows_ctl_f32", "evo_sample_rows_dfa_f32",
+    "evo_kv_quant_fp8", "evo_rope_append_decode_fp8", "evo_attn_decode_fp8",
 ]
 
 

@@ -42,6 +42,7 @@ class Backend:
         "hyena_ct": ("hyena_ct", "rmsnorm_rows", "linear_t", "yblk_empty", "linear_residual_yblk_", "zt_shape_ok"),
         "norm_fold": ("nf_shape_ok", "zt_stream_rows_ok", "linear_rs", "linear_t_rs", "mlp_gate_rs", "linear_residual_stats_", "linear_residual_yblk_stats_"),
         "unembed_logprob": ("unembed_logprob", "unembed_logprob_ok"),
+        "kv_fp8": ("kv_quant_fp8", "rope_append_decode_fp8", "attention_decode_fp8"),     # the FP8 KV cache (InferenceParams.kv_dtype == "fp8")
     }   # (single kernels go by their own name: rope_append_decode, unembed_profile, attention_prefix, attention_prefix_vt, attention_decode_prefix)
 
     def supports(self, *names: str) -> bool:

@@ -793,6 +793,14 @@ __global__ __launch_bounds__(512) void attn_decode_combine_kernel(const float* _
     }
 }
 
+// the combine launch for callers in other files (csrc/kv_fp8.hip: the FP8 cache's decode attention writes the same partials)
+int evo_attn_decode_combine_launch(const float* part_o, const float* part_ml, void* o, int64_t B, int64_t H, int64_t n_splits,
+                                   void* stream) {
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)H, (unsigned)B), dim3(512), 0, (hipStream_t)stream, part_o, part_ml,
+                       (uint16_t*)o, (int)H, (int)n_splits);
+    return evo_launch_status();
+}
+
 static int attn_check_strides(int64_t q_sb, int64_t q_st, int64_t q_sh, int64_t k_sb, int64_t k_st, int64_t k_sh,
                               int64_t v_sb, int64_t v_st, int64_t v_sh) {
     return ((q_st % 8) || (k_st % 8) || (v_st % 8) || (q_sh % 8) || (k_sh % 8) || (v_sh % 8) || (q_sb % 8) ||

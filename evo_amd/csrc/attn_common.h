@@ -62,3 +62,7 @@ __device__ __forceinline__ void attn_block_map(const AttnArgs& a, int& qb, int& 
 
 // csrc/attn_w64.hip: the 4-wave / 64-rows-per-wave prefill kernel (geometry + launch)
 int evo_attn_w64_launch(AttnArgs a, int64_t B, void* vt_ws, void* stream);
+
+// csrc/attn.hip: attn_decode_combine_kernel on part_o [B, H, n_splits, 128] / part_ml [B, H, n_splits, 2] -> o [B, H, 128] bf16
+int evo_attn_decode_combine_launch(const float* part_o, const float* part_ml, void* o, int64_t B, int64_t H, int64_t n_splits,
+                                   void* stream);

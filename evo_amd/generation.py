@@ -23,16 +23,22 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
+from .sh.cache import check_kv_dtype
 from .sh.sample import allowed_mask, sample
 from .tokenizer import CharLevelTokenizer
 
 
 class Generator:
     def __init__(self, model, tokenizer: CharLevelTokenizer, top_k: int = 50, top_p: float = 0.7,
-                 temperature: float = 1.0, seed: int = None, allowed_tokens=None):
+                 temperature: float = 1.0, seed: int = None, allowed_tokens=None, kv_dtype: str = "bf16"):
         """`seed` / `allowed_tokens` (additions to the reference's interface, off by default): with either, tokens are drawn by
         the device sampler `evo_sample_rows_f32` -- row b of a batch draws from random stream `stream_offset + b`, reproducibly
-        under `seed`, and only from `allowed_tokens` (e.g. "ACGT") when given."""
+        under `seed`, and only from `allowed_tokens` (e.g. "ACGT") when given.  `kv_dtype="fp8"`: the caches this
+        generator creates hold their K/V in FP8 e4m3fn."""
+        self.kv_dtype = check_kv_dtype(kv_dtype)
+        if self.kv_dtype == "fp8" and not (hasattr(model, "ops") and model.ops.supports("kv_fp8")):
+            raise RuntimeError('kv_dtype="fp8" needs a compute backend with the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, '
+                               "attention_decode_fp8); this model's backend has none")
         self.model = model
         self.tokenizer = tokenizer
         self.top_k = top_k
@@ -49,7 +55,7 @@ class Generator:
         for store in (cache["mha"].key_value_memory_dict, cache["hyena"].fir_state_dict,
                       cache["hyena"].state_dict):
             for key, t in store.items():
-                store[key] = t.to(device)
+                store[key] = t.to(device)                    # (an Fp8KV record moves both of its tensors)
 
     def generate(self, device: str, input_string: str = None, input_ids: torch.Tensor = None,
                  num_tokens: int = 32, cached_generation: bool = True, force_prompt_threshold: int = None,
@@ -92,6 +98,7 @@ class Generator:
             inference_params_dict = self.model.initialize_inference_params()
             inference_params_dict["mha"].max_batch_size = B
             inference_params_dict["hyena"].max_batch_size = B
+            inference_params_dict["mha"].kv_dtype = self.kv_dtype
 
         if verbose:
             print("Starting generation...")
@@ -158,14 +165,16 @@ class Generator:
 def generate(prompt_seqs: List[str], model, tokenizer: CharLevelTokenizer, n_tokens: int = 100,
              temperature: float = 0.0, top_k: int = 1, top_p: float = 1.0, batched: bool = True,
              prepend_bos: bool = False, cached_generation: bool = False, force_prompt_threshold: int = None,
-             verbose: int = 1, device: str = "cuda:0", seed: int = None, allowed_tokens=None,
+             verbose: int = 1, device: str = "cuda:0", seed: int = None, allowed_tokens=None, kv_dtype: str = "bf16",
              **kwargs) -> Tuple[List[str], List[float]]:
     """Generate `n_tokens` after each prompt.  Equal-length prompts run as one batch when `batched`.
     Returns (generated strings, mean log-likelihood score per generation).  `seed`: the same call gives the same strings
-    (prompt number i draws from random stream i); `allowed_tokens`: the characters that may be generated, e.g. "ACGT"."""
+    (prompt number i draws from random stream i); `allowed_tokens`: the characters that may be generated, e.g. "ACGT"; `kv_dtype="fp8"`
+    (with `cached_generation`): the KV cache in FP8 e4m3fn."""
     if hasattr(model, "eval"):
         model.eval()
-    g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, allowed_tokens=allowed_tokens)
+    g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, allowed_tokens=allowed_tokens,
+                  kv_dtype=kv_dtype)
 
     same_len = all(len(s) == len(prompt_seqs[0]) for s in prompt_seqs)
     if batched and same_len:

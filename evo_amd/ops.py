@@ -72,10 +72,13 @@ _SIGNATURES = {
                                                                                                                          _PTR, _I64, _PTR, _I64,
                                                                                                                          _PTR, _PTR, _I64, _I64,
                                                                                                                          _PTR], _c.c_int),
+    "evo_kv_quant_fp8": ([_PTR] * 4 + [_I64] * 18 + [_PTR], _c.c_int),
+    "evo_rope_append_decode_fp8": ([_PTR] * 5 + [_F32] + [_I64] * 10 + [_F32, _PTR], _c.c_int),
+    "evo_attn_decode_fp8": ([_PTR] * 4 + [_I64] * 12 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 18        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 19        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
                         # `prefix_streams` counter is computed from it on the host)
 
@@ -1009,6 +1012,81 @@ class HipOps(Backend):
                 v_store.stride(0), v_store.stride(1), v_store.stride(2), pre_row.data_ptr(), pre_len.data_ptr(),
                 part_o.data_ptr(), part_ml.data_ptr(), n_pre_splits, n_splits, 0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()),
                 "evo_attn_decode_prefix_bf16")
+        return o
+
+    # ---- FP8 (e4m3fn) KV cache: the optional group "kv_fp8" (csrc/kv_fp8.hip) --------------------------------------
+    def _fp8_cache_args(self, op: str, kv, B: int, H: int) -> tuple:
+        """The cache operand of the three FP8 launches, checked: kv.data [>=B, cap, 2, H, 128] uint8, kv.scale [>=B, 2, H, cap] f32 with
+        contiguous tokens -> (data ptr, scale ptr, the seven strides)."""
+        d, s = kv.data, kv.scale
+        if not d.is_cuda or not s.is_cuda or d.dtype != torch.uint8 or s.dtype != torch.float32 or d.dim() != 5 or s.dim() != 4:
+            raise RuntimeError(f"{op}: the FP8 cache is data [B,cap,2,H,128] uint8 + scale [B,2,H,cap] f32 on a ROCm device")
+        cap = d.shape[1]
+        if d.shape[0] < B or tuple(d.shape[2:]) != (2, H, 128) or d.stride(-1) != 1 or s.shape[0] < B or tuple(s.shape[1:]) != (2, H, cap) \
+                or s.stride(-1) != 1:
+            raise RuntimeError(f"{op}: cache shapes {tuple(d.shape)} / {tuple(s.shape)} do not fit B = {B}, H = {H}, head dim 128")
+        self._check_address(d.data_ptr(), f"{op} kv.data")
+        self._check_address(s.data_ptr(), f"{op} kv.scale", 4)
+        return (d.data_ptr(), s.data_ptr(), d.stride(0), d.stride(1), d.stride(2), d.stride(3), s.stride(0), s.stride(1), s.stride(2))
+
+    def kv_quant_fp8(self, k: torch.Tensor, v: torch.Tensor, kv, t0: int = 0) -> None:
+        """Rows k, v [B, T, H, 128] bf16 (strided views: the thirds of a packed qkv) -> tokens t0 .. t0 + T - 1 of the FP8 cache `kv`
+        (an Fp8KV: data [>=B, cap, 2, H, 128] uint8, scale [>=B, 2, H, cap] f32), by the rule of include/evo_mi355x.h."""
+        self._need_strided("kv_quant_fp8", 4, k=k, v=v)
+        B, T, H, hd = k.shape
+        if hd != 128 or v.shape != k.shape:
+            raise RuntimeError("kv_quant_fp8: expects k / v [B, T, H, 128]")
+        ptrs = self._fp8_cache_args("kv_quant_fp8", kv, B, H)
+        cap = kv.data.shape[1]
+        if t0 < 0 or t0 + T > cap:
+            raise RuntimeError(f"kv_quant_fp8: tokens [{t0}, {t0 + T}) do not fit a cache of {cap}")
+        with self._t("kv_quant_fp8"):
+            _check(self.lib.evo_kv_quant_fp8(k.data_ptr(), v.data_ptr(), ptrs[0], ptrs[1], B, T, H, int(t0), cap,
+                                             k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2), *ptrs[2:],
+                                             _stream()), "evo_kv_quant_fp8")
+
+    def rope_append_decode_fp8(self, qkv: torch.Tensor, kv, pos: torch.Tensor, inv_freq: torch.Tensor, scaling: float,
+                               q_scale: float = 1.0) -> None:
+        """`rope_append_decode` on an FP8 cache: the same rotary on q and k of qkv [B,1,3,H,128] (bit for bit), then k and v quantised
+        into token pos[b] of `kv` (an Fp8KV).  One launch."""
+        self._need(qkv, torch.bfloat16, "rope_append_decode_fp8 qkv")
+        B, T, three, H, hd = qkv.shape
+        if T != 1 or three != 3 or hd != 128:
+            raise RuntimeError("rope_append_decode_fp8: expects qkv [B,1,3,H,128]")
+        ptrs = self._fp8_cache_args("rope_append_decode_fp8", kv, B, H)
+        if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() != B or not pos.is_contiguous():
+            raise RuntimeError("rope_append_decode_fp8 pos: need a contiguous device int64 tensor with B entries")
+        self._check_address(pos.data_ptr(), "rope_append_decode_fp8 pos", 8)
+        self._need(inv_freq, torch.float32, "rope_append_decode_fp8 inv_freq")
+        _check(self.lib.evo_rope_append_decode_fp8(qkv.data_ptr(), ptrs[0], ptrs[1], pos.data_ptr(), inv_freq.data_ptr(), float(scaling),
+                                                   B, H, hd, *ptrs[2:], float(q_scale), _stream()), "evo_rope_append_decode_fp8")
+
+    def attention_decode_fp8(self, q: torch.Tensor, kv, pos: Optional[torch.Tensor] = None, n_keys: Optional[int] = None,
+                             n_splits: Optional[int] = None, prescaled: bool = False) -> torch.Tensor:
+        """`attention_decode` on an FP8 cache: q [B,1,H,128] against `kv` (an Fp8KV).  With `pos` (device int64 [B] or [1]) row b sees
+        keys [0, pos[b]] and the cache's capacity is only the bound; without it every row sees the first `n_keys` keys."""
+        B, Tq, H, hd = q.shape
+        if pos is not None:
+            if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() not in (1, B):
+                raise RuntimeError("attention_decode_fp8 pos: need a device int64 tensor with 1 or B entries")
+            pos = (pos.reshape(1).expand(B) if pos.numel() == 1 and B > 1 else pos.reshape(-1)).contiguous()
+            self._check_address(pos.data_ptr(), "attention_decode_fp8 pos", 8)
+        if Tq != 1 or hd != 128:
+            raise RuntimeError("attention_decode_fp8: expects [B,1,H,128] queries")
+        self._need_strided("attention_decode_fp8", q=q)
+        ptrs = self._fp8_cache_args("attention_decode_fp8", kv, B, H)
+        cap = kv.data.shape[1]
+        Tk = cap if pos is not None or n_keys is None else int(n_keys)
+        if Tk < 1 or Tk > cap:
+            raise RuntimeError(f"attention_decode_fp8: {Tk} keys in a cache of {cap}")
+        n_splits = self._decode_splits(Tk) if n_splits is None else n_splits
+        o = torch.empty(B, 1, H, hd, dtype=torch.bfloat16, device=q.device)
+        part_o = torch.empty(B, H, n_splits, hd, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(B, H, n_splits, 2, dtype=torch.float32, device=q.device)
+        with self._t("attn_decode_fp8"):
+            _check(self.lib.evo_attn_decode_fp8(q.data_ptr(), ptrs[0], ptrs[1], o.data_ptr(), B, H, Tk, q.stride(0), q.stride(2), *ptrs[2:],
+                                                _ptr(pos), part_o.data_ptr(), part_ml.data_ptr(), n_splits,
+                                                0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()), "evo_attn_decode_fp8")
         return o
 
     def norm_linear(self, x: torch.Tensor, scale: torch.Tensor, eps: float, w: torch.Tensor,

@@ -41,6 +41,11 @@ Constrained generation (opt-in): `generate(constraints=...
 (evo_amd/constraints.py: an IUPAC template, a protein to encode, an open reading frame, concatenations).  The job-control path then ends
 with the launch `evo_sample_rows_dfa_f32`: a slot's state in its prompt's automaton decides what it may draw, the token moves the state,
 and completing the constraint ends the job -- all of it inside the captured step.
+
+`kv_dtype="fp8"` (opt-in): the pool's KV cache holds FP8 e4m3fn rows with one power-of-two scale each (`Fp8KV`: 8,448
+bytes per key and layer at 32 heads instead of 16,384; `stats["kv_bytes"]` reports what is held).  Prefills attend to their own bf16 keys
+and only store quantised; the step appends with `rope_append_decode_fp8` and attends with `attention_decode_fp8`.  A pool has one format
+for its life, so its captured step is captured on it.  Not with `share_prompt_kv` (ValueError): the prompt store stays bf16.
 """
 from __future__ import annotations
 
@@ -51,7 +56,8 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
-from .sh.cache import PromptStore
+from .backend import Backend
+from .sh.cache import Fp8KV, PromptStore, check_kv_dtype
 from .sh.model import capture_graph
 from .constraints import TokenConstraint
 from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
@@ -62,8 +68,9 @@ class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
-                 prefill_max_tokens: int = 32768, poll_every: int = 8):
+                 prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16"):
         self.model = model
+        self.kv_dtype = check_kv_dtype(kv_dtype)
         self.poll_every = int(poll_every)
         if self.poll_every < 1:
             raise ValueError("poll_every must be >= 1")
@@ -76,6 +83,14 @@ class DecodePool:
         if self.share_prompt_kv and not hasattr(getattr(model, "ops", None), "attention_decode_prefix"):
             raise RuntimeError("share_prompt_kv=True needs a compute backend with attention_decode_prefix (the decode attention over a "
                                "shared prompt store); this model's backend has none")
+        if self.kv_dtype == "fp8":                                   # 
+            if self.share_prompt_kv:
+                raise ValueError('kv_dtype="fp8" does not combine with share_prompt_kv=True: the prompt store and its grouped decode '
+                                 "attention are bf16")
+            ops = getattr(model, "ops", None)
+            if ops is None or not Backend.adopt(ops).supports("kv_fp8"):
+                raise RuntimeError('kv_dtype="fp8" needs a compute backend with the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, '
+                                   "attention_decode_fp8); this model's backend has none")
         self.tok = tokenizer
         self.n_slots = int(n_slots)
         self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
@@ -113,14 +128,21 @@ class DecodePool:
         ipd = m.initialize_inference_params()
         ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
         ipd["mha"].max_seqlen = capacity
+        ipd["mha"].kv_dtype = self.kv_dtype
         D, H, hd = m.hidden_size, m.num_heads, m.head_dim
         dt = m.embedding_layer.weight.dtype
         for i in m.attn_layer_idxs:
-            kv = torch.zeros(S, capacity, 2, H, hd, dtype=dt, device=dev)
-            if old is not None:
-                prev = old["mha"].key_value_memory_dict[i]
-                kv[:, : prev.shape[1]] = prev
+            prev = None if old is None else old["mha"].key_value_memory_dict[i]
+            if self.kv_dtype == "fp8":
+                kv = Fp8KV.zeros(S, capacity, H, hd, dev)
+                if prev is not None:
+                    kv.copy_rows_(slice(None), prev, slice(None), prev.shape[1])
+            else:
+                kv = torch.zeros(S, capacity, 2, H, hd, dtype=dt, device=dev)
+                if prev is not None:
+                    kv[:, : prev.shape[1]] = prev
             ipd["mha"].key_value_memory_dict[i] = kv
+        self.stats["kv_bytes"] = self._kv_bytes(ipd)
         for i in m.hyena_layer_idxs:
             if old is not None:
                 ipd["hyena"].fir_state_dict[i] = old["hyena"].fir_state_dict[i]
@@ -134,6 +156,12 @@ class DecodePool:
         self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
         if self.device_sampler:
             self._allocate_sampler_state()
+
+    @staticmethod
+    def _kv_bytes(ipd, store=None) -> int:
+        """Bytes held by the KV tensors of `ipd` (and of a prompt store): what stats["kv_bytes"] reports."""
+        kvs = list(ipd["mha"].key_value_memory_dict.values()) + ([] if store is None else list(store.kv.values()))
+        return sum(kv.nbytes() if isinstance(kv, Fp8KV) else kv.numel() * kv.element_size() for kv in kvs)
 
     def _allocate_sampler_state(self) -> None:
         m, S, dev = self.model, self.n_slots, self.device
@@ -184,6 +212,7 @@ class DecodePool:
         self.ipd, self.capacity, self.store, self.store_cap = ipd, n_tokens, st, p_max
         self.store_refs, self._store_prompt, self._slot_row = [0] * R, [None] * R, [-1] * S
         self.stats["store_rows"] = R
+        self.stats["kv_bytes"] = self._kv_bytes(self.ipd, self.store)
         self._graph = None
         self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
         self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
@@ -249,6 +278,7 @@ class DecodePool:
         m = self.model
         tmp = m.initialize_inference_params()
         tmp["mha"].max_seqlen = ids.shape[1]
+        tmp["mha"].kv_dtype = self.kv_dtype
         with torch.inference_mode():
             logits, tmp = m(ids, inference_params_dict=tmp)
         self.stats["prefills"] += 1
@@ -282,7 +312,8 @@ class DecodePool:
         T = max(lens)
         ids = torch.stack([torch.cat([encoded[pi][0], encoded[pi][0, -1:].expand(T - n)]) for pi, n in zip(group, lens)])
         with torch.inference_mode():
-            logits, tmp = self.model.prefill_ragged(ids, lens, pad_to=self.PREFILL_PAD)
+            fp8 = {} if self.kv_dtype == "bf16" else {"kv_dtype": self.kv_dtype}
+            logits, tmp = self.model.prefill_ragged(ids, lens, pad_to=self.PREFILL_PAD, **fp8)
         self.stats["prefills"] += 1
         self.stats["prefill_pad_tokens"] += len(group) * (-(-T // self.PREFILL_PAD) * self.PREFILL_PAD) - sum(lens)
         return logits.float(), tmp
@@ -290,7 +321,11 @@ class DecodePool:
     def _install(self, slot: int, tmp: dict, P: int, row: int = 0) -> None:
         m = self.model
         for i in m.attn_layer_idxs:
-            self.ipd["mha"].key_value_memory_dict[i][slot, :P] = tmp["mha"].key_value_memory_dict[i][row, :P]
+            dst, src = self.ipd["mha"].key_value_memory_dict[i], tmp["mha"].key_value_memory_dict[i]
+            if isinstance(dst, Fp8KV):
+                dst.copy_rows_(slot, src, row, P)                        # both tensors of the layer
+            else:
+                dst[slot, :P] = src[row, :P]
         for i in m.hyena_layer_idxs:
             self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
             self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
@@ -805,7 +840,7 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
-                poll_every: int = 8, constraints=None):
+                poll_every: int = 8, constraints=None, kv_dtype: str = "bf16"):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
@@ -813,9 +848,11 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     together are prefilled in one forward, right-padded.  `n_tokens` as a sequence (one limit per prompt),
     `stop_tokens`, `stop_sequences` / `stop_frame` and `return_logits=False`: jobs that end on their own (see
     `DecodePool.generate`).  `constraints`: one `TokenConstraint` (evo_amd/constraints.py) for every prompt, or one (or None) per prompt --
-    constrained generation on the device."""
+    constrained generation on the device.  `kv_dtype="fp8"`: the pool's KV cache in FP8 e4m3fn, about half the bytes
+    (not with `share_prompt_kv`)."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
-                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every)
+                      allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every,
+                      kv_dtype=kv_dtype)
     ctl = {}
     if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)

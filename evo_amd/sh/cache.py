@@ -3,6 +3,7 @@
 from dataclasses import dataclass, field
 from typing import Optional
 
+import torch
 from torch import Tensor
 
 
@@ -27,14 +28,66 @@ class PromptStore:
     own_pos: Optional[Tensor] = None
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
+def check_kv_dtype(kv_dtype) -> str:
+    """`kv_dtype` if it names a cache format; ValueError otherwise (raised before any device work)."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+    return kv_dtype
+
+
+@dataclass(eq=False)
+class Fp8KV:
+    """One attention layer's FP8 (e4m3fn) KV cache: data [B, cap, 2, H, 128] uint8 -- the bf16 cache's layout,
+    byte-wide -- and scale [B, 2, H, cap] f32, one power of two per cached row (token-contiguous per head).  The value of
+    key_value_memory_dict[layer] when InferenceParams.kv_dtype == "fp8"; compared by identity, like the tensor it stands for."""
+    data: Tensor
+    scale: Tensor
+
+    @classmethod
+    def zeros(cls, B: int, cap: int, H: int, hd: int, device) -> "Fp8KV":
+        return cls(torch.zeros(B, cap, 2, H, hd, dtype=torch.uint8, device=device), torch.ones(B, 2, H, cap, dtype=torch.float32, device=device))
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def nbytes(self) -> int:
+        return self.data.numel() * self.data.element_size() + self.scale.numel() * self.scale.element_size()
+
+    def to(self, device) -> "Fp8KV":
+        return self if self.data.device == device else Fp8KV(self.data.to(device), self.scale.to(device))
+
+    def rows(self, B: int) -> "Fp8KV":
+        """The first B batch rows, as views."""
+        return Fp8KV(self.data[:B], self.scale[:B])
+
+    def copy_rows_(self, dst_b, src: "Fp8KV", src_b, n: int) -> None:
+        """Tokens [0, n) of batch row(s) `src_b` of `src` -> the same tokens of batch row(s) `dst_b` of this cache."""
+        self.data[dst_b, :n] = src.data[src_b, :n]
+        self.scale[dst_b, :, :, :n] = src.scale[src_b, :, :, :n]
+
+    def dequantize(self) -> Tensor:
+        """[B, cap, 2, H, 128] f32: byte * scale, exact."""
+        return self.data.view(torch.float8_e4m3fn).float() * self.scale.permute(0, 3, 1, 2).unsqueeze(-1)
+
+
 @dataclass
 class InferenceParams:
-    """Attention layers: key_value_memory_dict[layer] = [B_max, max_seqlen, 2, H, hd] bf16."""
+    """Attention layers: key_value_memory_dict[layer] = [B_max, max_seqlen, 2, H, hd] bf16, or with kv_dtype == "fp8" an Fp8KV record."""
     max_seqlen: int
     max_batch_size: int
     seqlen_offset: int = 0
     batch_size_offset: int = 0
     key_value_memory_dict: dict = field(default_factory=dict)
+    # "bf16" (default) or "fp8": the format of the KV cache (opt-in; DESIGN.md section 21)
+    kv_dtype: str = "bf16"
     lengths_per_sample: Optional[Tensor] = None
     # set: the rows continue the first `seqlen_offset` tokens of a shared reference -- attention reads that prefix from shared_prefix.kv and
     # no per-row KV buffer is allocated or written (StripedHyena._attn_block)

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
-from .cache import InferenceParams, RecurrentInferenceParams
+from .cache import Fp8KV, InferenceParams, RecurrentInferenceParams, check_kv_dtype
 from .utils import dotdict
 
 
@@ -680,24 +680,37 @@ class StripedHyena(nn.Module):
             self._tail_ix = cur
         return cur[1]
 
-    def _kv_buffer(self, cache: InferenceParams, i: int, B: int, need: int, like: torch.Tensor):
+    def _kv_buffer(self, cache: InferenceParams, i: int, B: int, need: int, like):
+        """Layer i's KV buffer with room for B rows of `need` tokens on `like`'s device: a bf16 tensor, or with cache.kv_dtype == "fp8" an
+        Fp8KV record (both of its tensors are allocated, grown and copied together)."""
         H, hd = self.num_heads, self.head_dim
         kv = cache.key_value_memory_dict.get(i)
+        fp8 = cache.kv_dtype == "fp8"
+        if kv is not None and isinstance(kv, Fp8KV) != fp8:
+            raise ValueError(f"layer {i}'s KV cache does not have the format kv_dtype = {cache.kv_dtype!r} names")
         cap_b = max(int(cache.max_batch_size or 1), B)
         if kv is None or kv.shape[0] < B or kv.shape[1] < need or kv.device != like.device:
             cap_t = max(int(cache.max_seqlen or 0), need)
             if kv is not None and kv.shape[1] < need:
                 cap_t = max(cap_t, 2 * kv.shape[1])           # grow geometrically past max_seqlen (a20)
-            new = torch.zeros(cap_b, cap_t, 2, H, hd, dtype=like.dtype, device=like.device)
-            if kv is not None:
-                b0, t0 = min(kv.shape[0], cap_b), min(kv.shape[1], cap_t)
-                new[:b0, :t0] = kv[:b0, :t0].to(like.device)
+            if fp8:
+                new = Fp8KV.zeros(cap_b, cap_t, H, hd, like.device)
+                if kv is not None:
+                    b0, t0 = min(kv.shape[0], cap_b), min(kv.shape[1], cap_t)
+                    new.data[:b0, :t0] = kv.data[:b0, :t0].to(like.device)
+                    new.scale[:b0, :, :, :t0] = kv.scale[:b0, :, :, :t0].to(like.device)
+            else:
+                new = torch.zeros(cap_b, cap_t, 2, H, hd, dtype=like.dtype, device=like.device)
+                if kv is not None:
+                    b0, t0 = min(kv.shape[0], cap_b), min(kv.shape[1], cap_t)
+                    new[:b0, :t0] = kv[:b0, :t0].to(like.device)
             cache.key_value_memory_dict[i] = kv = new
         return kv
 
     def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None):
         """One attention block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  After Wqkv, by the cache:
-        per-row decode step (pos_tensor), shared-prefix attention, scalar-offset decode step, causal attention."""
+        per-row decode step (pos_tensor), shared-prefix attention, scalar-offset decode step, causal attention; an FP8
+        cache (cache.kv_dtype == "fp8") takes _attn_fp8 for all of them."""
         ops = self.ops
         D, H, hd = self.hidden_size, self.num_heads, self.head_dim
         mha = blk.inner_mha_cls
@@ -718,7 +731,9 @@ class StripedHyena(nn.Module):
         # ops.attn_prescale: the rotary kernel folds softmax_scale * log2(e) into its one rounding of q, the attention kernels take scores as exponents
         pre = bool(ops.attn_prescale)
         q_scale = ops.attn_q_scale(hd) if pre else 1.0
-        if pos is not None and T == 1:
+        if cache is not None and cache.kv_dtype != "bf16":
+            a = self._attn_fp8(i, qkv, B, T, cache, off, pos, mask, pre, q_scale)
+        elif pos is not None and T == 1:
             # one position PER ROW, in device memory (hipGraph replay, continuous batching); behind a prompt store the append goes to the row's OWN index
             kv = cache.key_value_memory_dict[i][:B]
             store = cache.prompt_store
@@ -757,6 +772,37 @@ class StripedHyena(nn.Module):
                     a = ops.attention(q, k, v, off, prescaled=pre)
         return self._finish_block(blk, x2d, a.view(B * T, D), mha.out_proj.weight, mha.out_proj.bias, nf, None if mask is None else mask[0],
                                   mfma=True)
+
+    def _attn_fp8(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float):
+        """_attn_block's attention on an FP8 KV cache (cache.kv_dtype == "fp8"): a fresh prefill attends to its own bf16
+        q / k / v exactly as with a bf16 cache -- only the store is quantised -- and a single-token step reads the FP8 cache."""
+        ops = self.ops
+        check_kv_dtype(cache.kv_dtype)
+        if not ops.supports("kv_fp8"):
+            raise RuntimeError('kv_dtype="fp8" needs a compute backend with the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, '
+                               "attention_decode_fp8); this model's backend has none")
+        for what, bad in (("shared_prefix", cache.shared_prefix is not None), ("prompt_store", cache.prompt_store is not None),
+                          ("a padding mask", mask is not None),
+                          (f"a resumed multi-token prefill (T = {T} at offset {off})", T > 1 and (off > 0 or pos is not None))):
+            if bad:
+                raise ValueError(f'kv_dtype="fp8" does not combine with {what}: the FP8 cache serves a fresh prefill and single-token steps')
+        q = qkv[:, :, 0]
+        if pos is not None:                                   # one position per row, in device memory (the pool, the captured step)
+            if pos.numel() != B:
+                raise ValueError(f'kv_dtype="fp8": pos_tensor must hold one position per row ({B}), got {pos.numel()}')
+            kv = cache.key_value_memory_dict[i].rows(B)
+            ops.rope_append_decode_fp8(qkv, kv, pos, self._inv_freq(qkv.device), self.rotary_scaling, q_scale=q_scale)
+            return ops.attention_decode_fp8(q, kv, pos=pos, prescaled=pre)
+        cos, sin = self._rotary(off, T, qkv.device)
+        ops.rope_(qkv, cos, sin, q_scale=q_scale)
+        kv = self._kv_buffer(cache, i, B, off + T, qkv).rows(B)
+        ops.kv_quant_fp8(qkv[:, :, 1], qkv[:, :, 2], kv, t0=off)
+        if off > 0:                                           # (T == 1) a single-token step at a scalar offset (Generator)
+            return ops.attention_decode_fp8(q, kv, n_keys=off + 1, prescaled=pre)
+        # a fresh prefill, one-token prompts included: its own keys, through the launch a bf16 cache would take
+        if T == 1:
+            return ops.attention_decode(q, qkv[:, :, 1], qkv[:, :, 2], prescaled=pre)
+        return ops.attention(q, qkv[:, :, 1], qkv[:, :, 2], 0, prescaled=pre)
 
     # ------------------------------------------------------------------ forward
     max_rows_per_pass = 160 * 1024     # rows (B T) of one stateless pass; larger batches run in row groups (hidden_states)
@@ -942,7 +988,8 @@ class StripedHyena(nn.Module):
         return self._unembed_output(h, B, T), inference_params_dict
 
     @torch.no_grad()
-    def prefill_ragged(self, ids: torch.Tensor, lengths, pad_to: int = 64, inference_params_dict=None, padding_mask=None):
+    def prefill_ragged(self, ids: torch.Tensor, lengths, pad_to: int = 64, inference_params_dict=None, padding_mask=None,
+                       kv_dtype: str = "bf16"):
         """Cached prefill of B prompts of UNEQUAL length in one forward: ids [B, T] right-padded with any valid token id, lengths [B] (host
         list or tensor, 1 <= L_b <= T) -> (last_logits [B, V] f32: the logits at every row's own last token, inference_params_dict).
 
@@ -953,7 +1000,9 @@ class StripedHyena(nn.Module):
         history at L_b - 1 -- comes from HipOps.hyena_state_at_zt.  The cache holds KV [B, T_pad, 2, H, hd] (rows >= L_b are pad keys: a
         decode that appends at its own position overwrites them), per-row FIR / modal states and `lengths` (device int64 [B]) on both
         records.  It is meant for per-row-position decode (`pos_tensor`, DecodePool); Generator's scalar seqlen_offset cannot describe it.
-        A padding mask or an existing cache raises ValueError: a ragged batch starts at t = 0."""
+        A padding mask or an existing cache raises ValueError: a ragged batch starts at t = 0.  `kv_dtype`: the format of the KV cache
+        returned ("fp8": DESIGN.md section 21)."""
+        check_kv_dtype(kv_dtype)
         if padding_mask is not None or inference_params_dict is not None:
             raise ValueError("prefill_ragged: no padding_mask and no existing cache (a ragged batch starts at t = 0; pads are ordinary tokens)")
         if ids.dim() != 2:
@@ -973,6 +1022,7 @@ class StripedHyena(nn.Module):
         ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = B
         ipd["mha"].max_seqlen = Tw
         ipd["mha"].lengths = ipd["hyena"].lengths = lens_d
+        ipd["mha"].kv_dtype = kv_dtype
         h = self.hidden_states(ids.contiguous(), ipd)                                         # [B Tw, D]
         last = h.index_select(0, torch.arange(B, device=dev) * Tw + lens_d - 1).contiguous()   # only the B rows that are read
         logits = self.ops.linear(last, self.unembed.weight, None).view(B, self.vocab_size)
@@ -1018,7 +1068,7 @@ class StripedHyena(nn.Module):
         # The captured graph is bound to the ADDRESSES of the KV, modal-state and FIR-state tensors.  `st` keeps strong
         # references to the cache objects and to every captured tensor and compares by identity: a later cache can then
         # neither recycle a CPython id() nor a caching-allocator address of a freed buffer.
-        same_bufs = (st is not None and st["B"] == B and st["mha"] is mha and st["hyena"] is hy
+        same_bufs = (st is not None and st["B"] == B and st["mha"] is mha and st["hyena"] is hy and st["kv_dtype"] == mha.kv_dtype
                      and all(mha.key_value_memory_dict.get(i) is t for i, t in st["kv"].items())
                      and all(hy.state_dict.get(i) is t for i, t in st["iir"].items())
                      and all(hy.fir_state_dict.get(i) is t for i, t in st["fir"].items()))
@@ -1035,7 +1085,7 @@ class StripedHyena(nn.Module):
                     self._dgraph_warm = (mha, hy, B)  # first step with these caches runs eagerly (warms M=B GEMMs)
                     return None
                 dev = self.device
-                st = {"B": B, "mha": mha, "hyena": hy,
+                st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype,
                       "ids": torch.zeros(B, 1, dtype=torch.int64, device=dev),
                       "pos": torch.zeros(B, dtype=torch.int64, device=dev),
                       "kv": {i: mha.key_value_memory_dict[i] for i in self.attn_layer_idxs},

@@ -75,8 +75,10 @@ extern "C" {
  *  17: evo_sample_rows_ctl_f32 added (the seeded sampler with job control: stop tokens, in-frame stop patterns and per-row length
  *      limits decided on the device); no signature changed.
  *  18: evo_sample_rows_dfa_f32 added (the control sampler under a per-row token automaton: constrained generation); no signature
- *      changed. */
-#define EVO_ABI_VERSION 18
+ *      changed.
+ *  19: evo_kv_quant_fp8, evo_rope_append_decode_fp8 and evo_attn_decode_fp8 added (an opt-in FP8 e4m3fn KV cache for decode: the
+ *      quantising stores and the decode attention that reads them, csrc/kv_fp8.hip); no signature changed. */
+#define EVO_ABI_VERSION 19
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -322,6 +324,52 @@ int evo_attn_decode_bf16(const void* q, const void* k, const void* v, void* o,
                          int64_t v_sb, int64_t v_st, int64_t v_sh,
                          const int64_t* dyn_pos, float* part_o, float* part_ml, int64_t n_splits,
                          float softmax_scale, void* stream);
+
+/* ---- FP8 (OCP e4m3fn) KV cache for decode (ABI 19; csrc/kv_fp8.hip) ----------------------------------------------------
+ * The three entries below stand where the reference calls flash_attn_with_kvcache  [REF evo/generation.py:138-155]; the reference has
+ * no quantised cache.  gfx950's FP8 is OCP e4m3fn (max 448, no infinities), not MI300's fnuz.
+ *   THE RULE.  A cached row is the 128 values of one (stream b, token t, K-or-V, head h).  With a = max |x_j| over the row, e is the
+ *   smallest integer with a * 2^-e <= 448, clamped to [-126, 120]; a = 0 gives e = 0.  Stored: 128 bytes RNE_e4m3fn(x_j * 2^-e) and one
+ *   f32 scale 2^e.  The product is exact and at most 448 in magnitude (one rounding, never saturated); byte * scale is exact in fp32.
+ *   In torch: (x.float() * 2.0 ** -e).to(torch.float8_e4m3fn).  Inputs are finite; NaN / Inf rows are unspecified.
+ *   THE CACHE OPERAND of a layer (the same seven strides in all three entries):
+ *     kv_data  [B, cap, 2, H, 128] bytes, BYTE strides d_sb (batch), d_st (token), d_sw (K | V), d_sh (head), each a multiple of 16
+ *              (d_st, d_sw, d_sh >= 128), 16-byte aligned;
+ *     kv_scale [B, 2, H, cap] f32, ELEMENT strides s_sb (batch), s_sw (K | V), s_sh (head); tokens are contiguous, so the 64 scales of
+ *              a key block are one 256-byte run for the wave that streams that head.
+ *   8,448 bytes per key and layer at H = 32 instead of 16,384.
+ *   All three return -1 without a launch on a null pointer, a misaligned pointer (16 bytes for data, 8 for pos / dyn_pos, 4 for f32
+ *   vectors), a stride that breaks the rules above, or a size <= 0.
+ *
+ * evo_kv_quant_fp8: rows [B, T, H, 128] bf16 of K and of V (strided views with element strides batch / token / head, each a multiple
+ * of 8: the two thirds of a packed qkv) -> cache tokens t0 .. t0 + T - 1 of every batch row, by the rule.  t0 + T <= cap or -1.  Serves
+ * the cached prefill at any T (ragged batches included) and the scalar-offset single-token step (rotary first, evo_rope_qk_bf16).
+ * Nothing outside those tokens is written. */
+int evo_kv_quant_fp8(const void* k, const void* v, void* kv_data, float* kv_scale,
+                     int64_t B, int64_t T, int64_t H, int64_t t0, int64_t cap,
+                     int64_t k_sb, int64_t k_st, int64_t k_sh, int64_t v_sb, int64_t v_st, int64_t v_sh,
+                     int64_t d_sb, int64_t d_st, int64_t d_sw, int64_t d_sh, int64_t s_sb, int64_t s_sw, int64_t s_sh,
+                     void* stream);
+/* evo_rope_append_decode_bf16 with the append quantised: rotary on q and k of qkv [B, 3, H, 128] in place at pos[b] -- the bits left in
+ * qkv are exactly that entry's, q_scale included -- then k (rotated) and v go to token pos[b] of the FP8 cache by the rule.  One
+ * launch, per-row device positions (< cap: the caller's bound), capturable.  hd must be 128.  There is no `widx` form: a prompt store
+ * stays bf16. */
+int evo_rope_append_decode_fp8(void* qkv, void* kv_data, float* kv_scale, const int64_t* pos, const float* inv_freq, float scaling,
+                               int64_t B, int64_t H, int64_t hd,
+                               int64_t d_sb, int64_t d_st, int64_t d_sw, int64_t d_sh, int64_t s_sb, int64_t s_sw, int64_t s_sh,
+                               float q_scale, void* stream);
+/* evo_attn_decode_bf16's contract on an FP8 cache: q [B, 1, H, 128] bf16 (q_sb, q_sh element strides), o [B, 1, H, 128] bf16
+ * contiguous, Tk = the keys (dyn_pos NULL) or the capacity bound (dyn_pos [B] device int64: row b sees keys [0, dyn_pos[b]]; nothing
+ * behind a row's position is read), the same part_o / part_ml workspace, the same split partition (split s takes the 64-key blocks s,
+ * s + n_splits, ...) and the same combine launch.  softmax_scale <= 0: pre-scaled queries.  The kernel (attn_decode_fp8_kernel) is the
+ * streaming form: a wave owns a split and keeps two 32-key halves (8 KiB each: 4 KiB K, 4 KiB V, 256 B of scales) in flight while it
+ * reduces a third; a key's scale multiplies its fp32 score once, a V row's scale its probability once.  It addresses keys with 32-bit
+ * byte offsets and has no second form: Tk * d_st >= 2^32 - 1 is refused (-1, no launch). */
+int evo_attn_decode_fp8(const void* q, const void* kv_data, const float* kv_scale, void* o,
+                        int64_t B, int64_t H, int64_t Tk, int64_t q_sb, int64_t q_sh,
+                        int64_t d_sb, int64_t d_st, int64_t d_sw, int64_t d_sh, int64_t s_sb, int64_t s_sw, int64_t s_sh,
+                        const int64_t* dyn_pos, float* part_o, float* part_ml, int64_t n_splits,
+                        float softmax_scale, void* stream);
 
 /* decode behind SHARED prompts (ABI 15): row b attends to the keys [0, pre_len[pre_row[b]]) of row pre_row[b] of a prompt store and
  * then to its OWN keys [0, own_pos[b]] -- what evo_attn_decode_bf16 returns on the concatenation, without a copy of the prompt per

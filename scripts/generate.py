@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--verbose", type=int, default=1)
     ap.add_argument("--seed", type=int, default=None, help="reproducible sampling: sample i draws from its own random stream i")
     ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16", help="format of the KV cache of a cached generation; fp8 (e4m3fn "
+                                                                                "with one scale per cached row) holds about half the bytes")
     args = ap.parse_args()
 
     import evo_amd
@@ -41,7 +43,7 @@ def main():
                                     temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                     cached_generation=args.cached_generation, batched=args.batched,
                                     prepend_bos=args.prepend_bos, device=args.device, verbose=args.verbose, seed=args.seed,
-                                    allowed_tokens=args.allowed_tokens)
+                                    allowed_tokens=args.allowed_tokens, **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}))
     print("Generated sequences:")
     for s in seqs:
         print(s)

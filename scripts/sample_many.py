@@ -73,9 +73,14 @@ def main(argv=None):
                                                                                   "stop codon before codon N, then the first one ends it")
     ap.add_argument("--then", choices=["end", "free"], default="end", help="what follows a completed --template / --encode-protein: the "
                                                                            "generation ends (default) or goes on unconstrained")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16", help="format of the pool's KV cache; fp8 (e4m3fn with one scale per "
+                                                                                "cached row) holds about half the bytes; not with "
+                                                                                "--share-prompt-kv")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
+    if args.kv_dtype != "bf16" and args.share_prompt_kv:
+        ap.error("--kv-dtype fp8 does not combine with --share-prompt-kv (the prompt store is bf16)")
     if sum(x is not None for x in (args.template, args.encode_protein, args.orf_min_codons)) > 1:
         ap.error("at most one of --template, --encode-protein and --orf-min-codons")
     if args.then != "end" and args.template is None and args.encode_protein is None:
@@ -89,7 +94,8 @@ def main(argv=None):
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
                       temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
-                      share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch)
+                      share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch,
+                      **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}))
     ctl = {}                                                  # any of these moves the job onto the job-control path
     if args.stop_tokens:
         ctl["stop_tokens"] = args.stop_tokens
