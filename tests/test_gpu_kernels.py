@@ -205,7 +205,8 @@ def test_hyena_prefill_matches_oracle(ops, B, T, D, H, seg):
 def test_hyena_single_pass_matches_oracle(ops, B, T, D, H):
     """evo_hyena_ct (block Toeplitz + aggregates on bf16 MFMA with hi/lo-split operands, fp32 block scan, carry on bf16
     MFMA with hi/lo-split states) vs the fp64 oracle -- outputs AND the end state (== prefill_via_modal_fft) -- and vs the
-    three-launch modal kernels on the same data."""
+    three-launch modal kernels on the same data.  (Gaussian data under a statistical bound; tests/test_gpu_hyena_exact.py holds the same
+    launches to the fp64 recurrence with no tolerance term, on inputs whose sums are exact.)"""
     prm = hyena_params(D, 60)
     z = bf(torch.randn(B, T, 3 * D, generator=gen(61)))
     y, st = run_ct(ops, z, prm, H, want_state=True)
@@ -582,7 +583,8 @@ def _zt_of(ops, z, B, T, pad_value=float("nan")):
 def test_hyena_ct_matches_oracle_in_every_launch_form(ops, B, T, D, H):
     """evo_hyena_ct (z^T in, a lane's eight steps loaded as 16 contiguous bytes, no window in LDS) vs the fp64 oracle -- outputs and
     end state, with and without FIR history and a carry-in state, the state-only walk, row-major and blocked y (every form gives
-    the same bits)."""
+    the same bits).  tests/test_gpu_hyena_exact.py runs the same forms on exact sums: every T of three ranges, equality with the fp64
+    recurrence rounded once."""
     from evo_amd.hyena_tables import mfma_operand_table
     prm = hyena_params(D, 100)
     fir_w, fir_b, poles, res, dskip = [t.to(DEV) for t in prm]
