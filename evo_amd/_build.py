@@ -28,6 +28,8 @@ EXPORTS = [
     "evo_attn_fwd_prefix_bf16", "evo_attn_prefix_vt_bf16", "evo_attn_decode_prefix_bf16", "evo_rope_append_decode_at_bf16",
     "evo_hyena_state_at_zt", "evo_sample_rows_ctl_f32", "evo_sample_rows_dfa_f32",
     "evo_kv_quant_fp8", "evo_rope_append_decode_fp8", "evo_attn_decode_fp8",
+    "evo_w_quant_fp8", "evo_linear_small_m_w8", "evo_norm_linear_small_m_w8", "evo_hyena_decode_fused_small_m_w8",
+    "evo_mlp_gate_small_m_w8", "evo_norm_mlp_gate_small_m_w8",
 ]
 
 

@@ -43,6 +43,9 @@ class Backend:
         "norm_fold": ("nf_shape_ok", "zt_stream_rows_ok", "linear_rs", "linear_t_rs", "mlp_gate_rs", "linear_residual_stats_", "linear_residual_yblk_stats_"),
         "unembed_logprob": ("unembed_logprob", "unembed_logprob_ok"),
         "kv_fp8": ("kv_quant_fp8", "rope_append_decode_fp8", "attention_decode_fp8"),     # the FP8 KV cache (InferenceParams.kv_dtype == "fp8")
+        # FP8 weights for the single-token step at 1-8 rows (InferenceParams.weight_dtype == "fp8"): w_quant_fp8(w) -> Fp8Weight; the others
+        # are linear / linear_residual_ / norm_linear / hyena_decode_fused / mlp_gate with the record in place of the weight(s)
+        "w_fp8": ("w_quant_fp8", "linear_w8", "linear_residual_w8_", "norm_linear_w8", "hyena_decode_fused_w8", "mlp_gate_w8"),
     }   # (single kernels go by their own name: rope_append_decode, unembed_profile, attention_prefix, attention_prefix_vt, attention_decode_prefix)
 
     def supports(self, *names: str) -> bool:

@@ -23,19 +23,34 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
-from .sh.cache import check_kv_dtype
+from .sh.cache import check_kv_dtype, check_weight_dtype, check_weight_rows
 from .sh.sample import allowed_mask, sample
 from .tokenizer import CharLevelTokenizer
 
 
+def check_fp8_weight_model(model) -> None:
+    """weight_dtype="fp8" on this model: RuntimeError without the "w_fp8" kernels, ValueError for a streamed layer the launches cannot
+    take (K % 16 != 0) -- from shapes alone, before any device work."""
+    ops = getattr(model, "ops", None)
+    if ops is None or not hasattr(ops, "supports") or not ops.supports("w_fp8"):
+        raise RuntimeError('weight_dtype="fp8" needs a compute backend with the "w_fp8" kernels (w_quant_fp8 and the *_w8 dense launches); '
+                           "this model's backend has none")
+    model.check_fp8_weights()
+
+
 class Generator:
     def __init__(self, model, tokenizer: CharLevelTokenizer, top_k: int = 50, top_p: float = 0.7,
-                 temperature: float = 1.0, seed: int = None, allowed_tokens=None, kv_dtype: str = "bf16"):
+                 temperature: float = 1.0, seed: int = None, allowed_tokens=None, kv_dtype: str = "bf16",
+                 weight_dtype: str = "bf16"):
         """`seed` / `allowed_tokens` (additions to the reference's interface, off by default): with either, tokens are drawn by
         the device sampler `evo_sample_rows_f32` -- row b of a batch draws from random stream `stream_offset + b`, reproducibly
         under `seed`, and only from `allowed_tokens` (e.g. "ACGT") when given.  `kv_dtype="fp8"`: the caches this
-        generator creates hold their K/V in FP8 e4m3fn."""
+        generator creates hold their K/V in FP8 e4m3fn.  `weight_dtype="fp8"`: the single-token steps on those caches
+        stream FP8 e4m3fn copies of the dense weights (batches of up to 8 prompts; DESIGN.md section 22: more memory, less time per token)."""
         self.kv_dtype = check_kv_dtype(kv_dtype)
+        self.weight_dtype = check_weight_dtype(weight_dtype)
+        if self.weight_dtype == "fp8":
+            check_fp8_weight_model(model)
         if self.kv_dtype == "fp8" and not (hasattr(model, "ops") and model.ops.supports("kv_fp8")):
             raise RuntimeError('kv_dtype="fp8" needs a compute backend with the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, '
                                "attention_decode_fp8); this model's backend has none")
@@ -76,6 +91,8 @@ class Generator:
 
         num_tokens = int(num_tokens)
         B, P = x.shape
+        if self.weight_dtype == "fp8":
+            check_weight_rows(B, "prompts in the batch")
         x_force = None
         n_forced = 0
         if force_prompt_threshold is not None and P > force_prompt_threshold:
@@ -99,6 +116,8 @@ class Generator:
             inference_params_dict["mha"].max_batch_size = B
             inference_params_dict["hyena"].max_batch_size = B
             inference_params_dict["mha"].kv_dtype = self.kv_dtype
+        if inference_params_dict is not None:                # (a cache handed in continues in this generator's weight format)
+            inference_params_dict["mha"].weight_dtype = self.weight_dtype
 
         if verbose:
             print("Starting generation...")
@@ -166,18 +185,21 @@ def generate(prompt_seqs: List[str], model, tokenizer: CharLevelTokenizer, n_tok
              temperature: float = 0.0, top_k: int = 1, top_p: float = 1.0, batched: bool = True,
              prepend_bos: bool = False, cached_generation: bool = False, force_prompt_threshold: int = None,
              verbose: int = 1, device: str = "cuda:0", seed: int = None, allowed_tokens=None, kv_dtype: str = "bf16",
-             **kwargs) -> Tuple[List[str], List[float]]:
+             weight_dtype: str = "bf16", **kwargs) -> Tuple[List[str], List[float]]:
     """Generate `n_tokens` after each prompt.  Equal-length prompts run as one batch when `batched`.
     Returns (generated strings, mean log-likelihood score per generation).  `seed`: the same call gives the same strings
     (prompt number i draws from random stream i); `allowed_tokens`: the characters that may be generated, e.g. "ACGT"; `kv_dtype="fp8"`
-    (with `cached_generation`): the KV cache in FP8 e4m3fn."""
+    (with `cached_generation`): the KV cache in FP8 e4m3fn; `weight_dtype="fp8"` (with `cached_generation`, batches of up to 8 prompts): the
+    decode steps stream FP8 copies of the dense weights."""
     if hasattr(model, "eval"):
         model.eval()
     g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, allowed_tokens=allowed_tokens,
-                  kv_dtype=kv_dtype)
+                  kv_dtype=kv_dtype, weight_dtype=weight_dtype)
 
     same_len = all(len(s) == len(prompt_seqs[0]) for s in prompt_seqs)
     if batched and same_len:
+        if weight_dtype == "fp8":
+            check_weight_rows(len(prompt_seqs), "prompts in the batch")
         batches = [prepare_batch(prompt_seqs, tokenizer, prepend_bos=prepend_bos, device=device)[0]]
     else:
         if verbose:

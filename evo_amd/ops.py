@@ -75,10 +75,16 @@ _SIGNATURES = {
     "evo_kv_quant_fp8": ([_PTR] * 4 + [_I64] * 18 + [_PTR], _c.c_int),
     "evo_rope_append_decode_fp8": ([_PTR] * 5 + [_F32] + [_I64] * 10 + [_F32, _PTR], _c.c_int),
     "evo_attn_decode_fp8": ([_PTR] * 4 + [_I64] * 12 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
+    "evo_w_quant_fp8": ([_PTR] * 3 + [_I64] * 2 + [_PTR], _c.c_int),
+    "evo_linear_small_m_w8": ([_PTR] * 6 + [_I64] * 3 + [_PTR, _I64, _PTR], _c.c_int),
+    "evo_norm_linear_small_m_w8": ([_PTR] * 6 + [_I64] * 3 + [_F32, _PTR], _c.c_int),
+    "evo_hyena_decode_fused_small_m_w8": ([_PTR] * 13 + [_I64] * 3 + [_F32, _PTR], _c.c_int),
+    "evo_mlp_gate_small_m_w8": ([_PTR] * 4 + [_I64] * 4 + [_PTR], _c.c_int),
+    "evo_norm_mlp_gate_small_m_w8": ([_PTR] * 5 + [_I64] * 3 + [_F32, _I64, _PTR], _c.c_int),
 }
 
 _LIB = None
-ABI_VERSION = 19        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
+ABI_VERSION = 20        # must equal EVO_ABI_VERSION in include/evo_mi355x.h (bumped on every signature change)
 ATTN_GROUP_ROWS = 8     # must equal EVO_ATTN_GROUP_ROWS there: batch rows per workgroup tile of attn_decode_group_kernel (the decode pool's
                         # `prefix_streams` counter is computed from it on the host)
 
@@ -1088,6 +1094,103 @@ class HipOps(Backend):
                                                 _ptr(pos), part_o.data_ptr(), part_ml.data_ptr(), n_splits,
                                                 0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()), "evo_attn_decode_fp8")
         return o
+
+    # ---- FP8 (e4m3fn) weights for the single-token step at 1-8 rows: the optional group "w_fp8" (csrc/gemv_fp8.hip) ----
+    # Each method is its bf16 namesake with an Fp8Weight record in place of the weight, and takes the same route: fused where the bf16
+    # launch is fused (Backend.fused_rows_ok), norm pass + plain launch where it is not.  Nothing here falls back to bf16 weights.
+    def _w8_args(self, op: str, x: torch.Tensor, rec) -> tuple:
+        """(data ptr, scale ptr) of `rec` checked against x [M, K]: uint8 [N, K] + f32 [N] on x's device, K % 16 == 0, 1 <= M <= 8."""
+        self._need(x, torch.bfloat16, f"{op} x")
+        d, sc = rec.data, rec.scale
+        M, K = x.shape
+        if not d.is_cuda or not sc.is_cuda or d.dtype != torch.uint8 or sc.dtype != torch.float32 or d.dim() != 2 or not d.is_contiguous() \
+                or not sc.is_contiguous() or tuple(sc.shape) != (d.shape[0],):
+            raise RuntimeError(f"{op}: an FP8 weight is data [N, K] uint8 + scale [N] f32, contiguous, on a ROCm device")
+        if d.shape[1] != K or K % 16 or not 1 <= M <= 8:
+            raise RuntimeError(f"{op}: x {tuple(x.shape)} against an FP8 weight {tuple(d.shape)}: need matching K % 16 == 0 and 1-8 rows")
+        self._check_address(d.data_ptr(), f"{op} weight data")
+        self._check_address(sc.data_ptr(), f"{op} weight scale", 4)
+        return d.data_ptr(), sc.data_ptr()
+
+    def w_quant_fp8(self, w: torch.Tensor):
+        """w [N, K] bf16 -> Fp8Weight(data [N, K] uint8, scale [N] f32) by the rule of include/evo_mi355x.h (ABI 20).  One launch."""
+        from .sh.cache import Fp8Weight
+        self._need(w, torch.bfloat16, "w_quant_fp8 w")
+        N, K = w.shape
+        if K % 16:
+            raise RuntimeError(f"w_quant_fp8: K = {K} is not a multiple of 16")
+        rec = Fp8Weight(torch.empty(N, K, dtype=torch.uint8, device=w.device), torch.empty(N, dtype=torch.float32, device=w.device))
+        self._launch("w_quant_fp8", "evo_w_quant_fp8", w.data_ptr(), rec.data.data_ptr(), rec.scale.data_ptr(), N, K)
+        return rec
+
+    def _linear_w8(self, x, rec, b, res):
+        wd, ws = self._w8_args("linear_w8", x, rec)
+        M, K = x.shape
+        N = rec.data.shape[0]
+        if res is not None:
+            self._need(res, torch.bfloat16, "linear_w8 residual")
+        y = res if res is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        self._launch("gemv_w8", "evo_linear_small_m_w8", x.data_ptr(), wd, ws, _ptr(b), _ptr(res), y.data_ptr(), M, N, K, None, 0)
+        return y
+
+    def linear_w8(self, x: torch.Tensor, rec, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [M, K] @ W^T (+ b) -> [M, N] bf16, W an Fp8Weight, 1 <= M <= 8."""
+        return self._linear_w8(x, rec, b, None)
+
+    def linear_residual_w8_(self, res: torch.Tensor, x: torch.Tensor, rec, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """res += x @ W^T (+ bias), in place, one rounding."""
+        return self._linear_w8(x, rec, bias, res)
+
+    def norm_linear_w8(self, x: torch.Tensor, scale: torch.Tensor, eps: float, rec, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """linear_w8(rmsnorm(x) * scale, W, b): one launch where norm_linear has one."""
+        M, K = x.shape
+        N = rec.data.shape[0]
+        if self.fused_rows_ok(M, K) and N > 4096 and self._bf16_ok(x, scale=scale):
+            wd, ws = self._w8_args("norm_linear_w8", x, rec)
+            y = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+            self._launch("gemv_norm_w8", "evo_norm_linear_small_m_w8", x.data_ptr(), scale.data_ptr(), wd, ws, _ptr(b), y.data_ptr(), M, N, K,
+                         float(eps))
+            return y
+        return self.linear_w8(self.rmsnorm(x, None, scale, eps), rec, b)
+
+    def hyena_decode_fused_w8(self, x, norm_scale, eps, rec, proj_b, fir_state, iir_state, fir_w, fir_b, poles, residues, dskip,
+                              n_heads: int) -> torch.Tensor:
+        """hyena_decode_fused on an FP8 projection weight: one launch at the rows where that has one, norm_linear_w8 + hyena_step otherwise."""
+        M, D = x.shape
+        ok = (self.fused_rows_ok(M, D) and self._bf16_ok(x, scale=norm_scale) and proj_b is not None
+              and fir_state.dtype == torch.bfloat16 and fir_state.is_contiguous() and fir_state.shape[0] == M
+              and iir_state.dtype == torch.complex64 and iir_state.is_contiguous() and iir_state.shape[0] == M
+              and D == n_heads * 128)
+        if not ok:
+            z = self.norm_linear_w8(x, norm_scale, eps, rec, proj_b)
+            return self.hyena_step(z, fir_state, iir_state, fir_w, fir_b, poles, residues, dskip, n_heads)
+        wd, ws = self._w8_args("hyena_decode_fused_w8", x, rec)
+        if rec.data.shape[0] != 3 * D:
+            raise RuntimeError(f"hyena_decode_fused_w8: the projection weight must be [3 D, D], got {tuple(rec.data.shape)}")
+        y = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
+        sr = torch.view_as_real(iir_state)
+        self._launch("gemv_hyena_w8", "evo_hyena_decode_fused_small_m_w8", x.data_ptr(), norm_scale.data_ptr(), wd, ws, proj_b.data_ptr(),
+                     fir_state.data_ptr(), sr.data_ptr(), fir_w.data_ptr(), fir_b.data_ptr(), poles.data_ptr(), residues.data_ptr(),
+                     dskip.data_ptr(), y.data_ptr(), M, D, n_heads, float(eps))
+        return y
+
+    def mlp_gate_w8(self, x: torch.Tensor, rec, norm_scale: Optional[torch.Tensor] = None, eps: float = 0.0, grouped: bool = False) -> torch.Tensor:
+        """a [M, I] = gelu(x' @ W1^T) * (x' @ W2^T) with [W1; W2] an Fp8Weight ([2 I, K]; `grouped`: in pack_gate_weights' row order);
+        x' = x, or rmsnorm(x) * norm_scale.  One launch where the rows allow the fold, norm pass + one launch otherwise."""
+        M, K = x.shape
+        I = rec.data.shape[0] // 2
+        if norm_scale is not None and not (self.fused_rows_ok(M, K) and self._bf16_ok(x, scale=norm_scale)):
+            x, norm_scale = self.rmsnorm(x, None, norm_scale, eps), None
+        wd, ws = self._w8_args("mlp_gate_w8", x, rec)
+        if I % 2 or (grouped and I % 32):
+            raise RuntimeError(f"mlp_gate_w8: inner size {I} does not fit the launch (even; a multiple of 32 in the grouped order)")
+        a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
+        if norm_scale is None:
+            self._launch("gemv_gate_w8", "evo_mlp_gate_small_m_w8", x.data_ptr(), wd, ws, a.data_ptr(), M, I, K, int(bool(grouped)))
+        else:
+            self._launch("gemv_gate_w8", "evo_norm_mlp_gate_small_m_w8", x.data_ptr(), norm_scale.data_ptr(), wd, ws, a.data_ptr(), M, I, K,
+                         float(eps), int(bool(grouped)))
+        return a
 
     def norm_linear(self, x: torch.Tensor, scale: torch.Tensor, eps: float, w: torch.Tensor,
                     b: Optional[torch.Tensor] = None, mfma: bool = False) -> torch.Tensor:

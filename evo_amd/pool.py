@@ -46,6 +46,11 @@ and completing the constraint ends the job -- all of it inside the captured step
 bytes per key and layer at 32 heads instead of 16,384; `stats["kv_bytes"]` reports what is held).  Prefills attend to their own bf16 keys
 and only store quantised; the step appends with `rope_append_decode_fp8` and attends with `attention_decode_fp8`.  A pool has one format
 for its life, so its captured step is captured on it.  Not with `share_prompt_kv` (ValueError): the prompt store stays bf16.
+
+`weight_dtype="fp8"` (opt-in; pools of up to 8 slots): the step streams FP8 e4m3fn copies of the dense weights (half
+the bytes; the copies sit beside the bf16 weights, which the prefills keep reading).  `stats["weight_dtype"]` and
+`stats["decode_weight_bytes"]` report the format and what a step streams.  It composes with every option above: only the dense
+launches of the step change.
 """
 from __future__ import annotations
 
@@ -57,7 +62,7 @@ import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
 from .backend import Backend
-from .sh.cache import Fp8KV, PromptStore, check_kv_dtype
+from .sh.cache import Fp8KV, PromptStore, check_kv_dtype, check_weight_dtype, check_weight_rows
 from .sh.model import capture_graph
 from .constraints import TokenConstraint
 from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
@@ -68,9 +73,14 @@ class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
-                 prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16"):
+                 prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
         self.model = model
         self.kv_dtype = check_kv_dtype(kv_dtype)
+        self.weight_dtype = check_weight_dtype(weight_dtype)
+        if self.weight_dtype == "fp8":                               # 
+            from .generation import check_fp8_weight_model
+            check_weight_rows(int(n_slots), "n_slots")
+            check_fp8_weight_model(model)
         self.poll_every = int(poll_every)
         if self.poll_every < 1:
             raise ValueError("poll_every must be >= 1")
@@ -101,6 +111,8 @@ class DecodePool:
         self.capacity = 0
         self._graph = None
         self.stats = {"steps": 0, "prefills": 0, "tokens": 0}
+        if hasattr(model, "decode_weight_bytes"):
+            self.stats.update({"weight_dtype": self.weight_dtype, "decode_weight_bytes": model.decode_weight_bytes(self.weight_dtype)})
         if self.share_prompt_kv:
             self.stats.update({"prompt_kv_installs": 0, "store_rows": 0, "prefix_streams": 0})
         if self.prefill_batch > 1:                                   # (prefills then counts forwards)
@@ -129,6 +141,7 @@ class DecodePool:
         ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
         ipd["mha"].max_seqlen = capacity
         ipd["mha"].kv_dtype = self.kv_dtype
+        ipd["mha"].weight_dtype = self.weight_dtype                  # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
         D, H, hd = m.hidden_size, m.num_heads, m.head_dim
         dt = m.embedding_layer.weight.dtype
         for i in m.attn_layer_idxs:
@@ -840,7 +853,7 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
-                poll_every: int = 8, constraints=None, kv_dtype: str = "bf16"):
+                poll_every: int = 8, constraints=None, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
@@ -852,7 +865,7 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     (not with `share_prompt_kv`)."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
                       allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every,
-                      kv_dtype=kv_dtype)
+                      kv_dtype=kv_dtype, weight_dtype=weight_dtype)
     ctl = {}
     if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)

@@ -78,6 +78,64 @@ class Fp8KV:
         return self.data.view(torch.float8_e4m3fn).float() * self.scale.permute(0, 3, 1, 2).unsqueeze(-1)
 
 
+WEIGHT_DTYPES = ("bf16", "fp8")
+W8_MAX_ROWS = 8         # batch rows the FP8-weight launches serve (csrc/gemv_fp8.hip: the dot2 forms; the 9-64-row MFMA forms are bf16 only)
+
+
+def check_weight_dtype(weight_dtype) -> str:
+    """`weight_dtype` if it names a format of the decode step's dense weights; ValueError otherwise (raised before any device work)."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
+    return weight_dtype
+
+
+def check_weight_rows(rows: int, what: str) -> None:
+    """ValueError when `rows` decode streams are more than the FP8-weight launches serve."""
+    if rows > W8_MAX_ROWS:
+        raise ValueError(f'weight_dtype="fp8" serves at most {W8_MAX_ROWS} rows per decode step, got {what} = {rows} (the 9-64-row launches '
+                         "are bf16 only)")
+
+
+def fp8_row_rule(w: Tensor):
+    """THE RULE of the FP8 formats (include/evo_mi355x.h, ABI 19 / 20) in torch, on rows w [N, K]: with a = max |w[n, :]|, e is the smallest
+    integer with a 2^-e <= 448, clamped to [-126, 120] (a = 0: e = 0) -> (bytes RNE_e4m3fn(w 2^-e) [N, K] uint8, scales 2^e [N] f32).
+    e comes from frexp (exact), never from a logarithm; inputs are finite."""
+    wf = w.float()
+    a = wf.abs().amax(dim=1)
+    m, ex = torch.frexp(a)                                   # a = m 2^ex, 0.5 <= m < 1;  448 = 0.875 * 2^9
+    e = ex - 9 + (m > 0.875).to(ex.dtype)
+    e = torch.where(a == 0, torch.zeros_like(e), e.clamp(-126, 120))
+    data = (wf * torch.exp2(-e.float())[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return data, torch.exp2(e.float())
+
+
+@dataclass(eq=False)
+class Fp8Weight:
+    """One dense weight of the decode step in FP8 e4m3fn: data [N, K] uint8 row-major and scale [N] f32, one power
+    of two per output feature, by fp8_row_rule."""
+    data: Tensor
+    scale: Tensor
+
+    @classmethod
+    def quantize(cls, w: Tensor) -> "Fp8Weight":
+        return cls(*fp8_row_rule(w))
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def nbytes(self) -> int:
+        return self.data.numel() * self.data.element_size() + self.scale.numel() * self.scale.element_size()
+
+    def dequantize(self, dtype=torch.bfloat16) -> Tensor:
+        """[N, K]: byte * scale -- exact in fp32, and exact in bf16 (a byte has four significant bits, the scale is a power of two)."""
+        return (self.data.view(torch.float8_e4m3fn).float() * self.scale[:, None]).to(dtype)
+
+
 @dataclass
 class InferenceParams:
     """Attention layers: key_value_memory_dict[layer] = [B_max, max_seqlen, 2, H, hd] bf16, or with kv_dtype == "fp8" an Fp8KV record."""
@@ -88,6 +146,9 @@ class InferenceParams:
     key_value_memory_dict: dict = field(default_factory=dict)
     # "bf16" (default) or "fp8": the format of the KV cache (opt-in)
     kv_dtype: str = "bf16"
+    # "bf16" (default) or "fp8": the dense weights the single-token steps on this cache stream (opt-in).  Read for
+    # the Hyena blocks of the step too: the choice belongs to the generation, and this record is the one every step carries
+    weight_dtype: str = "bf16"
     lengths_per_sample: Optional[Tensor] = None
     # set: the rows continue the first `seqlen_offset` tokens of a shared reference -- attention reads that prefix from shared_prefix.kv and
     # no per-row KV buffer is allocated or written (StripedHyena._attn_block)

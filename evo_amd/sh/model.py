@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
-from .cache import Fp8KV, InferenceParams, RecurrentInferenceParams, check_kv_dtype
+from .cache import Fp8KV, InferenceParams, RecurrentInferenceParams, check_kv_dtype, check_weight_dtype, check_weight_rows
 from .utils import dotdict
 
 
@@ -166,6 +166,7 @@ class StripedHyena(nn.Module):
         self._rot_cache: Dict[Tuple[int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._norms_folded = False                                 # fold_norms_: ONE weight set, the parameters are the folded weights
         self._dgraph = self._dgraph_warm = None                    # the captured decode step and the caches whose first step ran eagerly
+        self._w8 = None                                            # the FP8 copies of the decode step's dense weights (prepare_fp8_weights)
         self.decode_graph_replays = 0
         self._tail_ix = self._rows = self._inv_freq_dev = None     # small index tensors: _tail_split_index, _row_index, _inv_freq
         # debugging / parity hook: a list that receives the residual stream entering every block, or only the listed ones (num_layers = the final stream)
@@ -192,6 +193,7 @@ class StripedHyena(nn.Module):
                 raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(t.shape)} vs model {tuple(own[k].shape)}")
             own[k].data = t.detach()
         self._packed = False
+        self._w8 = None
         self._rot_cache.clear()
         from torch.nn.modules.module import _IncompatibleKeys
         return _IncompatibleKeys(missing, unexpected)
@@ -206,10 +208,12 @@ class StripedHyena(nn.Module):
         for _, b in self.named_buffers():
             b.data = b.data.to(torch.float32)
         self._packed = False
+        self._w8 = None
 
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
         self._packed = False
+        self._w8 = None
         self._rot_cache.clear()
         return out
 
@@ -236,6 +240,7 @@ class StripedHyena(nn.Module):
         without a K tail and the fused l1|l2 GEMM 3 % faster; the padded rows/columns are exact zeros, so
         gelu(0)*0 = 0 flows through and the result is bit-identical), contiguous [3D,3] FIR taps and [D,8,2]
         poles/residues.  l1/l2/l3 keep their state-dict entries as views of the padded buffers."""
+        self._w8 = None                                       # (an FP8 set quantised the buffers replaced here)
         for blk in self.blocks:
             l1, l2, l3 = blk.mlp.l1.weight, blk.mlp.l2.weight, blk.mlp.l3.weight
             inner, D_ = l1.shape
@@ -350,7 +355,60 @@ class StripedHyena(nn.Module):
                 blk.post_norm.scale.data = torch.ones_like(blk.post_norm.scale.data)
             self._norms_folded = True
             self._dgraph = None
+            self._w8 = None                                   # (an FP8 set built before the fold holds the unfolded weights: rebuilt on next use)
         return self
+
+    # ------------------------------------------------------------------ FP8 weights for the decode step
+    def _w8_sources(self, blk) -> dict:
+        """The dense weights a block's single-token step streams, as the bf16 decode launches read them."""
+        mlp = blk.mlp
+        if isinstance(blk, _HyenaBlock):
+            w_in, w_out = blk.projections.weight.data, blk.out_filter_dense.weight.data
+        else:
+            w_in, w_out = blk.inner_mha_cls.Wqkv.weight.data, blk.inner_mha_cls.out_proj.weight.data
+        # (l1 | l2: the padded plain order, or the grouped order after fold_norms_())
+        return {"in": w_in, "out": w_out, "w12": mlp._w12 if mlp._w12 is not None else mlp._w12g, "w3": mlp._w3}
+
+    def _padded_inner(self) -> int:
+        """The MLP's inner size as _pack_impl pads it (the K of l3 and half the N of l1 | l2 that the decode launches see)."""
+        inner = self.inner_size
+        return ((inner + 255) // 256) * 256 if inner >= 1024 else inner
+
+    def check_fp8_weights(self) -> None:
+        """ValueError naming the first streamed layer whose K is not a multiple of 16 (the FP8 launches' contract); shapes only."""
+        D, ipad = self.hidden_size, self._padded_inner()
+        for i, blk in enumerate(self.blocks):
+            names = ("projections", "out_filter_dense") if isinstance(blk, _HyenaBlock) else ("inner_mha_cls.Wqkv", "inner_mha_cls.out_proj")
+            for n, K in ((names[0], D), (names[1], D), ("mlp.l1 | mlp.l2", D), ("mlp.l3", ipad)):
+                if K % 16:
+                    raise ValueError(f'weight_dtype="fp8": blocks.{i}.{n} has K = {K}, not a multiple of 16 (include/evo_mi355x.h, ABI 20)')
+
+    def prepare_fp8_weights(self) -> "StripedHyena":
+        """Builds the FP8 (e4m3fn) copies of the dense weights a single-token step streams -- Hyena projections, Wqkv, out_filter_dense /
+        out_proj, l1 | l2 (plain, or grouped after fold_norms_()) and l3, in whatever state the model is in -- NOW instead of inside the
+        first `weight_dtype="fp8"` step: a server gets its out-of-memory error at load time.  The set sits BESIDE the bf16 weights, which
+        prefill, scoring and embeddings keep reading: at 7B 6.45 GB + 4 bytes per output row more memory, for half the bytes per step.
+        Embedding / unembedding, biases, norm scales, FIR taps, poles and residues stay as they are.  fold_norms_(), .to(...) and a new
+        state dict drop the set (it is rebuilt on next use)."""
+        ops = self.ops
+        if not ops.supports("w_fp8"):
+            raise RuntimeError('weight_dtype="fp8" needs a compute backend with the "w_fp8" kernels (' + ", ".join(Backend.OPTIONAL["w_fp8"])
+                               + "); this model's backend has none")
+        self.check_fp8_weights()
+        if self._w8 is None:
+            with torch.inference_mode(False), torch.no_grad():
+                if not self._packed and not self._norms_folded:
+                    self._pack()
+                self._w8 = [{k: ops.w_quant_fp8(w) for k, w in self._w8_sources(blk).items()} for blk in self.blocks]
+        return self
+
+    def decode_weight_bytes(self, weight_dtype: str = "bf16") -> int:
+        """Bytes of dense weights one single-token step streams in this format (the unembedding, bf16 in both, included); from shapes."""
+        D, ipad = self.hidden_size, self._padded_inner()
+        elems, rows = 4 * D * D + 3 * ipad * D, 5 * D + 2 * ipad          # per block: in [3D, D], out [D, D], l1 | l2 [2I, D], l3 [D, I]
+        es = self.embedding_layer.weight.element_size()
+        per_block = elems + 4 * rows if check_weight_dtype(weight_dtype) == "fp8" else elems * es
+        return self.num_layers * per_block + (self.unembed.weight.numel() * es if self.has_own_unembed else 0)
 
     def release_unused_weight_copies(self) -> int:
         """Drops the derived weight copies the CURRENT routing does not read (a long-lived server that once ran a sub-1,024-row
@@ -403,6 +461,9 @@ class StripedHyena(nn.Module):
             for k, v in vars(mod).items():
                 if k.startswith("_") and isinstance(v, torch.Tensor):
                     add(v)
+        for rec in (r for layer in (self._w8 or []) for r in layer.values()):
+            add(rec.data)
+            add(rec.scale)
         return total
 
     # ------------------------------------------------------------------ caches
@@ -461,19 +522,22 @@ class StripedHyena(nn.Module):
     # ------------------------------------------------------------------ blocks
     DECODE_ROWS = Backend.DECODE_ROWS         # batches this small take the fused single-token launches (Backend.fused_rows_ok)
 
-    def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False):
-        """x += y @ w^T + bias, the mixer's output projection (bias in the dense layer's epilogue: one rounding where the reference rounds twice)."""
-        if y.dim() == 4:                                     # the Hyena operator's blocked output (ops.hyena_ct)
+    def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False, w8=None):
+        """x += y @ w^T + bias, the mixer's output projection (bias in the dense layer's epilogue: one rounding where the reference rounds twice).
+        `w8`: the block's FP8 weight records (a single-token step with weight_dtype == "fp8"), else None."""
+        if w8 is not None:
+            self.ops.linear_residual_w8_(x2d, y, w8["out"], bias=bias)
+        elif y.dim() == 4:                                     # the Hyena operator's blocked output (ops.hyena_ct)
             self.ops.linear_residual_yblk_(x2d, y, w, bias=bias)
         else:
             self.ops.linear_residual_(x2d, y, w, mfma=mfma, bias=bias)
 
-    def _finish_block(self, blk, x2d, y, w, bias, nf, mask=None, mfma=False):
+    def _finish_block(self, blk, x2d, y, w, bias, nf, mask=None, mfma=False, w8=None):
         """Every block's end: x += y @ w^T + bias, then x += MLP(x).  `nf` (_nf_ok): returns the NEXT block's `rs`; else None.  `mask`: [B T, 1]."""
         if nf:
             return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, y, w, bias))
-        self._mixer_out_(blk, x2d, y, w, bias, mfma=mfma)
-        self._mlp_residual_(blk, x2d, mask)
+        self._mixer_out_(blk, x2d, y, w, bias, mfma=mfma, w8=w8)
+        self._mlp_residual_(blk, x2d, mask, w8=w8)
         return None
 
     # ---- RMSNorm folded into the dense layers around it (csrc/gemm.hip NF; DESIGN.md): `rs` = every row's 1 / (rms + eps), block to block
@@ -520,9 +584,13 @@ class StripedHyena(nn.Module):
             mlp._w12g = self.ops.pack_gate_weights(mlp._w12)
         return mlp._w12g
 
-    def _mlp_residual_(self, blk, x2d, mask=None):
+    def _mlp_residual_(self, blk, x2d, mask=None, w8=None):
         """x += MLP(post_norm(x)), in place; `mask` (flat [B T, 1]): upstream's (mixer out + u) * padding_mask first."""
         ops = self.ops
+        if w8 is not None:                                               # (single-token steps carry no mask)
+            a = ops.mlp_gate_w8(x2d, w8["w12"], blk.post_norm.scale, self.eps, grouped=blk.mlp._w12 is None)
+            ops.linear_residual_w8_(x2d, a, w8["w3"])
+            return
         self._gate_pack(blk, x2d.shape[0])
         if mask is not None:
             x2d.mul_(mask)
@@ -563,7 +631,7 @@ class StripedHyena(nn.Module):
         return (ops.hyena_ct_flag and ops.supports("hyena_ct") and x2d.is_cuda and w.dtype == torch.bfloat16
                 and w.is_contiguous() and ops.zt_shape_ok(B, T, w.shape[0], w.shape[1]))
 
-    def _hyena_block(self, i, blk, x2d, B, T, cache: Optional[RecurrentInferenceParams], mask=None, rs=None):
+    def _hyena_block(self, i, blk, x2d, B, T, cache: Optional[RecurrentInferenceParams], mask=None, rs=None, w8=None):
         """One Hyena block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  Three routes: the decode step,
         the channel-major operator, the modal form.  `mask` = (flat [B*T,1] bf16, [B,T] uint8) of upstream's
         padding_mask, or None: the projections output, the FIR output and the mixer output + residual are multiplied by it, as upstream's
@@ -573,18 +641,23 @@ class StripedHyena(nn.Module):
         if lens is not None and (have_state or mask is not None):
             raise ValueError("a ragged prefill (lengths) starts at t = 0 without a padding mask: no resumed prefill, no mask")
         nf = False
+        w8 = w8 if have_state and T == 1 else None            # (only the single-token cached route takes the FP8 launches)
         if have_state and T == 1:
-            y = self._hyena_decode_step(blk, x2d, cache.fir_state_dict[i], cache.state_dict[i])
+            y = self._hyena_decode_step(blk, x2d, cache.fir_state_dict[i], cache.state_dict[i], w8)
         elif mask is None and self._mfma_hyena_ok(B, T) and self._hyena_ct_ok(x2d, blk, B, T) and self._table_ok(blk):
             nf = self._nf_ok(B * T, mask)
             y = self._hyena_channel_major(i, blk, x2d, B, T, cache, lens, rs, nf)
         else:
             y = self._hyena_modal(i, blk, x2d, B, T, cache, lens, mask)
-        return self._finish_block(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf, None if mask is None else mask[0])
+        return self._finish_block(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf, None if mask is None else mask[0], w8=w8)
 
-    def _hyena_decode_step(self, blk, x, fir_state, iir_state):
-        """One token per row: norm + projections + FIR / modal step + gate in one launch; the two states advance in place."""
+    def _hyena_decode_step(self, blk, x, fir_state, iir_state, w8=None):
+        """One token per row: norm + projections + FIR / modal step + gate in one launch; the two states advance in place.  `w8`: the
+        block's FP8 weight records, or None (bf16: the scoring path's tail split always)."""
         f = blk.filter
+        if w8 is not None:
+            return self.ops.hyena_decode_fused_w8(x, blk.pre_norm.scale, self.eps, w8["in"], blk.projections.bias, fir_state, iir_state,
+                                                  f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, self.num_heads)
         return self.ops.hyena_decode_fused(x, blk.pre_norm.scale, self.eps, blk.projections.weight, blk.projections.bias, fir_state, iir_state,
                                            f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D, self.num_heads)
 
@@ -707,7 +780,7 @@ class StripedHyena(nn.Module):
             cache.key_value_memory_dict[i] = kv = new
         return kv
 
-    def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None):
+    def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None, w8=None):
         """One attention block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  After Wqkv, by the cache:
         per-row decode step (pos_tensor), shared-prefix attention, scalar-offset decode step, causal attention; an FP8
         cache (cache.kv_dtype == "fp8") takes _attn_fp8 for all of them."""
@@ -717,7 +790,11 @@ class StripedHyena(nn.Module):
         if mask is not None:                      # upstream AttentionBlock: u * padding_mask before and after the mixer
             x2d.mul_(mask[0])
         nf = T > 1 and self._nf_ok(B * T, mask)
-        if nf and rs is not None:
+        # (only the decode branch -- one token on a layer that holds keys -- takes the FP8 launches)
+        w8 = w8 if T == 1 and cache is not None and i in cache.key_value_memory_dict else None
+        if w8 is not None:
+            qkv = ops.norm_linear_w8(x2d, blk.pre_norm.scale, self.eps, w8["in"], mha.Wqkv.bias).view(B, T, 3, H, hd)
+        elif nf and rs is not None:
             wqkv_f = self._folded(mha, "_wqkv_f", mha.Wqkv.weight, blk.pre_norm.scale)
             qkv = ops.linear_rs(x2d, rs, wqkv_f, mha.Wqkv.bias, mha.Wqkv.weight, blk.pre_norm.scale, self.eps).view(B, T, 3, H, hd)
         else:
@@ -771,7 +848,7 @@ class StripedHyena(nn.Module):
                 else:
                     a = ops.attention(q, k, v, off, prescaled=pre)
         return self._finish_block(blk, x2d, a.view(B * T, D), mha.out_proj.weight, mha.out_proj.bias, nf, None if mask is None else mask[0],
-                                  mfma=True)
+                                  mfma=True, w8=w8)
 
     def _attn_fp8(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float):
         """_attn_block's attention on an FP8 KV cache (cache.kv_dtype == "fp8"): a fresh prefill attends to its own bf16
@@ -884,6 +961,10 @@ class StripedHyena(nn.Module):
         block i has finished (StripedHyena.embeddings pools the streams it asked for there)."""
         stop = self.num_layers if stop is None else stop
         rs = None
+        w8s = None
+        if T == 1 and mha_c is not None and check_weight_dtype(mha_c.weight_dtype) == "fp8":     # (DESIGN.md section 22)
+            check_weight_rows(B, "batch rows")
+            w8s = self.prepare_fp8_weights()._w8
         taps, tap_idxs = self.block_taps, self.block_tap_idxs
         for i in range(stop):
             blk = self.blocks[i]
@@ -891,9 +972,9 @@ class StripedHyena(nn.Module):
                 taps.append(h.clone())
             # rs: 1 / (rms + eps) of every row of h, from the epilogue of the dense layer that wrote it (None: the block norms h itself)
             if isinstance(blk, _AttentionBlock):
-                rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs)
+                rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs, w8=None if w8s is None else w8s[i])
             else:
-                rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs)
+                rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs, w8=None if w8s is None else w8s[i])
             if after_block is not None:
                 after_block(i, h)
         if stop == self.num_layers and taps is not None and (tap_idxs is None or self.num_layers in tap_idxs):
@@ -1069,6 +1150,7 @@ class StripedHyena(nn.Module):
         # references to the cache objects and to every captured tensor and compares by identity: a later cache can then
         # neither recycle a CPython id() nor a caching-allocator address of a freed buffer.
         same_bufs = (st is not None and st["B"] == B and st["mha"] is mha and st["hyena"] is hy and st["kv_dtype"] == mha.kv_dtype
+                     and st["weight_dtype"] == mha.weight_dtype
                      and all(mha.key_value_memory_dict.get(i) is t for i, t in st["kv"].items())
                      and all(hy.state_dict.get(i) is t for i, t in st["iir"].items())
                      and all(hy.fir_state_dict.get(i) is t for i, t in st["fir"].items()))
@@ -1085,7 +1167,7 @@ class StripedHyena(nn.Module):
                     self._dgraph_warm = (mha, hy, B)  # first step with these caches runs eagerly (warms M=B GEMMs)
                     return None
                 dev = self.device
-                st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype,
+                st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype, "weight_dtype": mha.weight_dtype,
                       "ids": torch.zeros(B, 1, dtype=torch.int64, device=dev),
                       "pos": torch.zeros(B, dtype=torch.int64, device=dev),
                       "kv": {i: mha.key_value_memory_dict[i] for i in self.attn_layer_idxs},
@@ -1095,6 +1177,8 @@ class StripedHyena(nn.Module):
                 st["pos"].fill_(off)
                 mha.pos_tensor = st["pos"]
                 self._row_index(B, dev)             # (allocated outside the capture)
+                if mha.weight_dtype == "fp8":
+                    self.prepare_fp8_weights()
                 self._inv_freq(dev)
                 g = torch.cuda.CUDAGraph()
                 try:

@@ -77,8 +77,11 @@ extern "C" {
  *  18: evo_sample_rows_dfa_f32 added (the control sampler under a per-row token automaton: constrained generation); no signature
  *      changed.
  *  19: evo_kv_quant_fp8, evo_rope_append_decode_fp8 and evo_attn_decode_fp8 added (an opt-in FP8 e4m3fn KV cache for decode: the
- *      quantising stores and the decode attention that reads them, csrc/kv_fp8.hip); no signature changed. */
-#define EVO_ABI_VERSION 19
+ *      quantising stores and the decode attention that reads them, csrc/kv_fp8.hip); no signature changed.
+ *  20: evo_w_quant_fp8, evo_linear_small_m_w8, evo_norm_linear_small_m_w8, evo_hyena_decode_fused_small_m_w8, evo_mlp_gate_small_m_w8
+ *      and evo_norm_mlp_gate_small_m_w8 added (opt-in FP8 e4m3fn WEIGHTS for the decode step at 1-8 rows, csrc/gemv_fp8.hip); no
+ *      signature changed. */
+#define EVO_ABI_VERSION 20
 int evo_abi_version(void);
 
 /* ---- embedding gather ------------------------------------------------------------------------
@@ -370,6 +373,54 @@ int evo_attn_decode_fp8(const void* q, const void* kv_data, const float* kv_scal
                         int64_t d_sb, int64_t d_st, int64_t d_sw, int64_t d_sh, int64_t s_sb, int64_t s_sw, int64_t s_sh,
                         const int64_t* dyn_pos, float* part_o, float* part_ml, int64_t n_splits,
                         float softmax_scale, void* stream);
+
+/* ---- FP8 (OCP e4m3fn) weights for the decode step at 1-8 rows (ABI 20; csrc/gemv_fp8.hip; no counterpart in the reference) -------------
+ * Opt-in: the bf16 entries above are untouched and remain the default.  At 1-8 batch rows a decode step streams every dense weight
+ * once and is bound by those bytes; these entries stream half of them.
+ *
+ * THE RULE (the KV cache's, ABI 19, with a weight row in place of a cache row; evo_amd/sh/cache.py fp8_row_rule states it in torch and
+ * both sides agree bit for bit).  A row is the K values of one output feature n of a dense layer W [N, K].  With a = max_k |W[n, k]|, e is the
+ * smallest integer with a 2^-e <= 448, clamped to [-126, 120]; a = 0 gives e = 0.  Stored: K bytes RNE_e4m3fn(W[n, k] 2^-e) and one
+ * f32 scale 2^e.  Inputs are finite.  W 2^-e is exact in fp32 and at most 448 in magnitude, so the conversion rounds once and never
+ * saturates; byte * scale is exact.  A dequantised row quantises to a record of the same VALUES (to the same bytes and scale unless its
+ * scaled maximum rounded down to the byte 224: then to every byte doubled under half the scale).  The rule commutes with any permutation
+ * of the rows: the grouped l1 | l2 order (evo_mlp_gate_mfma_bf16) needs no rule of its own.
+ *
+ * LAYOUT: w_data [N, K] uint8, row-major, 16-byte aligned; w_scale [N] f32.  K % 16 == 0: a lane's 16-byte load is 16 weights and
+ * meets two of x's 16-byte vectors.
+ *
+ * ARITHMETIC: the bf16 kernels' on the bytes -- two bytes become a packed bf16 pair in registers (exactly: every e4m3fn value is a
+ * bf16 value), v_dot2c_f32_bf16 accumulates in fp32 -- and the row's scale multiplies the REDUCED fp32 sum once per output element,
+ * before bias, residual, gate or Hyena step.  With the rule's power-of-two scales that product is exact, so an entry returns what its
+ * bf16 sibling's arithmetic returns on the dequantised weight, up to the order of the fp32 additions.  Scales that are no powers of
+ * two are accepted and cost one more rounding per element.
+ *
+ * The compute entries take their bf16 siblings' arguments with (w_data, w_scale) in place of w, and return -1 without a launch on a
+ * null or misaligned pointer (16 bytes; 4 for w_scale; bias / residual may be NULL where the sibling allows it), K % 16 != 0, M outside
+ * 1-8, or a size <= 0.  Rows 9-64 (the MFMA forms) exist for bf16 weights only.
+ *
+ * evo_w_quant_fp8: w [N, K] bf16 -> w_data, w_scale by the rule; each row is read from memory once.  Nothing else is written. */
+int evo_w_quant_fp8(const void* w, void* w_data, float* w_scale, int64_t N, int64_t K, void* stream);
+/* evo_linear_small_m_bf16 at 1 <= M <= 8: y = x W^T (+ bias) (+ residual, which may alias y), one rounding.  ws / ws_bytes are the
+ * sibling's workspace arguments and are not used (its 17-64-row forms have no FP8 counterpart). */
+int evo_linear_small_m_w8(const void* x, const void* w_data, const float* w_scale, const void* bias, const void* residual, void* y,
+                          int64_t M, int64_t N, int64_t K, void* ws, int64_t ws_bytes, void* stream);
+/* evo_norm_linear_small_m_bf16: RMSNorm folded in front.  1 <= M <= 4 at any K, 5 <= M <= 8 at K = 4096 (the LDS-staged form), as the
+ * sibling. */
+int evo_norm_linear_small_m_w8(const void* x, const void* scale, const void* w_data, const float* w_scale, const void* bias, void* y,
+                               int64_t M, int64_t N, int64_t K, float eps, void* stream);
+/* evo_hyena_decode_fused_small_m: pre-norm + projection + FIR / modal step + gate, states updated in place.  Same rows as above, D = K. */
+int evo_hyena_decode_fused_small_m_w8(const void* x, const void* norm_scale, const void* proj_data, const float* proj_scale,
+                                      const void* proj_b, void* fir_state, float* iir_state, const void* fir_w, const void* fir_b,
+                                      const float* poles, const float* residues, const void* dskip, void* y,
+                                      int64_t M, int64_t D, int64_t n_heads, float eps, void* stream);
+/* evo_mlp_gate_small_m_bf16's dot2 form: a = gelu(x W1^T) * (x W2^T), w12 = [W1; W2] plain or grouped (`grouped` != 0: I % 32 == 0).
+ * 1 <= M <= 8 at any K (the sibling hands 5-8 rows to its MFMA form; here they stay on the dot2 stream). */
+int evo_mlp_gate_small_m_w8(const void* x, const void* w12_data, const float* w12_scale, void* a, int64_t M, int64_t I, int64_t K,
+                            int64_t grouped, void* stream);
+/* evo_norm_mlp_gate_small_m_bf16: the same with RMSNorm folded in front; rows as evo_norm_linear_small_m_w8. */
+int evo_norm_mlp_gate_small_m_w8(const void* x, const void* scale, const void* w12_data, const float* w12_scale, void* a,
+                                 int64_t M, int64_t I, int64_t K, float eps, int64_t grouped, void* stream);
 
 /* decode behind SHARED prompts (ABI 15): row b attends to the keys [0, pre_len[pre_row[b]]) of row pre_row[b] of a prompt store and
  * then to its OWN keys [0, own_pos[b]] -- what evo_attn_decode_bf16 returns on the concatenation, without a copy of the prompt per

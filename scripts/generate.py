@@ -34,7 +34,13 @@ def main():
     ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16", help="format of the KV cache of a cached generation; fp8 (e4m3fn "
                                                                                 "with one scale per cached row) holds about half the bytes")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the decode steps of a cached generation "
+                                                                                    "stream; fp8 (e4m3fn, one scale per output row) halves "
+                                                                                    "the bytes per token and adds an FP8 copy to memory; "
+                                                                                    "up to 8 samples per batch")
     args = ap.parse_args()
+    if args.weight_dtype != "bf16" and args.batched and args.n_samples > 8:
+        ap.error("--weight-dtype fp8 serves batches of up to 8 samples")
 
     import evo_amd
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)
@@ -43,7 +49,8 @@ def main():
                                     temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                                     cached_generation=args.cached_generation, batched=args.batched,
                                     prepend_bos=args.prepend_bos, device=args.device, verbose=args.verbose, seed=args.seed,
-                                    allowed_tokens=args.allowed_tokens, **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}))
+                                    allowed_tokens=args.allowed_tokens, **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}),
+                                    **({} if args.weight_dtype == "bf16" else {"weight_dtype": args.weight_dtype}))
     print("Generated sequences:")
     for s in seqs:
         print(s)

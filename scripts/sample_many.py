@@ -76,9 +76,14 @@ def main(argv=None):
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16", help="format of the pool's KV cache; fp8 (e4m3fn with one scale per "
                                                                                 "cached row) holds about half the bytes; not with "
                                                                                 "--share-prompt-kv")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the pool's decode step streams; fp8 (e4m3fn, "
+                                                                                    "one scale per output row) halves the bytes per step and "
+                                                                                    "adds an FP8 copy to memory; --n-slots up to 8")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
+    if args.weight_dtype != "bf16" and args.n_slots > 8:
+        ap.error("--weight-dtype fp8 serves pools of up to 8 slots")
     if args.kv_dtype != "bf16" and args.share_prompt_kv:
         ap.error("--kv-dtype fp8 does not combine with --share-prompt-kv (the prompt store is bf16)")
     if sum(x is not None for x in (args.template, args.encode_protein, args.orf_min_codons)) > 1:
@@ -95,7 +100,8 @@ def main(argv=None):
     pool = DecodePool(m.model, m.tokenizer, n_slots=args.n_slots, top_k=args.top_k, top_p=args.top_p,
                       temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
                       share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch,
-                      **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}))
+                      **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}),
+                      **({} if args.weight_dtype == "bf16" else {"weight_dtype": args.weight_dtype}))
     ctl = {}                                                  # any of these moves the job onto the job-control path
     if args.stop_tokens:
         ctl["stop_tokens"] = args.stop_tokens
