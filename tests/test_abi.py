@@ -74,6 +74,24 @@ def test_argument_validation_needs_no_gpu():
     assert lib.evo_attn_fwd_causal_bf16(None, None, None, None, 1, 1, 4, 4, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1.0, None, None) == -1
 
 
+def test_fp8_decode_attention_refuses_one_stride_step_beyond_its_largest_offset():
+    """evo_attn_decode_fp8 addresses a key by a 32-bit byte offset: at Tk = 2,100 the largest token stride it admits is 2,045,216 bytes
+    (tests/test_gpu_kv_fp8_exact.py launches there); one 16-byte step further, Tk * d_st = 4,294,987,200 >= 2^32 - 1, is refused with -1
+    before any launch (the pointers are never dereferenced)."""
+    from kv_fp8_exact import BIG_TK, largest_token_stride
+    lib = evo_ops.load_library()
+    one = ctypes.c_void_p(16)
+    st = largest_token_stride()
+    assert BIG_TK * st <= 0xffffffff - 1 < BIG_TK * (st + 16)
+
+    def call(Tk, d_st):
+        return lib.evo_attn_decode_fp8(one, one, one, one, 2, 2, Tk, 768, 128, 512, d_st, 256, 128, 4 * Tk, 2 * Tk, Tk, None, one, one, 1,
+                                       ctypes.c_float(0.0), None)
+    assert call(BIG_TK, st + 16) == -1
+    assert call(BIG_TK + 1, st) == -1                                  # the same stride, one key more
+    assert call(BIG_TK, st + 8) == -1                                  # (not a multiple of 16)
+
+
 def test_c_abi_reads_no_environment():
     """Which kernel a C-ABI call launches is a function of its arguments alone (no global state inside the boundary): no
     source or header of the library mentions getenv."""
