@@ -46,6 +46,7 @@ class Backend:
         # FP8 weights for the single-token step at 1-8 rows (InferenceParams.weight_dtype == "fp8"): w_quant_fp8(w) -> Fp8Weight; the others
         # are linear / linear_residual_ / norm_linear / hyena_decode_fused / mlp_gate with the record in place of the weight(s)
         "w_fp8": ("w_quant_fp8", "linear_w8", "linear_residual_w8_", "norm_linear_w8", "hyena_decode_fused_w8", "mlp_gate_w8"),
+        "kv_paged": ("rope_append_decode_paged", "attention_decode_paged"),               # the paged KV cache (InferenceParams.kv_layout == "paged")
     }   # (single kernels go by their own name: rope_append_decode, unembed_profile, attention_prefix, attention_prefix_vt, attention_decode_prefix)
 
     def supports(self, *names: str) -> bool:

@@ -617,15 +617,6 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pipe_kernel(AttnArgs a) {
 //   score: 8-element partial dot with the lane's q chunk (v_dot2), summed over the 16 lanes of the key; softmax statistics are
 //   per block (online across blocks, log2 domain, fp32); P.V: each lane accumulates its 8 output dims over its keys, the four
 //   key groups meet at the end.  The split's unnormalised (O, m, l) goes to the same partial buffers as before.
-typedef __bf16 attn_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float attn_dot8(const uint4& a, const uint4& b) {
-    float acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.x), __builtin_bit_cast(attn_bf16x2, b.x), 0.f, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.y), __builtin_bit_cast(attn_bf16x2, b.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.z), __builtin_bit_cast(attn_bf16x2, b.z), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.w), __builtin_bit_cast(attn_bf16x2, b.w), acc, false);
-    return acc;
-}
-
 __global__ __launch_bounds__(256) void attn_decode_stream_kernel(AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

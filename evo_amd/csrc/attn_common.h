@@ -11,6 +11,16 @@ typedef __bf16 mfma_bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ mfma_bf16x8 as_frag(uint4 v) { return __builtin_bit_cast(mfma_bf16x8, v); }
 
+// 8-element bf16 dot of two 16-byte chunks (v_dot2): the score arithmetic of the streaming decode kernels (csrc/attn.hip, csrc/kv_paged.hip)
+typedef __bf16 attn_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float attn_dot8(const uint4& a, const uint4& b) {
+    float acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.x), __builtin_bit_cast(attn_bf16x2, b.x), 0.f, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.y), __builtin_bit_cast(attn_bf16x2, b.y), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.z), __builtin_bit_cast(attn_bf16x2, b.z), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(attn_bf16x2, a.w), __builtin_bit_cast(attn_bf16x2, b.w), acc, false);
+    return acc;
+}
+
 struct AttnArgs {
     const uint16_t* q; const uint16_t* k; const uint16_t* v; uint16_t* o;
     int64_t Tq, Tk, q_pos0;

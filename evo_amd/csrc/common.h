@@ -25,6 +25,17 @@ __device__ __forceinline__ uint16_t f_to_bf(float f) { return (uint16_t)(pack_bf
 // value of f after a round trip through bf16
 __device__ __forceinline__ float round_bf(float f) { return bf_lo(pack_bf2(f, 0.f)); }
 
+// eight bf16 of one 16-byte vector <-> eight f32 (csrc/elementwise.hip, csrc/kv_paged.hip)
+__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
+    f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
+    f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
+}
+__device__ __forceinline__ uint4 pack8(const float* f) {
+    uint4 v;
+    v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]); v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
+    return v;
+}
+
 // Wave-wide butterfly reductions.  The four steps inside a 16-lane row are DPP operands of the add itself (no LDS traffic:
 // a __shfl_xor is a ds_bpermute, and the 4-16 reductions that end every wave of a weight-streaming launch all hit the LDS
 // pipe at the same moment); after the xor-1 and xor-2 steps the lanes of a quad agree bit for bit, so row_half_mirror /

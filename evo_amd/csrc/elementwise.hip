@@ -40,16 +40,6 @@ extern "C" int evo_embed_bf16(const int64_t* ids, const void* weight, void* out,
 // ------------------------------------------------------------------------------------------- rmsnorm
 // One wave per row; the row (<= 4096 elements) stays in registers between the square-sum and the
 // scale pass, so HBM sees exactly one read and one write (two writes with the bias/residual form).
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-    f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
-    f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-    uint4 v;
-    v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]); v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
-    return v;
-}
-
 __device__ __forceinline__ int64_t rms_out_row(int64_t row, int64_t T, int64_t Tp, int64_t Tm, int64_t tail0) {
     if (T == 0) return row;
     const int64_t b = row / T, t = row - b * T;

@@ -81,6 +81,8 @@ _SIGNATURES = {
     "evo_hyena_decode_fused_small_m_w8": ([_PTR] * 13 + [_I64] * 3 + [_F32, _PTR], _c.c_int),
     "evo_mlp_gate_small_m_w8": ([_PTR] * 4 + [_I64] * 4 + [_PTR], _c.c_int),
     "evo_norm_mlp_gate_small_m_w8": ([_PTR] * 5 + [_I64] * 3 + [_F32, _I64, _PTR], _c.c_int),
+    "evo_rope_append_decode_paged_bf16": ([_PTR] * 5 + [_F32] + [_I64] * 10 + [_F32, _PTR], _c.c_int),
+    "evo_attn_decode_paged_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
 }
 
 _LIB = None
@@ -1093,6 +1095,61 @@ class HipOps(Backend):
             _check(self.lib.evo_attn_decode_fp8(q.data_ptr(), ptrs[0], ptrs[1], o.data_ptr(), B, H, Tk, q.stride(0), q.stride(2), *ptrs[2:],
                                                 _ptr(pos), part_o.data_ptr(), part_ml.data_ptr(), n_splits,
                                                 0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()), "evo_attn_decode_fp8")
+        return o
+
+    # ---- paged bf16 KV cache: the optional group "kv_paged" (csrc/kv_paged.hip) ----------------------------------------
+    def _paged_cache_args(self, op: str, kv, B: int, H: int) -> tuple:
+        """The cache operand of the two paged launches, checked: kv.pages [n_pages, page_tokens, 2, H, 128] bf16, kv.table [>=B, width]
+        int32 with contiguous rows -> (pages ptr, table ptr, page_tokens, n_pages, table_width, the four strides).  The table is not read."""
+        p, t = kv.pages, kv.table
+        if not p.is_cuda or not t.is_cuda or p.dtype != torch.bfloat16 or t.dtype != torch.int32 or p.dim() != 5 or t.dim() != 2:
+            raise RuntimeError(f"{op}: the paged cache is pages [n_pages,page_tokens,2,H,128] bf16 + table [B,width] int32 on a ROCm device")
+        pt = p.shape[1]
+        if tuple(p.shape[2:]) != (2, H, 128) or p.stride(-1) != 1 or p.shape[0] < 1 or pt < 64 or pt & (pt - 1) or t.shape[0] < B \
+                or t.shape[1] < 1 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1]):
+            raise RuntimeError(f"{op}: cache shapes {tuple(p.shape)} / {tuple(t.shape)} do not fit B = {B}, H = {H}, head dim 128, "
+                               "page_tokens a power of two >= 64")
+        self._check_address(p.data_ptr(), f"{op} kv.pages")
+        self._check_address(t.data_ptr(), f"{op} kv.table", 4)
+        return (p.data_ptr(), t.data_ptr(), pt, p.shape[0], t.shape[1], p.stride(0), p.stride(1), p.stride(2), p.stride(3))
+
+    def rope_append_decode_paged(self, qkv: torch.Tensor, kv, pos: torch.Tensor, inv_freq: torch.Tensor, scaling: float,
+                                 q_scale: float = 1.0) -> None:
+        """`rope_append_decode` on a paged cache: the same rotary on q and k of qkv [B,1,3,H,128] (bit for bit), then k and v go to token
+        pos[b] of row b's pages (`kv`: a PagedKV).  One launch."""
+        self._need(qkv, torch.bfloat16, "rope_append_decode_paged qkv")
+        B, T, three, H, hd = qkv.shape
+        if T != 1 or three != 3 or hd != 128:
+            raise RuntimeError("rope_append_decode_paged: expects qkv [B,1,3,H,128]")
+        a = self._paged_cache_args("rope_append_decode_paged", kv, B, H)
+        if pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() != B or not pos.is_contiguous():
+            raise RuntimeError("rope_append_decode_paged pos: need a contiguous device int64 tensor with B entries")
+        self._check_address(pos.data_ptr(), "rope_append_decode_paged pos", 8)
+        self._need(inv_freq, torch.float32, "rope_append_decode_paged inv_freq")
+        _check(self.lib.evo_rope_append_decode_paged_bf16(qkv.data_ptr(), a[0], a[1], pos.data_ptr(), inv_freq.data_ptr(), float(scaling),
+                                                          B, H, hd, *a[2:], float(q_scale), _stream()), "evo_rope_append_decode_paged_bf16")
+
+    def attention_decode_paged(self, q: torch.Tensor, kv, pos: torch.Tensor, n_splits: Optional[int] = None,
+                               prescaled: bool = False) -> torch.Tensor:
+        """`attention_decode` on a paged cache: q [B,1,H,128] against `kv` (a PagedKV); row b sees keys [0, pos[b]] of its pages (pos:
+        device int64 [B], required).  A row is bounded by table_width * page_tokens keys, which also sets the default `n_splits`."""
+        B, Tq, H, hd = q.shape
+        if pos is None or pos.dtype != torch.int64 or not pos.is_cuda or pos.numel() != B:
+            raise RuntimeError("attention_decode_paged pos: need a device int64 tensor with B entries")
+        pos = pos.reshape(-1).contiguous()
+        self._check_address(pos.data_ptr(), "attention_decode_paged pos", 8)
+        if Tq != 1 or hd != 128:
+            raise RuntimeError("attention_decode_paged: expects [B,1,H,128] queries")
+        self._need_strided("attention_decode_paged", q=q)
+        a = self._paged_cache_args("attention_decode_paged", kv, B, H)
+        n_splits = self._decode_splits(a[4] * a[2]) if n_splits is None else int(n_splits)
+        o = torch.empty(B, 1, H, hd, dtype=torch.bfloat16, device=q.device)
+        part_o = torch.empty(B, H, n_splits, hd, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(B, H, n_splits, 2, dtype=torch.float32, device=q.device)
+        with self._t("attn_decode_paged"):
+            _check(self.lib.evo_attn_decode_paged_bf16(q.data_ptr(), a[0], a[1], o.data_ptr(), B, H, a[2], a[3], a[4], q.stride(0), q.stride(2),
+                                                       *a[5:], pos.data_ptr(), part_o.data_ptr(), part_ml.data_ptr(), n_splits,
+                                                       0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()), "evo_attn_decode_paged_bf16")
         return o
 
     # ---- FP8 (e4m3fn) weights for the single-token step at 1-8 rows: the optional group "w_fp8" (csrc/gemv_fp8.hip; DESIGN.md section 22) ----

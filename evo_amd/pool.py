@@ -51,6 +51,14 @@ for its life, so its captured step is captured on it.  Not with `share_prompt_kv
 the bytes; the copies sit beside the bf16 weights, which the prefills keep reading).  `stats["weight_dtype"]` and
 `stats["decode_weight_bytes"]` report the format and what a step streams.  It composes with every option above: only the dense
 launches of the step change.
+
+`kv_paged=True` (opt-in): the KV cache is a pool of pages of `kv_page_tokens` tokens (`PagedKV`) and ONE device table
+[n_slots, table_width] for all layers.  A job reserves ceil((prompt + its own limit) / page_tokens) pages from a host free list when it is
+admitted -- nothing is allocated per step, so the captured step never waits for the host -- and returns them when its slot is fetched; its
+table row then holds zeros again, the scrap page 0 that idle slots append into.  Without `kv_budget_tokens` the pool is sized per call for
+the `n_slots` largest jobs; with it a free slot takes the head of the queue only when enough pages are free (FIFO: the head blocks the
+jobs behind it; `stats["kv_page_waits"]` counts the slot-steps this idles), and a job larger than the whole budget is a ValueError.  The
+step appends with `rope_append_decode_paged` and attends with `attention_decode_paged`.  Not with `share_prompt_kv` or `kv_dtype="fp8"`.
 """
 from __future__ import annotations
 
@@ -62,7 +70,7 @@ import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
 from .backend import Backend
-from .sh.cache import Fp8KV, PromptStore, check_kv_dtype, check_weight_dtype, check_weight_rows
+from .sh.cache import Fp8KV, PagedKV, PromptStore, check_kv_dtype, check_page_tokens, check_weight_dtype, check_weight_rows
 from .sh.model import capture_graph
 from .constraints import TokenConstraint
 from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
@@ -73,9 +81,27 @@ class DecodePool:
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
-                 prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+                 prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16", weight_dtype: str = "bf16",
+                 kv_paged: bool = False, kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None):
         self.model = model
         self.kv_dtype = check_kv_dtype(kv_dtype)
+        self.kv_paged = bool(kv_paged)
+        if self.kv_paged:                                            #  every refusal before any device work
+            if share_prompt_kv:
+                raise ValueError("kv_paged=True does not combine with share_prompt_kv=True: the prompt store and its grouped decode "
+                                 "attention read contiguous rows")
+            if self.kv_dtype != "bf16":
+                raise ValueError('kv_paged=True does not combine with kv_dtype="fp8": the paged cache and its two kernels are bf16')
+            self.page_tokens = check_page_tokens(kv_page_tokens)
+            self.budget_pages = None
+            if kv_budget_tokens is not None:
+                self.budget_pages = int(kv_budget_tokens) // self.page_tokens
+                if self.budget_pages < 1:
+                    raise ValueError(f"kv_budget_tokens = {kv_budget_tokens} holds no page of {self.page_tokens} tokens")
+            ops = getattr(model, "ops", None)
+            if ops is None or not Backend.adopt(ops).supports("kv_paged"):
+                raise RuntimeError('kv_paged=True needs a compute backend with the "kv_paged" kernels (rope_append_decode_paged, '
+                                   "attention_decode_paged); this model's backend has none")
         self.weight_dtype = check_weight_dtype(weight_dtype)
         if self.weight_dtype == "fp8":                               # 
             from .generation import check_fp8_weight_model
@@ -117,6 +143,11 @@ class DecodePool:
             self.stats.update({"prompt_kv_installs": 0, "store_rows": 0, "prefix_streams": 0})
         if self.prefill_batch > 1:                                   # (prefills then counts forwards)
             self.stats.update({"prefill_prompts": 0, "prefill_pad_tokens": 0})
+        if self.kv_paged:
+            self.stats.update({"kv_pages": 0, "kv_pages_peak": 0, "kv_page_waits": 0})
+        self.table = None                                            # kv_paged: device int32 [S, table_width], shared by every layer's PagedKV
+        self._free_pages: List[int] = []                             # host free list (page 0, the scrap page, is never on it)
+        self._slot_pages: List[List[int]] = []                       # host: the pages each slot's job owns
         self.store = None
         self.store_refs: List[int] = []                              # host: live copies per store row
         self._store_prompt: List[Optional[int]] = []                 # host: the prompt a store row holds (kept after its last copy finished)
@@ -174,7 +205,73 @@ class DecodePool:
     def _kv_bytes(ipd, store=None) -> int:
         """Bytes held by the KV tensors of `ipd` (and of a prompt store): what stats["kv_bytes"] reports."""
         kvs = list(ipd["mha"].key_value_memory_dict.values()) + ([] if store is None else list(store.kv.values()))
-        return sum(kv.nbytes() if isinstance(kv, Fp8KV) else kv.numel() * kv.element_size() for kv in kvs)
+        return sum(kv.nbytes() if isinstance(kv, (Fp8KV, PagedKV)) else kv.numel() * kv.element_size() for kv in kvs)
+
+    # ------------------------------------------------------------------ paged KV (opt-in, DESIGN.md section 23)
+    def _page_need(self, n_keys: int) -> int:
+        """Pages a job of `n_keys` = prompt + own limit tokens reserves at admission."""
+        return -(-int(n_keys) // self.page_tokens)
+
+    def _allocate_paged(self, needs: Sequence[int]) -> None:
+        """Page pool and table for one generate() call whose jobs need `needs` pages each (job order).  The table is as wide as the
+        largest need; without a budget the pool holds the `n_slots` largest needs (admission never waits), with one it holds the
+        budget.  Runs between calls, when no job is live: a larger pool is allocated afresh and nothing is copied; a wider table or a
+        new pool drops the captured step (it is bound to their addresses)."""
+        m, S, dev, pt = self.model, self.n_slots, self.device, self.page_tokens
+        width = max(needs)
+        if self.budget_pages is not None:
+            if width > self.budget_pages:
+                raise ValueError(f"kv_paged: a job needs {width} pages of {pt} tokens, the budget kv_budget_tokens holds "
+                                 f"{self.budget_pages}")
+            n_pages = 1 + self.budget_pages
+        else:
+            n_pages = 1 + sum(sorted(needs, reverse=True)[:S])
+        fresh = self.ipd is None
+        if fresh:
+            ipd = m.initialize_inference_params()
+            ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
+            ipd["mha"].kv_layout = "paged"
+            ipd["mha"].weight_dtype = self.weight_dtype
+            D = m.hidden_size
+            dt = m.embedding_layer.weight.dtype
+            for i in m.hyena_layer_idxs:
+                ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
+                ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
+            self.ipd = ipd
+            self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
+            self._slot_pages = [[] for _ in range(S)]
+            if self.device_sampler:
+                self._allocate_sampler_state()
+        mha = self.ipd["mha"]
+        if self.table is None or self.table.shape[1] < width:
+            self.table = torch.zeros(S, width, dtype=torch.int32, device=dev)
+            for kv in mha.key_value_memory_dict.values():
+                kv.table = self.table
+            self._graph = None
+        if fresh or n_pages > self.stats["kv_pages"]:
+            dt = m.embedding_layer.weight.dtype
+            for i in m.attn_layer_idxs:
+                mha.key_value_memory_dict.pop(i, None)               # (let go of the old pool before the new one is made)
+                mha.key_value_memory_dict[i] = PagedKV.zeros(n_pages, pt, m.num_heads, m.head_dim, self.table, dtype=dt)
+            self._free_pages = list(range(n_pages - 1, 0, -1))       # popped from the end: page 1 first; page 0 stays out
+            self.stats["kv_pages"] = n_pages
+            self.stats["kv_bytes"] = self._kv_bytes(self.ipd)
+            self._graph = None
+        self.capacity = self.table.shape[1] * pt                     # the bound of a slot's position
+        mha.max_seqlen = self.capacity
+
+    def _can_admit(self, need: int) -> bool:
+        return not self.kv_paged or need <= len(self._free_pages)
+
+    def _release_pages(self, slots: Sequence[int]) -> None:
+        """Finished slots give their pages back; their table rows return to zeros (the scrap page)."""
+        if not self.kv_paged:
+            return
+        for s in slots:
+            self._free_pages.extend(reversed(self._slot_pages[s]))
+            self._slot_pages[s] = []
+        self.table[torch.tensor(list(slots), dtype=torch.int64, device=self.device)] = 0
 
     def _allocate_sampler_state(self) -> None:
         m, S, dev = self.model, self.n_slots, self.device
@@ -331,11 +428,20 @@ class DecodePool:
         self.stats["prefill_pad_tokens"] += len(group) * (-(-T // self.PREFILL_PAD) * self.PREFILL_PAD) - sum(lens)
         return logits.float(), tmp
 
-    def _install(self, slot: int, tmp: dict, P: int, row: int = 0) -> None:
+    def _install(self, slot: int, tmp: dict, P: int, row: int = 0, need: int = 0) -> None:
         m = self.model
+        if self.kv_paged:
+            # the job's reservation: `need` pages off the free list, named in its table row (outside the captured step, like all of this)
+            pages = [self._free_pages.pop() for _ in range(need)]
+            self._slot_pages[slot] = pages
+            ids = torch.tensor(pages, dtype=torch.int64, device=self.device)
+            self.table[slot, :need] = ids.to(torch.int32)
+            self.stats["kv_pages_peak"] = max(self.stats["kv_pages_peak"], self.stats["kv_pages"] - 1 - len(self._free_pages))
         for i in m.attn_layer_idxs:
             dst, src = self.ipd["mha"].key_value_memory_dict[i], tmp["mha"].key_value_memory_dict[i]
-            if isinstance(dst, Fp8KV):
+            if self.kv_paged:
+                dst.write_tokens_(ids, src[row, :P])                   # the prompt's K/V, from row `row` of the prefill's own cache
+            elif isinstance(dst, Fp8KV):
                 dst.copy_rows_(slot, src, row, P)                        # both tensors of the layer
             else:
                 dst[slot, :P] = src[row, :P]
@@ -486,8 +592,12 @@ class DecodePool:
                 raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
         if streams is not None and (not self.device_sampler or len(streams) != len(prompts) * int(n_sample_per_prompt)):
             raise ValueError("streams: one id per output, and only with the device sampler")
+        need_of = [0] * len(prompts)
         if self.share_prompt_kv:
             self._allocate_shared(max(e.shape[1] for e in encoded), n_tokens, int(n_sample_per_prompt))
+        elif self.kv_paged:
+            need_of = [self._page_need(e.shape[1] + n_tokens) for e in encoded]
+            self._allocate_paged([n for n in need_of for _ in range(int(n_sample_per_prompt))])
         else:
             self._allocate(max(e.shape[1] for e in encoded) + n_tokens)
         if self.device_sampler:
@@ -508,6 +618,8 @@ class DecodePool:
             last_logits, tmp, row = cached_prefill[pi]
             P = encoded[pi].shape[1]
             kw = {"row": row} if row else {}                         # (row 0 of a B = 1 prefill: the call as it always was)
+            if self.kv_paged:
+                kw["need"] = need_of[pi]
             if self.share_prompt_kv:
                 self._install_shared(slot, pi, tmp, P, **kw)
             else:
@@ -539,6 +651,7 @@ class DecodePool:
             self.s_active[idx] = False
             if self.share_prompt_kv:
                 self._release_shared(slots)
+            self._release_pages(slots)
             ids_cpu, lg_cpu = self.hist_ids[idx, :n_tokens].cpu(), self.hist_logits[idx, :n_tokens].cpu()
             for r, s in enumerate(slots):
                 out_ids[slot_job[s]], out_logits[slot_job[s]] = ids_cpu[r], lg_cpu[r]
@@ -546,19 +659,27 @@ class DecodePool:
 
         done = 0
         while done < n_jobs:
+            waiting = 0                                               # kv_paged: free slots the head of the queue could not take (FIFO)
             for s in range(S):
                 if slot_job[s] is None and jobs:
+                    if waiting or not self._can_admit(need_of[jobs[0][1]]):
+                        waiting += 1
+                        continue
                     fill(s)
                     if n_tokens == 1:
                         if self.device_sampler:
                             fetch([s])
-                        elif self.share_prompt_kv:
-                            self._release_shared([s])
+                        else:
+                            if self.share_prompt_kv:
+                                self._release_shared([s])
+                            self._release_pages([s])
                         slot_job[s] = None
                         done += 1
             active = [s for s in range(S) if slot_job[s] is not None]
             if not active:
                 continue
+            if waiting:
+                self.stats["kv_page_waits"] += waiting
             if self.share_prompt_kv:
                 self._count_prefix_streams()
             if self.device_sampler:
@@ -589,6 +710,8 @@ class DecodePool:
                     done += 1
             if ended and self.share_prompt_kv:
                 self._release_shared(ended)
+            if ended:
+                self._release_pages(ended)
 
         self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
         for name in ("last_lengths", "last_finish", "last_logprobs"):    # (an earlier job-control run's: they would describe that run)
@@ -703,6 +826,8 @@ class DecodePool:
         try:
             if self.share_prompt_kv:
                 self._allocate_shared(max(e.shape[1] for e in encoded), L, n_spp, rows=min(S, len(prompts)))
+            elif self.kv_paged:                                      # a job reserves to its OWN limit
+                self._allocate_paged([self._page_need(e.shape[1] + n) for e, n in zip(encoded, limits) for _ in range(n_spp)])
             else:
                 self._allocate(max(e.shape[1] for e in encoded) + L)
             if not hasattr(self, "s_limit"):
@@ -739,6 +864,7 @@ class DecodePool:
         slot_n = [0] * S                                             # tokens the slot's job has if it is still running
         slot_limit = [0] * S
         cached_prefill: Dict[int, tuple] = {}
+        need_of = [self._page_need(e.shape[1] + n) for e, n in zip(encoded, limits)] if self.kv_paged else [0] * len(prompts)
 
         def fill(slot: int) -> None:
             j, pi = jobs.popleft()
@@ -747,6 +873,8 @@ class DecodePool:
             last_logits, tmp, row = cached_prefill[pi]
             P = encoded[pi].shape[1]
             kw = {"row": row} if row else {}
+            if self.kv_paged:
+                kw["need"] = need_of[pi]
             if self.share_prompt_kv:
                 self._install_shared(slot, pi, tmp, P, **kw)
             else:
@@ -774,6 +902,7 @@ class DecodePool:
             idx = torch.tensor(slots, dtype=torch.int64, device=dev)
             if self.share_prompt_kv:
                 self._release_shared(slots)
+            self._release_pages(slots)
             if lengths is None:
                 lengths, fins = [slot_limit[s] for s in slots], [FINISH_LENGTH] * len(slots)
             else:
@@ -796,9 +925,12 @@ class DecodePool:
 
         done, since_poll = 0, 0
         while done < n_jobs:
-            filled = False
+            filled, waiting = False, 0
             for s in range(S):
                 if slot_job[s] is None and jobs:
+                    if waiting or not self._can_admit(need_of[jobs[0][1]]):   # kv_paged: the head of the queue waits for pages (FIFO)
+                        waiting += 1
+                        continue
                     fill(s)
                     filled = True
                     if slot_limit[s] == 1 and not has_stop:
@@ -814,6 +946,8 @@ class DecodePool:
             if not look and not due:
                 if self.share_prompt_kv:
                     self._count_prefix_streams()
+                if waiting:
+                    self.stats["kv_page_waits"] += waiting
                 self._step_sampled()
                 since_poll += 1
                 for s in active:
@@ -822,9 +956,10 @@ class DecodePool:
                 due = [s for s in active if slot_n[s] >= slot_limit[s]]
             if not has_stop:
                 finished, lengths = due, None                         # lengths are the limits: the host knows without reading
-            elif look or due or since_poll >= self.poll_every or not jobs:
+            elif look or due or since_poll >= self.poll_every or not jobs or waiting:
                 # the one read: [S] lengths, -1 while a job runs.  With nothing left to admit the host looks after every step: no step
-                # may run with every row already ended
+                # may run with every row already ended.  While the head of the queue waits for pages (kv_paged) it looks after every step too:
+                # a job that ended sooner frees the pages the head needs
                 polled = self.s_length.cpu().tolist()
                 self.stats["polls"] += 1
                 since_poll = 0
@@ -853,7 +988,8 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 top_p: float = 1.0, n_sample_per_prompt: int = 1, n_slots: int = 8, prepend_bos: bool = False,
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
-                poll_every: int = 8, constraints=None, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+                poll_every: int = 8, constraints=None, kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_paged: bool = False,
+                kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
@@ -862,10 +998,13 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     `stop_tokens`, `stop_sequences` / `stop_frame` and `return_logits=False`: jobs that end on their own (see
     `DecodePool.generate`).  `constraints`: one `TokenConstraint` (evo_amd/constraints.py) for every prompt, or one (or None) per prompt --
     constrained generation on the device.  `kv_dtype="fp8"`: the pool's KV cache in FP8 e4m3fn, about half the bytes
-    (not with `share_prompt_kv`)."""
+    (not with `share_prompt_kv`).  `kv_paged=True`: the KV cache is a pool of pages of `kv_page_tokens` tokens, a job
+    holds what its own prompt and limit need, and `kv_budget_tokens` caps the pool (not with `share_prompt_kv` or
+    `kv_dtype="fp8"`)."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
                       allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every,
-                      kv_dtype=kv_dtype, weight_dtype=weight_dtype)
+                      kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_paged=kv_paged, kv_page_tokens=kv_page_tokens,
+                      kv_budget_tokens=kv_budget_tokens)
     ctl = {}
     if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)

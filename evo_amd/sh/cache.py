@@ -78,8 +78,76 @@ class Fp8KV:
         return self.data.view(torch.float8_e4m3fn).float() * self.scale.permute(0, 3, 1, 2).unsqueeze(-1)
 
 
+KV_LAYOUTS = ("contiguous", "paged")
+KV_PAGE_TOKENS_MIN = 64     # a 64-key block of the streaming decode attention must lie inside one page
+
+
+def check_page_tokens(page_tokens) -> int:
+    """`page_tokens` if it is a power of two >= 64; ValueError otherwise (raised before any device work)."""
+    n = int(page_tokens)
+    if n < KV_PAGE_TOKENS_MIN or n & (n - 1):
+        raise ValueError(f"kv_page_tokens must be a power of two >= {KV_PAGE_TOKENS_MIN}, got {page_tokens!r}")
+    return n
+
+
+@dataclass(eq=False)
+class PagedKV:
+    """One attention layer's paged bf16 KV cache: pages [n_pages, page_tokens, 2, H, 128] -- a page is a
+    [page_tokens, 2, H, 128] view with the contiguous cache's inner layout -- and table [n_slots, table_width] int32 on the device, ONE
+    tensor shared by every attention layer of a pool: token t of slot s lives in pages[table[s, t // page_tokens], t % page_tokens].
+    Page 0 is a scrap page that is never handed out; every table entry no live job owns holds 0.  The value of
+    key_value_memory_dict[layer] when InferenceParams.kv_layout == "paged"; compared by identity."""
+    pages: Tensor
+    table: Tensor
+
+    @classmethod
+    def zeros(cls, n_pages: int, page_tokens: int, H: int, hd: int, table: Tensor, dtype=torch.bfloat16) -> "PagedKV":
+        check_page_tokens(page_tokens)
+        return cls(torch.zeros(n_pages, page_tokens, 2, H, hd, dtype=dtype, device=table.device), table)
+
+    @property
+    def page_tokens(self) -> int:
+        return self.pages.shape[1]
+
+    @property
+    def n_pages(self) -> int:
+        return self.pages.shape[0]
+
+    @property
+    def table_width(self) -> int:
+        return self.table.shape[1]
+
+    @property
+    def shape(self):
+        return self.pages.shape
+
+    @property
+    def device(self):
+        return self.pages.device
+
+    def nbytes(self) -> int:
+        """Bytes of the page pool (the table is shared by all layers and a few KiB)."""
+        return self.pages.numel() * self.pages.element_size()
+
+    def rows(self, B: int) -> "PagedKV":
+        """The first B table rows, as a view (the pages are the pool's)."""
+        return self if self.table.shape[0] == B else PagedKV(self.pages, self.table[:B])
+
+    def write_tokens_(self, page_ids: Tensor, src: Tensor) -> None:
+        """src [n, 2, H, 128] -> tokens 0 .. n - 1 of the stream whose pages are `page_ids` (device int64, in order)."""
+        n, pt = src.shape[0], self.page_tokens
+        t = torch.arange(n, device=src.device)
+        self.pages[page_ids[t // pt], t % pt] = src
+
+    def gather(self, slot: int, n: int) -> Tensor:
+        """Tokens 0 .. n - 1 of slot `slot` as one [n, 2, H, 128] tensor (tests, inspection: not a hot path)."""
+        pt = self.page_tokens
+        t = torch.arange(n, device=self.pages.device)
+        return self.pages[self.table[slot].long()[t // pt], t % pt]
+
+
 WEIGHT_DTYPES = ("bf16", "fp8")
-W8_MAX_ROWS = 8         # batch rows the FP8-weight launches serve (csrc/gemv_fp8.hip: the dot2 forms; the 9-64-row MFMA forms are bf16 only)
+W8_MAX_ROWS = 8        # batch rows the FP8-weight launches serve (csrc/gemv_fp8.hip: the dot2 forms; the 9-64-row MFMA forms are bf16 only)
 
 
 def check_weight_dtype(weight_dtype) -> str:
@@ -146,6 +214,9 @@ class InferenceParams:
     key_value_memory_dict: dict = field(default_factory=dict)
     # "bf16" (default) or "fp8": the format of the KV cache (opt-in)
     kv_dtype: str = "bf16"
+    # "contiguous" (default) or "paged": key_value_memory_dict[layer] is then a PagedKV record (opt-in, the decode pool's per-row step only;
+    # DESIGN.md section 23)
+    kv_layout: str = "contiguous"
     # "bf16" (default) or "fp8": the dense weights the single-token steps on this cache stream (opt-in).  Read for
     # the Hyena blocks of the step too: the choice belongs to the generation, and this record is the one every step carries
     weight_dtype: str = "bf16"

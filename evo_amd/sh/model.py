@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
-from .cache import Fp8KV, InferenceParams, RecurrentInferenceParams, check_kv_dtype, check_weight_dtype, check_weight_rows
+from .cache import Fp8KV, InferenceParams, PagedKV, RecurrentInferenceParams, check_kv_dtype, check_weight_dtype, check_weight_rows
 from .utils import dotdict
 
 
@@ -758,6 +758,9 @@ class StripedHyena(nn.Module):
         Fp8KV record (both of its tensors are allocated, grown and copied together)."""
         H, hd = self.num_heads, self.head_dim
         kv = cache.key_value_memory_dict.get(i)
+        if isinstance(kv, PagedKV) or cache.kv_layout != "contiguous":
+            raise ValueError(f"layer {i}: a paged KV cache is sized by its pool and never grown or allocated here (kv_layout = "
+                             f"{cache.kv_layout!r}; it serves the decode pool's per-row single-token step only)")
         fp8 = cache.kv_dtype == "fp8"
         if kv is not None and isinstance(kv, Fp8KV) != fp8:
             raise ValueError(f"layer {i}'s KV cache does not have the format kv_dtype = {cache.kv_dtype!r} names")
@@ -808,7 +811,9 @@ class StripedHyena(nn.Module):
         # ops.attn_prescale: the rotary kernel folds softmax_scale * log2(e) into its one rounding of q, the attention kernels take scores as exponents
         pre = bool(ops.attn_prescale)
         q_scale = ops.attn_q_scale(hd) if pre else 1.0
-        if cache is not None and cache.kv_dtype != "bf16":
+        if cache is not None and (cache.kv_layout != "contiguous" or isinstance(cache.key_value_memory_dict.get(i), PagedKV)):
+            a = self._attn_paged(i, qkv, B, T, cache, off, pos, mask, pre, q_scale)
+        elif cache is not None and cache.kv_dtype != "bf16":
             a = self._attn_fp8(i, qkv, B, T, cache, off, pos, mask, pre, q_scale)
         elif pos is not None and T == 1:
             # one position PER ROW, in device memory (hipGraph replay, continuous batching); behind a prompt store the append goes to the row's OWN index
@@ -880,6 +885,28 @@ class StripedHyena(nn.Module):
         if T == 1:
             return ops.attention_decode(q, qkv[:, :, 1], qkv[:, :, 2], prescaled=pre)
         return ops.attention(q, qkv[:, :, 1], qkv[:, :, 2], 0, prescaled=pre)
+
+    def _attn_paged(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float):
+        """_attn_block's attention on a paged KV cache (cache.kv_layout == "paged"): the per-row single-token step of a
+        decode pool and nothing else -- prompts are prefilled on contiguous caches of their own and copied into pages."""
+        ops = self.ops
+        kv = cache.key_value_memory_dict.get(i)
+        if cache.kv_layout != "paged" or not isinstance(kv, PagedKV):
+            raise ValueError(f"layer {i}'s KV cache does not have the layout kv_layout = {cache.kv_layout!r} names")
+        for what, bad in (("shared_prefix", cache.shared_prefix is not None), ("prompt_store", cache.prompt_store is not None),
+                          ('kv_dtype="fp8"', cache.kv_dtype != "bf16"), ("a padding mask", mask is not None),
+                          (f"a multi-token forward (T = {T})", T > 1),
+                          ("a scalar-offset step (no pos_tensor)", T == 1 and pos is None)):
+            if bad:
+                raise ValueError(f'kv_layout="paged" does not combine with {what}: the paged cache serves per-row single-token steps')
+        if pos.numel() != B:
+            raise ValueError(f'kv_layout="paged": pos_tensor must hold one position per row ({B}), got {pos.numel()}')
+        if not ops.supports("kv_paged"):
+            raise RuntimeError('kv_layout="paged" needs a compute backend with the "kv_paged" kernels (rope_append_decode_paged, '
+                               "attention_decode_paged); this model's backend has none")
+        kv = kv.rows(B)
+        ops.rope_append_decode_paged(qkv, kv, pos, self._inv_freq(qkv.device), self.rotary_scaling, q_scale=q_scale)
+        return ops.attention_decode_paged(qkv[:, :, 0], kv, pos, prescaled=pre)
 
     # ------------------------------------------------------------------ forward
     max_rows_per_pass = 160 * 1024     # rows (B T) of one stateless pass; larger batches run in row groups (hidden_states)
@@ -1136,6 +1163,8 @@ class StripedHyena(nn.Module):
         if not self.has_own_unembed:          # the captured step bakes in the engine's unembedding weight
             return False
         hy, mha = ipd["hyena"], ipd["mha"]
+        if mha.kv_layout != "contiguous":     # a paged cache belongs to a decode pool, which captures its own step
+            return False
         # every layer must already hold state (i.e. a prefill happened), on this device
         return all(i in hy.fir_state_dict for i in self.hyena_layer_idxs) and \
             all(i in mha.key_value_memory_dict for i in self.attn_layer_idxs)
@@ -1150,7 +1179,7 @@ class StripedHyena(nn.Module):
         # references to the cache objects and to every captured tensor and compares by identity: a later cache can then
         # neither recycle a CPython id() nor a caching-allocator address of a freed buffer.
         same_bufs = (st is not None and st["B"] == B and st["mha"] is mha and st["hyena"] is hy and st["kv_dtype"] == mha.kv_dtype
-                     and st["weight_dtype"] == mha.weight_dtype
+                     and st["kv_layout"] == mha.kv_layout and st["weight_dtype"] == mha.weight_dtype
                      and all(mha.key_value_memory_dict.get(i) is t for i, t in st["kv"].items())
                      and all(hy.state_dict.get(i) is t for i, t in st["iir"].items())
                      and all(hy.fir_state_dict.get(i) is t for i, t in st["fir"].items()))
@@ -1167,7 +1196,8 @@ class StripedHyena(nn.Module):
                     self._dgraph_warm = (mha, hy, B)  # first step with these caches runs eagerly (warms M=B GEMMs)
                     return None
                 dev = self.device
-                st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype, "weight_dtype": mha.weight_dtype,
+                st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype, "kv_layout": mha.kv_layout,
+                      "weight_dtype": mha.weight_dtype,
                       "ids": torch.zeros(B, 1, dtype=torch.int64, device=dev),
                       "pos": torch.zeros(B, dtype=torch.int64, device=dev),
                       "kv": {i: mha.key_value_memory_dict[i] for i in self.attn_layer_idxs},

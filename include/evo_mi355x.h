@@ -374,6 +374,41 @@ int evo_attn_decode_fp8(const void* q, const void* kv_data, const float* kv_scal
                         const int64_t* dyn_pos, float* part_o, float* part_ml, int64_t n_splits,
                         float softmax_scale, void* stream);
 
+/* ---- paged bf16 KV cache for decode (added under ABI 20, no signature changed; csrc/kv_paged.hip) ---------------------------------------
+ * The two entries below stand where the reference calls flash_attn_with_kvcache  [REF evo/generation.py:138-155] on one contiguous
+ * cache per sequence; the reference has no paged cache.  Opt-in (DecodePool(kv_paged=True)): the entries above are untouched.
+ *   THE CACHE OPERAND of a layer (the same in both entries):
+ *     pages [n_pages, page_tokens, 2, H, 128] bf16, 16-byte aligned, ELEMENT strides p_sp (page), p_st (token), p_sw (K | V), p_sh
+ *           (head), each a multiple of 8 (p_st, p_sw, p_sh >= 128) -- inside a page the layout of evo_attn_decode_bf16's cache;
+ *     table [B, table_width] int32, contiguous, 4-byte aligned: token t of row b lives in page table[b, t >> log2(page_tokens)], at
+ *           row t & (page_tokens - 1) of it.  One table serves every layer of a model.
+ *   page_tokens is a power of two >= 64 (a 64-key block of the streaming kernel then lies inside one page) with
+ *   page_tokens * p_st * 2 < 2^32 - 1 (a lane's offset inside a page is 32-bit); n_pages >= 1, table_width >= 1.  A row holds at most
+ *   table_width * page_tokens keys: there is no 4 GiB bound on a row or on the pool (the page base is 64-bit) and no second kernel form.
+ *   Whatever the table holds, no access leaves the pool: the kernels clamp a table index to [0, table_width - 1] and a page id to
+ *   [0, n_pages - 1].  By convention page 0 is a scrap page and every entry no live row owns is 0 (evo_amd/sh/cache.py PagedKV).
+ *   Both return -1 without a launch on a null pointer, a misaligned pointer (16 bytes for data, 8 for pos, 4 for the table and f32
+ *   vectors), a page_tokens, stride or count that breaks the rules above, or a size <= 0.
+ *
+ * evo_rope_append_decode_bf16 with the cache row found through the table: rotary on q and k of qkv [B, 3, H, 128] in place at pos[b]
+ * -- the bits left in qkv are exactly that entry's, q_scale included -- then k (rotated) and v go to token pos[b] of row b's pages.
+ * One launch, per-row device positions, capturable.  hd must be 128. */
+int evo_rope_append_decode_paged_bf16(void* qkv, void* pages, const int32_t* table, const int64_t* pos, const float* inv_freq,
+                                      float scaling, int64_t B, int64_t H, int64_t hd,
+                                      int64_t page_tokens, int64_t n_pages, int64_t table_width,
+                                      int64_t p_sp, int64_t p_st, int64_t p_sw, int64_t p_sh, float q_scale, void* stream);
+/* evo_attn_decode_bf16's contract on paged keys: q [B, 1, H, 128] bf16 (q_sb, q_sh element strides), o [B, 1, H, 128] bf16 contiguous,
+ * pos [B] device int64 (required): row b sees keys [0, pos[b]] and nothing behind them is read; the same part_o / part_ml workspace, the
+ * same split partition (split s takes the 64-key blocks s, s + n_splits, ...; 1 <= n_splits <= 1024) and the same combine launch.
+ * softmax_scale <= 0: pre-scaled queries.  The kernel (attn_decode_paged_kernel) is attn_decode_stream_kernel in everything that
+ * produces a value, so for the same keys, positions and n_splits its output equals evo_attn_decode_bf16's bit for bit; a wave takes the
+ * page ids of its next 64 blocks with one load per lane ahead of their use. */
+int evo_attn_decode_paged_bf16(const void* q, const void* pages, const int32_t* table, void* o,
+                               int64_t B, int64_t H, int64_t page_tokens, int64_t n_pages, int64_t table_width,
+                               int64_t q_sb, int64_t q_sh, int64_t p_sp, int64_t p_st, int64_t p_sw, int64_t p_sh,
+                               const int64_t* pos, float* part_o, float* part_ml, int64_t n_splits,
+                               float softmax_scale, void* stream);
+
 /* ---- FP8 (OCP e4m3fn) weights for the decode step at 1-8 rows (ABI 20; csrc/gemv_fp8.hip; no counterpart in the reference) -------------
  * Opt-in: the bf16 entries above are untouched and remain the default.  At 1-8 batch rows a decode step streams every dense weight
  * once and is bound by those bytes; these entries stream half of them.

@@ -79,9 +79,21 @@ def main(argv=None):
     ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the pool's decode step streams; fp8 (e4m3fn, "
                                                                                     "one scale per output row) halves the bytes per step and "
                                                                                     "adds an FP8 copy to memory; --n-slots up to 8")
+    ap.add_argument("--kv-paged", action="store_true", help="keep the pool's KV cache in pages: a job holds what its own prompt and "
+                                                            "limit need, not the longest job's; not with --share-prompt-kv or "
+                                                            "--kv-dtype fp8")
+    ap.add_argument("--kv-page-tokens", type=int, default=256, metavar="N", help="tokens per page with --kv-paged (a power of two >= 64)")
+    ap.add_argument("--kv-budget-tokens", type=int, default=None, metavar="N", help="with --kv-paged: cap the page pool at N tokens; jobs "
+                                                                                    "then wait for free pages, in order")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
+    if args.kv_paged and (args.share_prompt_kv or args.kv_dtype != "bf16"):
+        ap.error("--kv-paged does not combine with --share-prompt-kv or --kv-dtype fp8")
+    if not args.kv_paged and (args.kv_page_tokens != 256 or args.kv_budget_tokens is not None):
+        ap.error("--kv-page-tokens and --kv-budget-tokens apply with --kv-paged only")
+    if args.kv_page_tokens < 64 or args.kv_page_tokens & (args.kv_page_tokens - 1):
+        ap.error("--kv-page-tokens must be a power of two >= 64")
     if args.weight_dtype != "bf16" and args.n_slots > 8:
         ap.error("--weight-dtype fp8 serves pools of up to 8 slots")
     if args.kv_dtype != "bf16" and args.share_prompt_kv:
@@ -101,6 +113,8 @@ def main(argv=None):
                       temperature=args.temperature, device=args.device, seed=args.seed, allowed_tokens=args.allowed_tokens,
                       share_prompt_kv=args.share_prompt_kv, prefill_batch=args.prefill_batch,
                       **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}),
+                      **({"kv_paged": True, "kv_page_tokens": args.kv_page_tokens, "kv_budget_tokens": args.kv_budget_tokens}
+                         if args.kv_paged else {}),
                       **({} if args.weight_dtype == "bf16" else {"weight_dtype": args.weight_dtype}))
     ctl = {}                                                  # any of these moves the job onto the job-control path
     if args.stop_tokens:
