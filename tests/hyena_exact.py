@@ -30,7 +30,10 @@ The operator is causal: one reference run at the longest T serves every shorter 
 end state of a run of t + 1 steps -- tests/test_hyena_exact_host.py).
 
 `mutants()`: deliberately wrong references (reference(..., mutant=name) / round_store(..., mutant=name)) -- the defects the GPU file is
-there to catch; which family sees which is tabulated and asserted in tests/test_hyena_exact_host.py."""
+there to catch; which family sees which is tabulated and asserted in tests/test_hyena_exact_host.py.  The last three are the defects of
+the single-token launches (a row's modal state from the previous row, a channel's poles and residues from its pair c ^ 1, an FIR history
+whose older column is never replaced); tests/hyena_fused_exact.py builds the walks that see them, tests/test_hyena_fused_exact_host.py
+tabulates where."""
 from collections import namedtuple
 
 import torch
@@ -87,14 +90,18 @@ def mutants():
             ("pow_plus4", "y"),               # p^(k + 4) instead of p^k in the carry product
             ("mode_xor1", "y"),               # mode s read as mode s ^ 1 in the output
             ("state_early", "state"),         # the end state one step early
-            ("trunc_store", "y")]             # truncation instead of round-to-nearest-even at the bf16 store
+            ("trunc_store", "y"),             # truncation instead of round-to-nearest-even at the bf16 store
+            # the single-token launches' own defects: the walks of tests/hyena_fused_exact.py are made to see them (the sweep's data does too)
+            ("state_prev_row", "y"),          # the modal state of batch row m read from row m - 1
+            ("chan_xor1", "y"),               # poles and residues of channel c read from channel c ^ 1 (the pair a two-channel wave owns)
+            ("fir_old_kept", "y")]            # the FIR history's older column never replaced (`fir_after` gives the history it leaves)
 
 
 # which family sees which mutant (U, I) after the store's rounding -- asserted on the sweep's data in tests/test_hyena_exact_host.py (the table
 # with its reasons is in that module's docstring)
 CAUGHT = {"fir_reversed": (True, True), "tile_hist_zero": (True, False), "row_hist_prev_row": (True, False), "swap_reim": (True, True),
           "carry_block_off": (True, True), "pow_plus4": (False, True), "mode_xor1": (True, True), "state_early": (True, True),
-          "trunc_store": (True, True)}
+          "trunc_store": (True, True), "state_prev_row": (True, True), "chan_xor1": (True, True), "fir_old_kept": (True, False)}
 
 
 def round_store(y, mutant=None):
@@ -123,6 +130,8 @@ def reference(z, prm, H, z_halo=None, s0=None, mask=None, mutant=None, state_at=
         h2[:, TILE::TILE] = 0
     if mutant == "row_hist_prev_row" and B > 1 and T > 1:
         h1[1:, 0], h2[1:, 0] = zd[:-1, T - 1], zd[:-1, T - 2]
+    if mutant == "fir_old_kept":
+        h2[:] = hist[:, 0:1]
     zc = w[:, 0] * h2 + w[:, 1] * h1 + w[:, 2] * zd + fir_b.double().to(dev)
     if mask is not None:
         zc = zc * (mask != 0).double().to(dev)[:, :, None]
@@ -130,6 +139,8 @@ def reference(z, prm, H, z_halo=None, s0=None, mask=None, mutant=None, state_at=
     x = x1 * v                                                                     # [B, T, D]
     p = torch.view_as_complex(poles.double().contiguous()).to(dev)                 # [D, 8]
     r = torch.view_as_complex(residues.double().contiguous()).to(dev)
+    if mutant == "chan_xor1":
+        p, r = p[torch.arange(D, device=dev) ^ 1], r[torch.arange(D, device=dev) ^ 1]
     r_out = r[:, [1, 0, 3, 2, 5, 4, 7, 6]] if mutant == "mode_xor1" else r
     S = torch.zeros(B, D, 8, dtype=torch.complex128, device=dev) if s0 is None else s0.to(torch.complex128).to(dev).clone()
     S_in = S.clone()
@@ -145,6 +156,8 @@ def reference(z, prm, H, z_halo=None, s0=None, mask=None, mutant=None, state_at=
     bad = torch.zeros((), dtype=torch.bool, device=dev)
     s_max = torch.zeros((), dtype=torch.float64, device=dev)
     for t in range(T):
+        if mutant == "state_prev_row":
+            S = torch.cat([S[:1], S[:-1]], 0)
         S = p * S + x[:, t, :, None]
         So = S
         if mutant == "swap_reim":
@@ -204,14 +217,25 @@ def reference(z, prm, H, z_halo=None, s0=None, mask=None, mutant=None, state_at=
     return Ref(y, states, hist)
 
 
+def fir_after(hist, t, mutant=None):
+    """The FIR history [B, 3 D, 2] (fir_state's layout: older | newer) a single-token launch leaves behind step t, from Ref.hist."""
+    old = hist[:, 0] if mutant == "fir_old_kept" else hist[:, t + 1]
+    return torch.stack([old, hist[:, t + 2]], -1)
+
+
+def flushed_ok(got, ref):
+    """equal_or_flushed without the count (no host synchronisation) -> (ok, tiny), both bool tensors."""
+    assert got.dtype == ref.dtype and got.shape == ref.shape
+    tiny = (ref != 0) & (ref.double().abs() < FLUSH)
+    return torch.where(tiny, got.double().abs() <= FLUSH_GOT, got == ref), tiny
+
+
 def equal_or_flushed(got, ref):
     """Family I's comparison, elementwise on real tensors of one dtype: the same VALUE where ref is 0 or |ref| >= 2^-100 (ref already
     cast to got's type; the same value of one type is the same bit pattern, except that -0 == +0: the sign of an exact zero depends on
     the order of the sum and is no arithmetic), |got| <= 2^-99 in between -> (ok [bool tensor], number of elements under the flush rule)."""
-    assert got.dtype == ref.dtype and got.shape == ref.shape
-    same = got == ref
-    tiny = (ref != 0) & (ref.double().abs() < FLUSH)
-    return torch.where(tiny, got.double().abs() <= FLUSH_GOT, same), int(tiny.sum())
+    ok, tiny = flushed_ok(got, ref)
+    return ok, int(tiny.sum())
 
 
 # ------------------------------------------------------------------------------------------------ the families

@@ -514,7 +514,8 @@ def test_norm_gate(I, K):
 def test_hyena_decode_fused(D, Ms):
     """evo_hyena_decode_fused_small_m from zero FIR / modal states: the z_t the launch computed (norm -> projection + bias), read back from
     fir_state's newest column, must equal expected() bit for bit; the outputs stay under row 22d's bound (2^-8 |ref| + 2e-3 of the
-    channel's largest + 1e-4 of its terms) against the fp64 operator on exactly those z rows."""
+    channel's largest + 1e-4 of its terms) against the fp64 operator on exactly those z rows.  The launch's FIR / modal / gate tail is
+    held bit for bit, from non-zero states, in tests/test_gpu_hyena_fused_exact.py (PARITY row 9e)."""
     import math
     from gpu_ref64 import gpu_fft_hyena
     ops = _ops()

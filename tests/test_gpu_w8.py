@@ -229,7 +229,8 @@ def _filter(D, g):
 @pytest.mark.parametrize("D,Ms", W8.HYENA)
 def test_hyena_fused(D, Ms, design):
     """From zero FIR / modal states: the z_t the launch computed (fir_state's newest column) equals expected() bit for bit; the outputs
-    stay under row 22d's bound against the fp64 operator on exactly those z rows (tests/test_gpu_dense_exact.py's judgement)."""
+    stay under row 22d's bound against the fp64 operator on exactly those z rows (tests/test_gpu_dense_exact.py's judgement).  The
+    launch's FIR / modal / gate tail is held bit for bit, from non-zero states, in tests/test_gpu_hyena_fused_exact.py (PARITY row 9e)."""
     from gpu_ref64 import gpu_fft_hyena
     ops = _ops()
     H = D // 128

@@ -14,6 +14,9 @@ Which family sees which mutant (asserted below, `CAUGHT`):
     mode_xor1            yes   yes
     state_early          yes   yes    (the end state; y is untouched)
     trunc_store          yes   yes    (I: only through s0's response, up to 9 significant bits; an impulse's own has <= 4: no rounding)
+    state_prev_row       yes   yes    (the single-token launches' defects, tests/hyena_fused_exact.py: here through the rows' start states)
+    chan_xor1            yes   yes
+    fir_old_kept         yes   no     (I's FIR reads no history; the fused launches' walks see it in fir_state)
 """
 import pytest
 import torch
