@@ -16,6 +16,7 @@ from .generation import generate
 from .scoring import score_sequences, positional_entropies, position_profiles, substitution_scores, PositionProfile
 from .scoring import score_variants, single_substitutions, plan_variants, VariantScores
 from .embeddings import embed_sequences
+from .pool import beam_search, BeamResult
 from .constraints import TokenConstraint, iupac_template, encode_protein, open_reading_frame, concat
 
 SHIM_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "shim")

@@ -31,6 +31,7 @@ EXPORTS = [
     "evo_w_quant_fp8", "evo_linear_small_m_w8", "evo_norm_linear_small_m_w8", "evo_hyena_decode_fused_small_m_w8",
     "evo_mlp_gate_small_m_w8", "evo_norm_mlp_gate_small_m_w8",
     "evo_rope_append_decode_paged_bf16", "evo_attn_decode_paged_bf16",
+    "evo_beam_select_f32", "evo_gather_rows",
 ]
 
 

@@ -15,9 +15,8 @@
 // (evo_sample_rows_dfa_f32) is the control kernel whose allow set at each draw is decided by the row's state in
 // a small token automaton, which the drawn token moves on.
 #include "common.h"
+#include "sample_row.h"     // sample_ord / sample_unord, the wave sum, the log-sum-exp: shared with csrc/beam.hip
 #include "../../include/evo_mi355x.h"
-
-#define EVO_SAMPLE_V 512
 
 __device__ __forceinline__ uint32_t philox4x32_10_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -34,21 +33,6 @@ __device__ __forceinline__ uint32_t philox4x32_10_x0(uint32_t c0, uint32_t c1, u
         k1 += 0xBB67AE85u;
     }
     return c0;
-}
-
-// float <-> a 32-bit pattern whose unsigned order is the float order (-inf lowest, +inf highest)
-__device__ __forceinline__ uint32_t sample_ord(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sample_unord(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
-
-__device__ __forceinline__ int sample_wave_sum_i(int v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // The draw of one row by one wave, shared by the kernels below: token and its log-probability under the unfiltered row (every lane
@@ -87,15 +71,7 @@ __device__ __forceinline__ SampleDraw sample_draw_row(const void* __restrict__ l
     }
 
     // ---- log-sum-exp of the UNFILTERED row (fp32)
-    float mx = x[0];
-#pragma unroll
-    for (int j = 1; j < 8; ++j) mx = fmaxf(mx, x[j]);
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) se += expf(x[j] - mx);
-    se = wave_sum(se);
-    const float lse = mx + logf(se);
+    EVO_SAMPLE_ROW_LSE(x, lse)
 
     // ---- keys: allow bits (bit j of `abits`: token 8 lane + j), then (logit, id) -> LDS
 #pragma unroll

@@ -83,6 +83,8 @@ _SIGNATURES = {
     "evo_norm_mlp_gate_small_m_w8": ([_PTR] * 5 + [_I64] * 3 + [_F32, _I64, _PTR], _c.c_int),
     "evo_rope_append_decode_paged_bf16": ([_PTR] * 5 + [_F32] + [_I64] * 10 + [_F32, _PTR], _c.c_int),
     "evo_attn_decode_paged_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
+    "evo_beam_select_f32": ([_PTR, _I64, _I64] + [_PTR] * 11 + [_I64, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
+    "evo_gather_rows": ([_PTR, _I64, _PTR, _PTR, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
 }
 
 _LIB = None
@@ -1631,6 +1633,106 @@ class HipOps(Backend):
                 limit.data_ptr(), _ptr(stop_mask), seq_ptr, len_ptr, n_seq, int(stop_frame), length.data_ptr(), finish.data_ptr(), *extra,
                 S, V, _stream()), entry)
         return ids_out, logprob_out
+
+    # ---- beam search: the optional group "beam" (csrc/beam.hip) ---------------------------------------------------------
+    def beam_select(self, logits: torch.Tensor, cum: torch.Tensor, ended: torch.Tensor, length: torch.Tensor, ids: torch.Tensor,
+                    parent: torch.Tensor, beam_width: int, group_active: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                    stop_mask: Optional[torch.Tensor] = None, hist_parent: Optional[torch.Tensor] = None,
+                    hist_ids: Optional[torch.Tensor] = None, hist_cum: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
+                    t: int = -1) -> None:
+        """One step of beam search on the device (specification: sh/sample.py beam_select): logits [S, 512] bf16 | f32; per-slot state, in
+        place: cum [S] f32, ended [S] uint8 | bool, length [S] int64, ids [S] (or [S, 1]) int64; parent [S] int64 out.  Groups of
+        `beam_width` consecutive slots; group_active [S // beam_width] uint8 | bool; `allow` / `stop_mask`: the 64 bytes of
+        `pack_allow_mask`.  History [S, L]: hist_parent int32, hist_ids int64, hist_cum f32 (optional), written at column step[g] (`step`:
+        int64 [S // beam_width], advanced by the launch) or at the scalar `t`.  One launch, nothing read back: capturable."""
+        if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2 or not logits.is_cuda:
+            raise RuntimeError("beam_select: logits must be a [S, 512] bf16 or f32 device matrix")
+        S, V = logits.shape
+        W = int(beam_width)
+        if not 1 <= W <= 8 or S < W:
+            raise RuntimeError(f"beam_select: beam_width {W} must be 1 ... 8 and at most S = {S}")
+        if logits.stride(1) != 1 or logits.stride(0) % 8 or logits.stride(0) < V or logits.data_ptr() % 16:
+            logits = logits.contiguous()
+        dev, G = logits.device, S // W
+
+        def need(x, dtypes, shape, what, required=False):
+            if x is None and not required:
+                return
+            if x is None or x.dtype not in dtypes or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+                raise RuntimeError(f"beam_select: {what} must be a contiguous {dtypes[0]} tensor of shape {shape} on {dev}")
+        bytes_ = (torch.uint8, torch.bool)
+        need(cum, (torch.float32,), (S,), "cum", True)
+        need(ended, bytes_, (S,), "ended", True)
+        need(length, (torch.int64,), (S,), "length", True)
+        need(ids.view(-1), (torch.int64,), (S,), "ids", True)
+        need(parent, (torch.int64,), (S,), "parent", True)
+        need(group_active, bytes_, (G,), "group_active")
+        need(allow, (torch.uint8,), (64,), "allow")
+        need(stop_mask, (torch.uint8,), (64,), "stop_mask")
+        need(step, (torch.int64,), (G,), "step")
+        hist_len = 0
+        if step is not None or int(t) >= 0:
+            if hist_parent is None or hist_ids is None:
+                raise RuntimeError("beam_select: a step to record needs hist_parent and hist_ids")
+            hist_len = int(hist_parent.shape[1])
+            need(hist_parent, (torch.int32,), (S, hist_len), "hist_parent")
+            need(hist_ids, (torch.int64,), (S, hist_len), "hist_ids")
+            need(hist_cum, (torch.float32,), (S, hist_len), "hist_cum")
+        with self._t("beam_select"):
+            _check(self.lib.evo_beam_select_f32(logits.data_ptr(), int(logits.dtype == torch.float32), logits.stride(0), _ptr(allow),
+                                                _ptr(stop_mask), _ptr(group_active), cum.data_ptr(), ended.data_ptr(), length.data_ptr(),
+                                                ids.data_ptr(), parent.data_ptr(), _ptr(hist_parent), _ptr(hist_ids), _ptr(hist_cum), hist_len,
+                                                _ptr(step), int(t), W, S, V, _stream()), "evo_beam_select_f32")
+
+    def gather_table(self, fixed, per_token=()):
+        """Registers the tensors `gather_rows` moves: `fixed` [S, ...] whose whole rows move, `per_token` [S, n_tokens, ...] of which only
+        the first own_pos[parent] + 1 tokens move.  -> a `GatherTable` (the device table, the scratch buffer of S rows, its sizes)."""
+        tensors = [(x, False) for x in fixed] + [(x, True) for x in per_token]
+        if not tensors:
+            raise RuntimeError("gather_table: nothing to register")
+        S, dev = int(tensors[0][0].shape[0]), tensors[0][0].device
+        rows, off, max_row = [], 0, 0
+        for x, tok in tensors:
+            if not x.is_cuda or x.device != dev or x.shape[0] != S or x.dim() < (3 if tok else 2) or not x[0].is_contiguous():
+                raise RuntimeError("gather_table: every tensor is [S, ...] on one ROCm device with contiguous rows")
+            es = x.element_size()
+            stride, row = x.stride(0) * es, x[0].numel() * es
+            bpt = x[0, 0].numel() * es if tok else 0
+            if x.data_ptr() % 16 or stride % 16 or row % 16 or bpt % 16 or row < 16 or stride < row:
+                raise RuntimeError("gather_table: addresses, row strides, rows and tokens must be multiples of 16 bytes")
+            rows.append([x.data_ptr(), stride, row, bpt, off, 0])
+            off += row
+            max_row = max(max_row, row)
+        if S > 65535 or len(rows) > 65535:
+            raise RuntimeError("gather_table: at most 65535 slots and 65535 tensors")
+        return GatherTable(table=torch.tensor(rows, dtype=torch.int64).to(dev), scratch=torch.empty(S * off, dtype=torch.uint8, device=dev),
+                           row_bytes=off, max_row_bytes=max_row, n_slots=S, tensors=[x for x, _ in tensors])
+
+    def gather_rows(self, tab: "GatherTable", parent: torch.Tensor, own_pos: torch.Tensor) -> None:
+        """The reparenting copy (csrc/beam.hip): for every slot s with parent[s] != s, row parent[s] of every tensor of `tab` goes to row
+        s -- out to the scratch buffer in one launch, back in a second.  parent / own_pos: device int64 [S].  Capturable."""
+        S = tab.n_slots
+        for x, what in ((parent, "parent"), (own_pos, "own_pos")):
+            if x.dtype != torch.int64 or tuple(x.shape) != (S,) or not x.is_contiguous() or x.device != tab.table.device:
+                raise RuntimeError(f"gather_rows: {what} must be a contiguous int64 tensor of shape ({S},) on {tab.table.device}")
+        with self._t("gather_rows"):
+            for back in (0, 1):
+                _check(self.lib.evo_gather_rows(tab.table.data_ptr(), int(tab.table.shape[0]), parent.data_ptr(), own_pos.data_ptr(),
+                                                tab.scratch.data_ptr(), tab.row_bytes, tab.max_row_bytes, S, back, _stream()),
+                       "evo_gather_rows")
+
+
+class GatherTable:
+    """What `HipOps.gather_table` registers: table int64 [n, 6] on the device (include/evo_mi355x.h: evo_gather_rows), the scratch buffer
+    [S x row_bytes] bytes, and the tensors themselves (kept alive: the table holds their addresses)."""
+
+    def __init__(self, table, scratch, row_bytes, max_row_bytes, n_slots, tensors):
+        self.table, self.scratch, self.row_bytes, self.max_row_bytes, self.n_slots, self.tensors = \
+            table, scratch, int(row_bytes), int(max_row_bytes), int(n_slots), tensors
+
+    @property
+    def scratch_bytes(self) -> int:
+        return int(self.scratch.numel())
 
 
 _DEFAULT_OPS = None

@@ -59,6 +59,12 @@ table row then holds zeros again, the scrap page 0 that idle slots append into. 
 the `n_slots` largest jobs; with it a free slot takes the head of the queue only when enough pages are free (FIFO: the head blocks the
 jobs behind it; `stats["kv_page_waits"]` counts the slot-steps this idles), and a job larger than the whole budget is a ValueError.  The
 step appends with `rope_append_decode_paged` and attends with `attention_decode_paged`.  Not with `share_prompt_kv` or `kv_dtype="fp8"`.
+
+Beam search: `beam_search(prompts, n_tokens, beam_width)` on a pool built with `share_prompt_kv=True` returns the
+`beam_width` most likely continuations of every prompt.  A prompt owns a group of `beam_width` consecutive slots behind one store row; the
+captured step is forward, `beam_select` (the group's W x 512 candidates ranked on the device; parents, tokens and scores written where the
+next step reads them), `gather_rows` out to a scratch buffer and back (every record of a slot -- FIR history, modal state, the keys it has
+generated -- moves to the slot that continues its hypothesis), advance.  The host walks the recorded back-pointers when a group is fetched.
 """
 from __future__ import annotations
 
@@ -159,6 +165,7 @@ class DecodePool:
         self.hist_ids = self.hist_logits = self.hist_logprob = None
         self._ctl = None                                             # job control: the stop rule of the running generate()
         self._graph_key = None                                       # what the captured step's sampler launch was captured with
+        self._beam = self._beam_graph = None                         # beam search: its state and its captured step
 
     # ------------------------------------------------------------------ cache rows
     def _allocate(self, capacity: int) -> None:
@@ -383,7 +390,7 @@ class DecodePool:
         self.hist_logits = torch.zeros(S, n_tokens, self.model.vocab_size, dtype=torch.float32, device=dev)
         self._graph = None
 
-    def _prefill(self, ids: torch.Tensor):
+    def _prefill(self, ids: torch.Tensor, logits_dtype=torch.float32):
         """ids [1, P] -> (last-position logits [V] f32, the B = 1 caches of the prompt)."""
         m = self.model
         tmp = m.initialize_inference_params()
@@ -392,7 +399,7 @@ class DecodePool:
         with torch.inference_mode():
             logits, tmp = m(ids, inference_params_dict=tmp)
         self.stats["prefills"] += 1
-        return logits[0, -1].float(), tmp
+        return logits[0, -1].to(logits_dtype), tmp
 
     # ------------------------------------------------------------------ prompts admitted together share one prefill (opt-in)
     PREFILL_PAD = 64                                                   # StripedHyena.prefill_ragged's pad_to
@@ -416,7 +423,7 @@ class DecodePool:
             t_max = t
         return group
 
-    def _prefill_ragged(self, encoded: Sequence[torch.Tensor], group: Sequence[int]):
+    def _prefill_ragged(self, encoded: Sequence[torch.Tensor], group: Sequence[int], logits_dtype=torch.float32):
         """The prompts `group` in ONE forward -> (last-position logits [B, V] f32, the caches of the padded batch: row b = group[b])."""
         lens = [int(encoded[pi].shape[1]) for pi in group]
         T = max(lens)
@@ -426,7 +433,7 @@ class DecodePool:
             logits, tmp = self.model.prefill_ragged(ids, lens, pad_to=self.PREFILL_PAD, **fp8)
         self.stats["prefills"] += 1
         self.stats["prefill_pad_tokens"] += len(group) * (-(-T // self.PREFILL_PAD) * self.PREFILL_PAD) - sum(lens)
-        return logits.float(), tmp
+        return logits.to(logits_dtype), tmp
 
     def _install(self, slot: int, tmp: dict, P: int, row: int = 0, need: int = 0) -> None:
         m = self.model
@@ -528,7 +535,7 @@ class DecodePool:
                 return None
             self._graph[0].replay()
 
-    def _prefill_for(self, pi: int, jobs, slot_job, encoded, cached_prefill: Dict[int, tuple]) -> None:
+    def _prefill_for(self, pi: int, jobs, slot_job, encoded, cached_prefill: Dict[int, tuple], logits_dtype=torch.float32) -> None:
         """Prompt `pi` needs a prefill: it, and with `prefill_batch` > 1 the prompts admitted with it, land in `cached_prefill` as
         (last-position logits [V] f32, caches, row of those caches)."""
         cached_prefill.clear()                               # keep one prefill's caches alive at a time (every earlier prompt's copies are installed)
@@ -540,9 +547,9 @@ class DecodePool:
                                         [e.shape[1] for e in encoded])
             self.stats["prefill_prompts"] += len(group)
         if len(group) == 1:
-            cached_prefill[pi] = self._prefill(encoded[pi]) + (0,)
+            cached_prefill[pi] = self._prefill(encoded[pi], logits_dtype) + (0,)
         else:
-            lg, tmp_b = self._prefill_ragged(encoded, group)
+            lg, tmp_b = self._prefill_ragged(encoded, group, logits_dtype)
             for r, q in enumerate(group):
                 cached_prefill[q] = (lg[r], tmp_b, r)
 
@@ -982,6 +989,255 @@ class DecodePool:
             scores.append(float(np.mean(out_logprobs[j, :out_len[j]].numpy().astype(np.float64))))
         owner = [pi for pi in range(len(prompts)) for _ in range(n_spp)]
         return seqs, scores, owner
+
+
+    # ------------------------------------------------------------------ beam search
+    def _allocate_beam(self, W: int, n_tokens: int, has_stop: bool) -> dict:
+        """Per-pool state of a beam search: the per-slot vectors the selection launch reads and writes, the back-pointer history, and the
+        table of every per-slot record the reparenting copy moves.  Bound to the caches it registers: new caches, a new width or a longer
+        history make new state and drop the captured beam step."""
+        m, S, dev, ops = self.model, self.n_slots, self.device, self.model.ops
+        key = (W, has_stop)
+        b = self._beam
+        if b is not None and b["ipd"] is self.ipd and b["key"] == key and b["hist_parent"].shape[1] >= n_tokens:
+            return b
+        G = S // W
+        hy, mha = self.ipd["hyena"], self.ipd["mha"]
+        if getattr(ops, "beam_cum_dtype", torch.float32) == torch.float64:       # an fp64 backend: the search keeps the modal state in its precision too
+            for i in m.hyena_layer_idxs:
+                hy.state_dict[i] = hy.state_dict[i].to(torch.complex128)
+        fixed =[hy.fir_state_dict[i] for i in m.hyena_layer_idxs] + [hy.state_dict[i] for i in m.hyena_layer_idxs]
+        table = ops.gather_table(fixed, [mha.key_value_memory_dict[i] for i in m.attn_layer_idxs])
+        L = n_tokens
+        b = {"key": key, "ipd": self.ipd, "W": W, "G": G, "table": table,
+             "cum": torch.full((S,), float("-inf"), dtype=getattr(ops, "beam_cum_dtype", torch.float32), device=dev),
+             "ended": torch.zeros(S, dtype=torch.uint8, device=dev), "length": torch.zeros(S, dtype=torch.int64, device=dev),
+             "parent": torch.arange(S, dtype=torch.int64, device=dev), "active": torch.zeros(G, dtype=torch.uint8, device=dev),
+             "admit": torch.zeros(G, dtype=torch.uint8, device=dev), "step": torch.zeros(G, dtype=torch.int64, device=dev),
+             "hist_parent": torch.zeros(S, L, dtype=torch.int32, device=dev), "hist_ids": torch.zeros(S, L, dtype=torch.int64, device=dev),
+             "hist_cum": torch.zeros(S, L, dtype=getattr(ops, "beam_cum_dtype", torch.float32), device=dev),
+             "first": torch.zeros(S, m.vocab_size, dtype=getattr(ops, "beam_cum_dtype", torch.float32), device=dev),
+             "allow": None if self.allow_mask is None else ops.pack_allow_mask(self.allow_mask, dev),
+             "stop": torch.zeros(64, dtype=torch.uint8, device=dev) if has_stop else None}
+        self._beam, self._beam_graph = b, None
+        self.stats["beam_scratch_bytes"] = int(getattr(table, "scratch_bytes", 0))
+        return b
+
+    def _beam_select(self, logits: torch.Tensor, group_active: torch.Tensor) -> None:
+        b = self._beam
+        self.model.ops.beam_select(logits, b["cum"], b["ended"], b["length"], self.ids, b["parent"], b["W"], group_active=group_active,
+                                   allow=b["allow"], stop_mask=b["stop"], hist_parent=b["hist_parent"], hist_ids=b["hist_ids"],
+                                   hist_cum=b["hist_cum"], step=b["step"])
+
+    def _step_beam_eager(self) -> None:
+        """Forward, selection, the reparenting copy (out, then back), advance: every slot's records follow the hypothesis it now holds."""
+        b = self._beam
+        self._beam_select(self._step_eager(), b["active"])
+        self.model.ops.gather_rows(b["table"], b["parent"], self.store.own_pos)
+        self._advance()
+
+    def _step_beam(self) -> None:
+        self.stats["steps"] += 1
+        self.stats["beam_steps"] += 1
+        with torch.inference_mode():
+            if not self.use_graph:
+                return self._step_beam_eager()
+            if self._beam_graph is None:
+                self._step_beam_eager()                               # the first step runs eagerly and IS the step (see _step)
+                torch.cuda.synchronize(self.device)
+                self.model._row_index(self.n_slots, self.device)
+                g = torch.cuda.CUDAGraph()
+                with capture_graph(g):
+                    self._step_beam_eager()
+                self._beam_graph = g
+                return None
+            self._beam_graph.replay()
+
+    def beam_search(self, prompts: Sequence[str], n_tokens: int, beam_width: int = 4, stop_tokens=None, prepend_bos: bool = False,
+                    return_steps: bool = False, **refused) -> List["BeamResult"]:
+        """The `beam_width` most likely continuations of every prompt, by total log-probability: one `BeamResult` per
+        prompt, its hypotheses in rank order.  A prompt owns a group of `beam_width` consecutive slots; n_slots // beam_width prompts are
+        searched together, a finished group is fetched and re-filled while the others go on.  Needs `share_prompt_kv=True`; uses the
+        pool's `allowed_tokens`; `stop_tokens` end a hypothesis (it keeps its score and competes on) and are trimmed from its string; one
+        outside `allowed_tokens` can never be chosen and is harmless.  A
+        group is over after `n_tokens` steps, or sooner when every beam has ended (the host looks every `poll_every` steps).  No length
+        penalty, no temperature, no top-k / top-p.  `return_steps=True`: every result also carries the recorded per-step
+        (parent, token, cum) of its group."""
+        for name in ("constraints", "stop_sequences", "seed"):
+            if refused.pop(name, None) is not None:
+                raise ValueError(f"beam_search: {name} is not supported (a search is deterministic, and ends hypotheses on stop TOKENS only)")
+        if refused:
+            raise TypeError(f"beam_search: unexpected arguments {sorted(refused)}")
+        m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+        W = int(beam_width)
+        if not 1 <= W <= 8 or W > S:
+            raise ValueError(f"beam_width must be 1 ... 8 and at most n_slots = {S}, got {beam_width}")
+        if not self.share_prompt_kv:
+            raise ValueError("beam_search needs a pool built with share_prompt_kv=True (a beam group reads one stored copy of its prompt)")
+        if self.kv_dtype != "bf16" or self.kv_paged:                 # (such a pool cannot be built with share_prompt_kv; kept for the day it can)
+            raise ValueError('beam_search does not combine with kv_dtype="fp8" or kv_paged=True')
+        n_tokens = int(n_tokens)
+        if n_tokens < 1:
+            raise ValueError("n_tokens must be >= 1")
+        prompts = list(prompts)
+        if not prompts:
+            raise ValueError("beam_search: the prompt list is empty")
+        if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
+            raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
+        stop_set = None
+        if stop_tokens is not None and len(stop_tokens):
+            stop_set = allowed_mask(tok, stop_tokens)
+        if not Backend.adopt(m.ops).supports("beam"):
+            raise RuntimeError('beam_search needs a compute backend with the "beam" kernels (beam_select, gather_rows); this model\'s backend '
+                               "has none")
+        if hasattr(m, "eval"):
+            m.eval()
+        encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
+        G = S // W
+        self._allocate_shared(max(e.shape[1] for e in encoded), n_tokens, W, rows=min(G, len(prompts)))
+        b = self._allocate_beam(W, n_tokens, stop_set is not None)
+        if stop_set is not None:
+            b["stop"].copy_(m.ops.pack_allow_mask(stop_set, dev))
+        for name in ("beam_groups", "beam_steps", "beam_rows_moved", "polls"):
+            self.stats.setdefault(name, 0)
+        was = self.ipd["mha"].weight_dtype
+        self.ipd["mha"].weight_dtype = self.weight_dtype             # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
+        try:
+            return self._run_beam(prompts, encoded, n_tokens, stop_set, return_steps)
+        finally:
+            self.ipd["mha"].weight_dtype = was
+
+    def _run_beam(self, prompts, encoded, n_tokens, stop_set, return_steps):
+        m, tok, S, dev, b = self.model, self.tok, self.n_slots, self.device, self._beam
+        W, G = b["W"], b["G"]
+        jobs = deque((pi, pi) for pi in range(len(prompts)))         # (job, prompt) as _prefill_for reads them: one job per prompt
+        results: List[Optional[BeamResult]] = [None] * len(prompts)
+        group_job: List[Optional[int]] = [None] * G
+        group_n = [0] * G                                            # selections the group has been through (the admission's is the first)
+        cached_prefill: Dict[int, tuple] = {}
+        neg_inf = float("-inf")
+
+        def fill(g: int) -> None:
+            _, pi = jobs.popleft()
+            if pi not in cached_prefill:
+                self._prefill_for(pi, jobs, group_job, encoded, cached_prefill, logits_dtype=b["first"].dtype)
+            last_logits, tmp, row = cached_prefill[pi]
+            P = encoded[pi].shape[1]
+            rows = slice(g * W, g * W + W)
+            for s in range(g * W, g * W + W):                        # one store row; every slot of the group holds the prompt's states
+                self._install_shared(s, pi, tmp, P, **({"row": row} if row else {}))
+            b["cum"][rows] = neg_inf
+            b["cum"][g * W] = 0.0
+            b["ended"][rows] = 0
+            b["length"][rows] = 0
+            b["step"][g] = 0
+            self.ids[rows, 0] = encoded[pi][0, -1]
+            # the group's first selection is the same launch on the prefill's last logits: one live beam seeds W (nothing to move yet:
+            # the group's slots hold the same records)
+            b["first"][rows] = last_logits.to(b["first"].dtype)
+            b["admit"].zero_()
+            b["admit"][g] = 1
+            self._beam_select(b["first"], b["admit"])
+            self.pos[rows] = P
+            b["active"][g] = 1
+            group_job[g], group_n[g] = pi, 1
+            self.stats["beam_groups"] += 1
+
+        def fetch(groups: List[int]) -> None:
+            """Finished groups: their back-pointers and final state leave the device; the hypotheses are rebuilt on the host."""
+            slots = [s for g in groups for s in range(g * W, g * W + W)]
+            idx = torch.tensor(slots, dtype=torch.int64, device=dev)
+            self._release_shared(slots)
+            b["active"][torch.tensor(groups, dtype=torch.int64, device=dev)] = 0
+            T = max(min(group_n[g], n_tokens) for g in groups)
+            hp, hi, hc = b["hist_parent"][idx, :T].cpu(), b["hist_ids"][idx, :T].cpu(), b["hist_cum"][idx, :T].cpu()
+            cum, length, ended = b["cum"][idx].cpu(), b["length"][idx].cpu().tolist(), b["ended"][idx].cpu().tolist()
+            for k, g in enumerate(groups):
+                Tg, lo = min(group_n[g], n_tokens), k * W
+                res = BeamResult([], [], [], [])
+                for j in range(W):
+                    if not bool(cum[lo + j] > neg_inf):
+                        continue
+                    toks, s = [], g * W + j
+                    for col in range(Tg - 1, -1, -1):                # walk the back-pointers
+                        toks.append(int(hi[lo + s - g * W, col]))
+                        s = int(hp[lo + s - g * W, col])
+                    toks = toks[::-1][:length[lo + j]]               # (beyond its length an ended hypothesis only repeats its last token)
+                    n_text = len(toks) - (1 if ended[lo + j] and stop_set is not None and toks and bool(stop_set[toks[-1]]) else 0)
+                    res.sequences.append(tok.detokenize(toks[:n_text]))
+                    res.scores.append(float(cum[lo + j]))
+                    res.lengths.append(int(length[lo + j]))
+                    res.mean_scores.append(float(cum[lo + j]) / max(int(length[lo + j]), 1))
+                own = torch.arange(g * W, g * W + W, dtype=hp.dtype)[:, None]
+                self.stats["beam_rows_moved"] += int(((hp[lo:lo + W, 1:Tg] != own) & (hc[lo:lo + W, 1:Tg] > neg_inf)).sum())
+                if return_steps:
+                    res.steps = (hp[lo:lo + W, :Tg].clone(), hi[lo:lo + W, :Tg].clone(), hc[lo:lo + W, :Tg].clone())
+                results[group_job[g]] = res
+                group_job[g] = None
+
+        done, since_poll = 0, 0
+        while done < len(prompts):
+            filled = False
+            for g in range(G):
+                if group_job[g] is None and jobs:
+                    fill(g)
+                    filled = True
+            active = [g for g in range(G) if group_job[g] is not None]
+            due = [g for g in active if group_n[g] >= n_tokens]
+            look = stop_set is not None and filled                    # (a hypothesis may end on its first token)
+            if not due and not look:
+                self._count_prefix_streams()
+                self._step_beam()
+                since_poll += 1
+                for g in active:
+                    group_n[g] += 1
+                self.stats["tokens"] += len(active) * W
+                due = [g for g in active if group_n[g] >= n_tokens]
+            finished = due
+            if stop_set is not None and (look or due or since_poll >= self.poll_every or not jobs):
+                # the one read: is every beam of a group ended or empty?  (with nothing left to admit the host looks after every step)
+                over = (b["ended"].bool() | ~(b["cum"] > neg_inf))[:G * W].view(G, W).all(-1).cpu().tolist()
+                self.stats["polls"] += 1
+                since_poll = 0
+                finished = [g for g in active if over[g] or g in due]
+            if finished:
+                fetch(finished)
+                done += len(finished)
+        return results
+
+
+class BeamResult:
+    """What `beam_search` returns for one prompt: its non-empty hypotheses in rank order -- `sequences` (a stop token trimmed), `scores`
+    (total log-probability), `lengths` (tokens generated, the stop token included), `mean_scores` (score / length, to re-rank with) --
+    and, with return_steps=True, `steps` = (parent, token, cum), each [beam_width, steps run]: what every selection gave the group's
+    slots (parent: a slot index of the pool)."""
+
+    def __init__(self, sequences, scores, lengths, mean_scores, steps=None):
+        self.sequences, self.scores, self.lengths, self.mean_scores, self.steps = sequences, scores, lengths, mean_scores, steps
+
+    def __len__(self):
+        return len(self.sequences)
+
+    def __repr__(self):
+        return f"BeamResult(sequences={self.sequences!r}, scores={self.scores!r}, lengths={self.lengths!r})"
+
+
+def beam_search(prompts: Sequence[str], model, tokenizer, n_tokens: int, beam_width: int = 4, n_slots: Optional[int] = None,
+                allowed_tokens=None, stop_tokens=None, prefill_batch: int = 1, weight_dtype: str = "bf16", device: Optional[str] = None,
+                prepend_bos: bool = False, return_steps: bool = False, poll_every: int = 8) -> List[BeamResult]:
+    """The `beam_width` most likely continuations of every prompt (`DecodePool.beam_search` on a pool of its own with
+    `share_prompt_kv=True`; DESIGN.md section 24).  `n_slots` defaults to beam_width * min(len(prompts), 32 // beam_width)."""
+    prompts = list(prompts)
+    W = int(beam_width)
+    if not 1 <= W <= 8:
+        raise ValueError(f"beam_width must be 1 ... 8, got {beam_width}")
+    if not prompts:
+        raise ValueError("beam_search: the prompt list is empty")
+    if n_slots is None:
+        n_slots = W * min(len(prompts), 32 // W)
+    pool = DecodePool(model, tokenizer, n_slots=n_slots, device=device, allowed_tokens=allowed_tokens, share_prompt_kv=True,
+                      prefill_batch=prefill_batch, weight_dtype=weight_dtype, poll_every=poll_every)
+    return pool.beam_search(prompts, n_tokens, beam_width=W, stop_tokens=stop_tokens, prepend_bos=prepend_bos, return_steps=return_steps)
 
 
 def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, temp: float = 0.7, top_k: int = 4,

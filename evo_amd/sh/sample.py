@@ -294,3 +294,68 @@ def sample_dfa(logits: torch.Tensor, top_k: int, top_p: float, temperature: floa
     if not fin and cnt + 1 >= int(limit):
         fin = FINISH_LENGTH
     return tok, cnt + 1, fin, (state if nxt == DFA_ACCEPT else nxt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Beam search: the written specification of `evo_beam_select_f32` (csrc/beam.hip).  A prompt owns a GROUP of
+# W = beam_width consecutive slots g W ... g W + W - 1; G = S // W groups; slots >= G W and groups whose `group_active` is 0 are left
+# alone (parent[s] = s, everything else unchanged).  One step, per active group, on the rows the forward produced:
+#   * a LIVE beam b (cum[b] > -inf, not ended) offers (b, v) for every allowed token v with score cum[b] + (x[b, v] - lse[b]), in exactly
+#     that association; lse[b] is the log-sum-exp of the UNFILTERED row;
+#   * an ENDED beam offers itself: score, ids and length unchanged, it stays ended;
+#   * an EMPTY beam (cum == -inf) offers nothing;
+#   * a candidate whose score is NaN or -inf is none: a NaN logit is never chosen, a row whose lse is NaN or +inf (it holds a NaN or a
+#     +inf) offers nothing at all, and a -inf logit would only make an empty beam;
+#   * candidates rank by score descending (-0 and +0 are one value), then parent ascending, then token ascending; the best W go to the
+#     group's slots in rank order: slot g W + j gets parent (a SLOT index), token, cum, length[parent] + (0 if the parent had ended else 1),
+#     ended = parent ended or token in the stop set; with fewer than W candidates the remaining slots become empty: parent = s,
+#     cum = -inf, not ended, ids and length unchanged.
+
+def beam_select(logits: torch.Tensor, cum: torch.Tensor, ended: torch.Tensor, length: torch.Tensor, ids: torch.Tensor, beam_width: int,
+                group_active=None, allowed=None, stop_tokens=None, dtype=torch.float64):
+    """logits [S, V]; cum [S]; ended [S] (bool / u8); length [S]; ids [S] -> (parent, ids, cum, ended, length), new CPU tensors
+    (int64, int64, `dtype`, bool, int64); nothing is changed in place.  `allowed` / `stop_tokens`: bool masks [V] or None; `dtype`: what
+    the scores are evaluated in (torch.float32 is the kernel's arithmetic, up to the order of the sum inside lse)."""
+    W = int(beam_width)
+    x = logits.detach().to("cpu").to(dtype)
+    if x.dim() != 2:
+        raise ValueError("logits must be [S, V]")
+    S, V = x.shape
+    if not 1 <= W <= 8 or S < W:
+        raise ValueError("beam_select: 1 <= beam_width <= 8 and beam_width <= S")
+    old_cum = cum.detach().to("cpu").to(dtype).reshape(S)
+    old_end = ended.detach().to("cpu").reshape(S).bool()
+    old_len = length.detach().to("cpu").reshape(S).to(torch.int64)
+    old_ids = ids.detach().to("cpu").reshape(S).to(torch.int64)
+    allow = torch.ones(V, dtype=torch.bool) if allowed is None else torch.as_tensor(allowed, dtype=torch.bool).cpu()
+    stop = torch.zeros(V, dtype=torch.bool) if stop_tokens is None else torch.as_tensor(stop_tokens, dtype=torch.bool).cpu()
+    parent = torch.arange(S, dtype=torch.int64)
+    new_ids, new_cum, new_end, new_len = old_ids.clone(), old_cum.clone(), old_end.clone(), old_len.clone()
+    lse = torch.logsumexp(x, dim=-1)
+    neg_inf = float("-inf")
+    for g in range(S // W):
+        if group_active is not None and not bool(group_active[g]):
+            continue
+        cands = []                                                    # (-score, parent, token, score)
+        for b in range(g * W, g * W + W):
+            c = old_cum[b]
+            if not bool(c > neg_inf):                                 # empty (or NaN)
+                continue
+            if bool(old_end[b]):
+                cands.append((-float(c), b, int(old_ids[b]), c))
+                continue
+            score = c + (x[b] - lse[b])
+            ok = allow & (score > neg_inf)                            # (NaN compares false)
+            for v in torch.nonzero(ok).reshape(-1).tolist():
+                cands.append((-float(score[v]), b, v, score[v]))
+        cands.sort(key=lambda t: t[:3])
+        for j in range(W):
+            s = g * W + j
+            if j >= len(cands):
+                new_cum[s], new_end[s] = neg_inf, False               # empty; parent = s, ids and length as they were
+                continue
+            _, b, v, sc = cands[j]
+            parent[s], new_ids[s], new_cum[s] = b, v, sc
+            new_end[s] = bool(old_end[b]) or bool(stop[v])
+            new_len[s] = old_len[b] + (0 if bool(old_end[b]) else 1)
+    return parent, new_ids, new_cum, new_end, new_len

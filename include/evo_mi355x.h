@@ -746,6 +746,46 @@ int evo_sample_rows_dfa_f32(const void* logits, int64_t logits_f32, int64_t ld, 
                             const int32_t* dfa_next, int64_t n_states, const int64_t* dfa_base, int32_t* dfa_state,
                             int64_t S, int64_t V, void* stream);
 
+/* ---- beam search on the device (csrc/beam.hip; specification: evo_amd/sh/sample.py beam_select) ----------------
+ * evo_beam_select_f32: one step of beam search over logits [S, 512] (bf16, or f32 with logits_f32 != 0; row stride ld), one launch,
+ *   nothing read back: capturable.  A prompt owns a GROUP of W consecutive slots g W ... g W + W - 1, 1 <= W <= EVO_BEAM_MAX_WIDTH;
+ *   G = S / W groups.  Slots >= G W and the slots of a group with group_active[g] == 0 (group_active NULL: every group is active) get
+ *   parent[s] = s and nothing else is written for them.  Per-slot state, in / out: cum [S] f32 (sum of log-probabilities; -inf: the beam
+ *   is EMPTY), ended [S] bytes, length [S] int64, ids [S] int64 (the token the next step feeds).  Per active group:
+ *     a live beam b (cum > -inf, not ended) offers (b, v) for every token v of `allow` (64 bytes, bit j of byte i: token 8 i + j; NULL:
+ *     all) with score cum[b] + (x[b][v] - lse[b]) in f32 in exactly that association, lse[b] the log-sum-exp of the UNFILTERED row by
+ *     the sampler entries' own device code; an ended beam offers itself (score, ids, length unchanged; it stays ended); an empty beam
+ *     offers nothing; a score that is NaN or -inf is no candidate.  Candidates rank by score descending (-0 = +0), then parent
+ *     ascending, then token ascending.  Slot g W + j receives the j-th: parent (a slot index), ids = token, cum = score, length =
+ *     length[parent] + (0 if the parent had ended, else 1), ended = parent ended or token in `stop_mask` (64 bytes as `allow`, or NULL).
+ *     With fewer than W candidates the remaining slots become empty: parent = s, cum = -inf, ended = 0, ids and length unchanged.
+ *   All of a group's state is read before any of it is written (one barrier; only the group's first wave writes).
+ *   History: the step's column is step[g] when `step` (device int64 [G]) is given -- the launch then also writes step[g] + 1 back -- and
+ *   the scalar t otherwise; with a column in [0, hist_len) the launch records hist_parent[s][col] (int32), hist_ids[s][col] (int64) and,
+ *   when hist_cum is given, hist_cum[s][col] (f32) for the W slots of every active group ([S, hist_len] each).  t < 0 without `step`:
+ *   nothing is recorded and the history operands are ignored.
+ *   Returns -1 before any launch for: a null logits / cum / ended / length / ids / parent; logits not 16-byte aligned or another operand
+ *   not aligned to its element; W outside 1 ... 8; S < W or S > 2^31 - 1; V != 512; ld < V or ld % 8 != 0; a step to record (t >= 0, or
+ *   `step` given) with a null hist_parent or hist_ids or hist_len < 1.
+ * evo_gather_rows: the reparenting copy.  For every slot s with p = clamp(parent[s], 0, S - 1) != s, row p of every tensor of `table`
+ *   goes to row s -- OUT to the slot's scratch row (back == 0) and BACK from it (back == 1): the caller launches both, in that order, so
+ *   that no row is read after it may have been written.  `table`: device int64 [n_entries][EVO_GATHER_FIELDS] = (base address, row
+ *   stride in bytes, bytes of a row, bytes per token, offset in a scratch row, 0).  Bytes per token 0: the whole row moves; > 0: only
+ *   the first own_pos[p] + 1 tokens (clamped to the row; own_pos: device int64 [S]).  Every address, stride, size and offset is a
+ *   multiple of 16 (16-byte vector loads and stores); bytes beyond what moves, and slots with parent[s] == s, are untouched.  A copy
+ *   never leaves the slot's scratch row [s scratch_row_bytes, (s + 1) scratch_row_bytes).  max_row_bytes: the longest row of the table
+ *   (sizes the grid).  Returns -1 before any launch for: a null or misaligned table / parent / own_pos / scratch (scratch: 16 bytes);
+ *   n_entries or S outside 1 ... 65535; scratch_row_bytes or max_row_bytes < 16, no multiple of 16, or max_row_bytes >
+ *   scratch_row_bytes; back other than 0 or 1. */
+#define EVO_BEAM_MAX_WIDTH 8
+#define EVO_GATHER_FIELDS 6
+int evo_beam_select_f32(const void* logits, int64_t logits_f32, int64_t ld, const void* allow, const void* stop_mask,
+                        const uint8_t* group_active, float* cum, uint8_t* ended, int64_t* length, int64_t* ids, int64_t* parent,
+                        int32_t* hist_parent, int64_t* hist_ids, float* hist_cum, int64_t hist_len, int64_t* step, int64_t t,
+                        int64_t W, int64_t S, int64_t V, void* stream);
+int evo_gather_rows(const int64_t* table, int64_t n_entries, const int64_t* parent, const int64_t* own_pos, void* scratch,
+                    int64_t scratch_row_bytes, int64_t max_row_bytes, int64_t S, int64_t back, void* stream);
+
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:
  * bench.py times them in the same process right before the headline so that a driver-timed number can be compared across
