@@ -47,6 +47,10 @@ class Backend:
         # are linear / linear_residual_ / norm_linear / hyena_decode_fused / mlp_gate with the record in place of the weight(s)
         "w_fp8": ("w_quant_fp8", "linear_w8", "linear_residual_w8_", "norm_linear_w8", "hyena_decode_fused_w8", "mlp_gate_w8"),
         "kv_paged": ("rope_append_decode_paged", "attention_decode_paged"),               # the paged KV cache (InferenceParams.kv_layout == "paged")
+        # the batch-invariant single-token step (InferenceParams.batch_invariant): dense launches whose rows do not see how many ride along --
+        # linear_rowinv(x, w, b=None), linear_residual_rowinv_(res, x, w, bias=None), mlp_gate_rowinv(x_normed, w12, w12g=None); that step
+        # also calls hyena_step(z_t, fir_state, iir_state, fir_w, fir_b, poles, residues, dskip, n_heads) where the default one is fused
+        "row_invariant": ("linear_rowinv", "linear_residual_rowinv_", "mlp_gate_rowinv"),
         # beam search (DecodePool.beam_search): the step's selection, and the copy that moves a slot's records to the slot that continues it
         "beam": ("beam_select", "gather_rows"),
     }   # (single kernels go by their own name: rope_append_decode, unembed_profile, attention_prefix, attention_prefix_vt, attention_decode_prefix)

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "evo_attn_decode_paged_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
     "evo_beam_select_f32": ([_PTR, _I64, _I64] + [_PTR] * 11 + [_I64, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
     "evo_gather_rows": ([_PTR, _I64, _PTR, _PTR, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
+    "evo_linear_rowinv_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR, _I64, _PTR], _c.c_int),
+    "evo_mlp_gate_rowinv_bf16": ([_PTR] * 3 + [_I64] * 4 + [_PTR], _c.c_int),
 }
 
 _LIB = None
@@ -1153,6 +1155,43 @@ class HipOps(Backend):
                                                        *a[5:], pos.data_ptr(), part_o.data_ptr(), part_ml.data_ptr(), n_splits,
                                                        0.0 if prescaled else 1.0 / math.sqrt(hd), _stream()), "evo_attn_decode_paged_bf16")
         return o
+
+    # ---- row-invariant dense launches: the optional group "row_invariant" (csrc/gemv_inv.hip) ----
+    # One form per layer shape for 1-64 rows: row i of an M-row call is bit for bit the one-row call on row i.  A shape outside the contract
+    # (K % 256, N % 64, I % 32) is an error: another form would sum in another order.
+    def _linear_rowinv(self, x, w, b, res):
+        M, K = x.shape
+        N = w.shape[0]
+        if not self._bf16_ok(x, w) or (b is not None and not self._bf16_ok(b)) or (res is not None and not self._bf16_ok(res)):
+            raise RuntimeError("linear_rowinv: operands must be contiguous ROCm bf16 tensors")
+        if not 1 <= M <= 64 or K % 256 or N % 64 or w.shape[1] != K:
+            raise RuntimeError(f"linear_rowinv: x {tuple(x.shape)} against w {tuple(w.shape)}: need 1-64 rows, K % 256 == 0, N % 64 == 0")
+        y = res if res is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        ws = torch.empty(8 * M * N, dtype=torch.float32, device=x.device) if N < 8192 else None     # the K slices' partial sums
+        self._launch("gemv_rowinv", "evo_linear_rowinv_bf16", x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(), M, N, K, _ptr(ws),
+                     0 if ws is None else ws.numel() * 4)
+        return y
+
+    def linear_rowinv(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [M, K] @ w [N, K]^T (+ b) -> [M, N] bf16, every row computed as if it were alone (1 <= M <= 64)."""
+        return self._linear_rowinv(x, w, b, None)
+
+    def linear_residual_rowinv_(self, res: torch.Tensor, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """res += x @ w^T (+ bias) in place (fp32 accumulate, one rounding), every row computed as if it were alone."""
+        return self._linear_rowinv(x, w, bias, res)
+
+    def mlp_gate_rowinv(self, x: torch.Tensor, w12: Optional[torch.Tensor], w12g: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """a [M, I] = gelu(x @ W1^T) * (x @ W2^T) on rows x that are already normalised; w12 = [W1; W2], or (w12 None) the regrouped w12g."""
+        M, K = x.shape
+        wsrc = w12 if w12 is not None else w12g
+        I = wsrc.shape[0] // 2
+        if not self._bf16_ok(x, wsrc):
+            raise RuntimeError("mlp_gate_rowinv: operands must be contiguous ROCm bf16 tensors")
+        if not 1 <= M <= 64 or K % 256 or I % 32 or wsrc.shape[1] != K:
+            raise RuntimeError(f"mlp_gate_rowinv: x {tuple(x.shape)} against w12 {tuple(wsrc.shape)}: need 1-64 rows, K % 256 == 0, I % 32 == 0")
+        a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
+        self._launch("gemv_gate_rowinv", "evo_mlp_gate_rowinv_bf16", x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, 1 if w12 is None else 0)
+        return a
 
     # ---- FP8 (e4m3fn) weights for the single-token step at 1-8 rows: the optional group "w_fp8" (csrc/gemv_fp8.hip; DESIGN.md section 22) ----
     # Each method is its bf16 namesake with an Fp8Weight record in place of the weight, and takes the same route: fused where the bf16

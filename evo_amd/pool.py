@@ -60,6 +60,14 @@ the `n_slots` largest jobs; with it a free slot takes the head of the queue only
 jobs behind it; `stats["kv_page_waits"]` counts the slot-steps this idles), and a job larger than the whole budget is a ValueError.  The
 step appends with `rope_append_decode_paged` and attends with `attention_decode_paged`.  Not with `share_prompt_kv` or `kv_dtype="fp8"`.
 
+`batch_invariant=True` (opt-in; pools of up to 64 slots): a job's tokens, recorded logits and `last_logprobs` depend on
+the model, its prompt, its sampling arguments, the seed and its sample index -- not on `n_slots`, the slot it ran in, the other jobs of the
+call, the cache capacity, `kv_paged` / `kv_page_tokens`, `poll_every` or `EVO_AMD_DECODE_GRAPH`.  The step then runs ONE launch sequence at
+every slot count -- norm, row-invariant projection (csrc/gemv_inv.hip), Hyena step or rotary + append, decode attention with 32 splits,
+row-invariant output projection, norm, row-invariant gate and l3, final norm, row-invariant unembedding -- and gives up the fused dot2
+launches of 1-8 slots.  Refused (ValueError, each has row-count- or group-dependent arithmetic of its own): `n_slots` > 64,
+`prefill_batch` > 1, `share_prompt_kv`, `kv_dtype="fp8"`, `weight_dtype="fp8"`, and `beam_search` on such a pool.
+
 Beam search: `beam_search(prompts, n_tokens, beam_width)` on a pool built with `share_prompt_kv=True` returns the
 `beam_width` most likely continuations of every prompt.  A prompt owns a group of `beam_width` consecutive slots behind one store row; the
 captured step is forward, `beam_select` (the group's W x 512 candidates ranked on the device; parents, tokens and scores written where the
@@ -76,7 +84,8 @@ import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
 from .backend import Backend
-from .sh.cache import Fp8KV, PagedKV, PromptStore, check_kv_dtype, check_page_tokens, check_weight_dtype, check_weight_rows
+from .sh.cache import (Fp8KV, PagedKV, PromptStore, check_kv_dtype, check_page_tokens, check_rowinv_rows, check_weight_dtype,
+                       check_weight_rows)
 from .sh.model import capture_graph
 from .constraints import TokenConstraint
 from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
@@ -88,9 +97,21 @@ class DecodePool:
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
                  prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16", weight_dtype: str = "bf16",
-                 kv_paged: bool = False, kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None):
+                 kv_paged: bool = False, kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None, batch_invariant: bool = False):
         self.model = model
         self.kv_dtype = check_kv_dtype(kv_dtype)
+        self.batch_invariant = bool(batch_invariant)
+        if self.batch_invariant:                                     #  every refusal before any device work
+            check_rowinv_rows(int(n_slots), "n_slots")
+            for what, bad in (("prefill_batch > 1 (a padded batch's prefill depends on the prompts admitted together)", int(prefill_batch) > 1),
+                              ("share_prompt_kv=True (the grouped decode attention splits by group)", bool(share_prompt_kv)),
+                              ('kv_dtype="fp8"', self.kv_dtype != "bf16"), ('weight_dtype="fp8"', weight_dtype != "bf16")):
+                if bad:
+                    raise ValueError(f"batch_invariant=True does not combine with {what}")
+            ops = getattr(model, "ops", None)
+            if ops is None or not Backend.adopt(ops).supports("row_invariant", "hyena_step"):
+                raise RuntimeError('batch_invariant=True needs a compute backend with the "row_invariant" kernels ('
+                                   + ", ".join(Backend.OPTIONAL["row_invariant"]) + ") and hyena_step; this model's backend has none")
         self.kv_paged = bool(kv_paged)
         if self.kv_paged:                                            #  every refusal before any device work
             if share_prompt_kv:
@@ -142,7 +163,7 @@ class DecodePool:
         self.ipd = None
         self.capacity = 0
         self._graph = None
-        self.stats = {"steps": 0, "prefills": 0, "tokens": 0}
+        self.stats = {"steps": 0, "prefills": 0, "tokens": 0, "batch_invariant": self.batch_invariant}
         if hasattr(model, "decode_weight_bytes"):
             self.stats.update({"weight_dtype": self.weight_dtype, "decode_weight_bytes": model.decode_weight_bytes(self.weight_dtype)})
         if self.share_prompt_kv:
@@ -180,6 +201,7 @@ class DecodePool:
         ipd["mha"].max_seqlen = capacity
         ipd["mha"].kv_dtype = self.kv_dtype
         ipd["mha"].weight_dtype = self.weight_dtype                  # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
+        ipd["mha"].batch_invariant = self.batch_invariant
         D, H, hd = m.hidden_size, m.num_heads, m.head_dim
         dt = m.embedding_layer.weight.dtype
         for i in m.attn_layer_idxs:
@@ -239,6 +261,7 @@ class DecodePool:
             ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
             ipd["mha"].kv_layout = "paged"
             ipd["mha"].weight_dtype = self.weight_dtype
+            ipd["mha"].batch_invariant = self.batch_invariant
             D = m.hidden_size
             dt = m.embedding_layer.weight.dtype
             for i in m.hyena_layer_idxs:
@@ -463,7 +486,8 @@ class DecodePool:
         mha.pos_tensor = self.pos
         try:
             h = m.hidden_states(self.ids, self.ipd)
-            return m.ops.linear(h, m.unembed.weight, None).view(self.n_slots, m.vocab_size)
+            unembed = m.ops.linear_rowinv if self.batch_invariant else m.ops.linear
+            return unembed(h, m.unembed.weight, None).view(self.n_slots, m.vocab_size)
         finally:
             mha.pos_tensor = None
 
@@ -1068,6 +1092,8 @@ class DecodePool:
                 raise ValueError(f"beam_search: {name} is not supported (a search is deterministic, and ends hypotheses on stop TOKENS only)")
         if refused:
             raise TypeError(f"beam_search: unexpected arguments {sorted(refused)}")
+        if self.batch_invariant:
+            raise ValueError("beam_search does not combine with batch_invariant=True (a beam group's attention splits by group)")
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         W = int(beam_width)
         if not 1 <= W <= 8 or W > S:
@@ -1245,7 +1271,7 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
                 poll_every: int = 8, constraints=None, kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_paged: bool = False,
-                kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None):
+                kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None, batch_invariant: bool = False):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
@@ -1256,11 +1282,12 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     constrained generation on the device.  `kv_dtype="fp8"`: the pool's KV cache in FP8 e4m3fn, about half the bytes
     (not with `share_prompt_kv`).  `kv_paged=True`: the KV cache is a pool of pages of `kv_page_tokens` tokens, a job
     holds what its own prompt and limit need, and `kv_budget_tokens` caps the pool (not with `share_prompt_kv` or
-    `kv_dtype="fp8"`)."""
+    `kv_dtype="fp8"`).  `batch_invariant=True`: with a `seed`, every job's result is the same bits at any `n_slots` from 1 to 64 (DESIGN.md
+    section 25; not with `prefill_batch` > 1, `share_prompt_kv`, `kv_dtype="fp8"` or `weight_dtype="fp8"`)."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
                       allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every,
                       kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_paged=kv_paged, kv_page_tokens=kv_page_tokens,
-                      kv_budget_tokens=kv_budget_tokens)
+                      kv_budget_tokens=kv_budget_tokens, batch_invariant=batch_invariant)
     ctl = {}
     if stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1 or not return_logits:
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)

@@ -164,6 +164,16 @@ def check_weight_rows(rows: int, what: str) -> None:
                          "are bf16 only)")
 
 
+ROWINV_MAX_ROWS = 64    # batch rows the row-invariant dense launches serve (csrc/gemv_inv.hip)
+ROWINV_SPLITS = 32      # decode-attention splits of the batch-invariant step: what HipOps._decode_splits returns from 1,857 keys of capacity up
+
+
+def check_rowinv_rows(rows: int, what: str) -> None:
+    """ValueError when `rows` decode streams are more than the row-invariant launches serve."""
+    if rows > ROWINV_MAX_ROWS:
+        raise ValueError(f"batch_invariant=True serves at most {ROWINV_MAX_ROWS} rows per decode step, got {what} = {rows}")
+
+
 def fp8_row_rule(w: Tensor):
     """THE RULE of the FP8 formats (include/evo_mi355x.h, ABI 19 / 20) in torch, on rows w [N, K]: with a = max |w[n, :]|, e is the smallest
     integer with a 2^-e <= 448, clamped to [-126, 120] (a = 0: e = 0) -> (bytes RNE_e4m3fn(w 2^-e) [N, K] uint8, scales 2^e [N] f32).
@@ -220,6 +230,9 @@ class InferenceParams:
     # "bf16" (default) or "fp8": the dense weights the single-token steps on this cache stream (opt-in).  Read for
     # the Hyena blocks of the step too: the choice belongs to the generation, and this record is the one every step carries
     weight_dtype: str = "bf16"
+    # set: the single-token steps on this cache run ONE launch sequence whose arithmetic per row does not depend on the number of rows or
+    # on the cache capacity (opt-in, the decode pool).  Like weight_dtype it is read for the Hyena blocks too
+    batch_invariant: bool = False
     lengths_per_sample: Optional[Tensor] = None
     # set: the rows continue the first `seqlen_offset` tokens of a shared reference -- attention reads that prefix from shared_prefix.kv and
     # no per-row KV buffer is allocated or written (StripedHyena._attn_block)

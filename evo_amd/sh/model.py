@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
-from .cache import Fp8KV, InferenceParams, PagedKV, RecurrentInferenceParams, check_kv_dtype, check_weight_dtype, check_weight_rows
+from .cache import (ROWINV_SPLITS, Fp8KV, InferenceParams, PagedKV, RecurrentInferenceParams, check_kv_dtype, check_rowinv_rows, check_weight_dtype,
+                    check_weight_rows)
 from .utils import dotdict
 
 
@@ -522,22 +523,25 @@ class StripedHyena(nn.Module):
     # ------------------------------------------------------------------ blocks
     DECODE_ROWS = Backend.DECODE_ROWS         # batches this small take the fused single-token launches (Backend.fused_rows_ok)
 
-    def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False, w8=None):
+    def _mixer_out_(self, blk, x2d, y, w, bias, mfma=False, w8=None, inv=False):
         """x += y @ w^T + bias, the mixer's output projection (bias in the dense layer's epilogue: one rounding where the reference rounds twice).
-        `w8`: the block's FP8 weight records (a single-token step with weight_dtype == "fp8"), else None."""
-        if w8 is not None:
+        `w8`: the block's FP8 weight records (a single-token step with weight_dtype == "fp8"), else None.  `inv`: a batch-invariant
+        single-token step."""
+        if inv:
+            self.ops.linear_residual_rowinv_(x2d, y, w, bias=bias)
+        elif w8 is not None:
             self.ops.linear_residual_w8_(x2d, y, w8["out"], bias=bias)
         elif y.dim() == 4:                                     # the Hyena operator's blocked output (ops.hyena_ct)
             self.ops.linear_residual_yblk_(x2d, y, w, bias=bias)
         else:
             self.ops.linear_residual_(x2d, y, w, mfma=mfma, bias=bias)
 
-    def _finish_block(self, blk, x2d, y, w, bias, nf, mask=None, mfma=False, w8=None):
+    def _finish_block(self, blk, x2d, y, w, bias, nf, mask=None, mfma=False, w8=None, inv=False):
         """Every block's end: x += y @ w^T + bias, then x += MLP(x).  `nf` (_nf_ok): returns the NEXT block's `rs`; else None.  `mask`: [B T, 1]."""
         if nf:
             return self._mlp_residual_rs_(blk, x2d, self._mixer_out_rs_(blk, x2d, y, w, bias))
-        self._mixer_out_(blk, x2d, y, w, bias, mfma=mfma, w8=w8)
-        self._mlp_residual_(blk, x2d, mask, w8=w8)
+        self._mixer_out_(blk, x2d, y, w, bias, mfma=mfma, w8=w8, inv=inv)
+        self._mlp_residual_(blk, x2d, mask, w8=w8, inv=inv)
         return None
 
     # ---- RMSNorm folded into the dense layers around it (csrc/gemm.hip NF; DESIGN.md): `rs` = every row's 1 / (rms + eps), block to block
@@ -584,9 +588,13 @@ class StripedHyena(nn.Module):
             mlp._w12g = self.ops.pack_gate_weights(mlp._w12)
         return mlp._w12g
 
-    def _mlp_residual_(self, blk, x2d, mask=None, w8=None):
+    def _mlp_residual_(self, blk, x2d, mask=None, w8=None, inv=False):
         """x += MLP(post_norm(x)), in place; `mask` (flat [B T, 1]): upstream's (mixer out + u) * padding_mask first."""
         ops = self.ops
+        if inv:                                                          # norm, gate, l3: three launches at every row count
+            n2 = ops.rmsnorm(x2d, None, blk.post_norm.scale, self.eps)
+            ops.linear_residual_rowinv_(x2d, ops.mlp_gate_rowinv(n2, blk.mlp._w12, w12g=blk.mlp._w12g), blk.mlp._w3)
+            return
         if w8 is not None:                                               # (single-token steps carry no mask)
             a = ops.mlp_gate_w8(x2d, w8["w12"], blk.post_norm.scale, self.eps, grouped=blk.mlp._w12 is None)
             ops.linear_residual_w8_(x2d, a, w8["w3"])
@@ -631,7 +639,7 @@ class StripedHyena(nn.Module):
         return (ops.hyena_ct_flag and ops.supports("hyena_ct") and x2d.is_cuda and w.dtype == torch.bfloat16
                 and w.is_contiguous() and ops.zt_shape_ok(B, T, w.shape[0], w.shape[1]))
 
-    def _hyena_block(self, i, blk, x2d, B, T, cache: Optional[RecurrentInferenceParams], mask=None, rs=None, w8=None):
+    def _hyena_block(self, i, blk, x2d, B, T, cache: Optional[RecurrentInferenceParams], mask=None, rs=None, w8=None, inv=False):
         """One Hyena block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  Three routes: the decode step,
         the channel-major operator, the modal form.  `mask` = (flat [B*T,1] bf16, [B,T] uint8) of upstream's
         padding_mask, or None: the projections output, the FIR output and the mixer output + residual are multiplied by it, as upstream's
@@ -642,14 +650,21 @@ class StripedHyena(nn.Module):
             raise ValueError("a ragged prefill (lengths) starts at t = 0 without a padding mask: no resumed prefill, no mask")
         nf = False
         w8 = w8 if have_state and T == 1 else None            # (only the single-token cached route takes the FP8 launches)
-        if have_state and T == 1:
+        inv = inv and have_state and T == 1                   # (and only it the row-invariant ones)
+        if inv:                                               # norm, projection, step: the unfused sequence, at every row count
+            f = blk.filter
+            z = self.ops.linear_rowinv(self.ops.rmsnorm(x2d, None, blk.pre_norm.scale, self.eps), blk.projections.weight, blk.projections.bias)
+            y = self.ops.hyena_step(z, cache.fir_state_dict[i], cache.state_dict[i], f._fir_w, f.short_filter_bias, f._poles, f._residues, f.D,
+                                    self.num_heads)
+        elif have_state and T == 1:
             y = self._hyena_decode_step(blk, x2d, cache.fir_state_dict[i], cache.state_dict[i], w8)
         elif mask is None and self._mfma_hyena_ok(B, T) and self._hyena_ct_ok(x2d, blk, B, T) and self._table_ok(blk):
             nf = self._nf_ok(B * T, mask)
             y = self._hyena_channel_major(i, blk, x2d, B, T, cache, lens, rs, nf)
         else:
             y = self._hyena_modal(i, blk, x2d, B, T, cache, lens, mask)
-        return self._finish_block(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf, None if mask is None else mask[0], w8=w8)
+        return self._finish_block(blk, x2d, y, blk.out_filter_dense.weight, blk.out_filter_dense.bias, nf, None if mask is None else mask[0], w8=w8,
+                                  inv=inv)
 
     def _hyena_decode_step(self, blk, x, fir_state, iir_state, w8=None):
         """One token per row: norm + projections + FIR / modal step + gate in one launch; the two states advance in place.  `w8`: the
@@ -783,7 +798,7 @@ class StripedHyena(nn.Module):
             cache.key_value_memory_dict[i] = kv = new
         return kv
 
-    def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None, w8=None):
+    def _attn_block(self, i, blk, x2d, B, T, cache: Optional[InferenceParams], mask=None, rs=None, w8=None, inv=False):
         """One attention block on the stream x2d [B T, D], in place; returns the next block's `rs` (or None).  After Wqkv, by the cache:
         per-row decode step (pos_tensor), shared-prefix attention, scalar-offset decode step, causal attention; an FP8
         cache (cache.kv_dtype == "fp8") takes _attn_fp8 for all of them."""
@@ -795,7 +810,15 @@ class StripedHyena(nn.Module):
         nf = T > 1 and self._nf_ok(B * T, mask)
         # (only the decode branch -- one token on a layer that holds keys -- takes the FP8 launches)
         w8 = w8 if T == 1 and cache is not None and i in cache.key_value_memory_dict else None
-        if w8 is not None:
+        # a batch-invariant step: the per-row decode branch on a bf16 cache, contiguous or paged, with a fixed split count
+        inv = inv and T == 1 and cache is not None and i in cache.key_value_memory_dict
+        if inv and (cache.pos_tensor is None or cache.pos_tensor.numel() != B or cache.prompt_store is not None or cache.kv_dtype != "bf16"):
+            raise ValueError("a batch-invariant step is the per-row single-token step (pos_tensor, one position per row) on a bf16 KV cache "
+                             "without a prompt store")
+        splits = ROWINV_SPLITS if inv else None
+        if inv:
+            qkv = ops.linear_rowinv(ops.rmsnorm(x2d, None, blk.pre_norm.scale, self.eps), mha.Wqkv.weight, mha.Wqkv.bias).view(B, T, 3, H, hd)
+        elif w8 is not None:
             qkv = ops.norm_linear_w8(x2d, blk.pre_norm.scale, self.eps, w8["in"], mha.Wqkv.bias).view(B, T, 3, H, hd)
         elif nf and rs is not None:
             wqkv_f = self._folded(mha, "_wqkv_f", mha.Wqkv.weight, blk.pre_norm.scale)
@@ -812,7 +835,7 @@ class StripedHyena(nn.Module):
         pre = bool(ops.attn_prescale)
         q_scale = ops.attn_q_scale(hd) if pre else 1.0
         if cache is not None and (cache.kv_layout != "contiguous" or isinstance(cache.key_value_memory_dict.get(i), PagedKV)):
-            a = self._attn_paged(i, qkv, B, T, cache, off, pos, mask, pre, q_scale)
+            a = self._attn_paged(i, qkv, B, T, cache, off, pos, mask, pre, q_scale, splits)
         elif cache is not None and cache.kv_dtype != "bf16":
             a = self._attn_fp8(i, qkv, B, T, cache, off, pos, mask, pre, q_scale)
         elif pos is not None and T == 1:
@@ -833,7 +856,7 @@ class StripedHyena(nn.Module):
                 a = ops.attention_decode_prefix(q, kv[:, :, 0], kv[:, :, 1], widx, skv[:, :, 0], skv[:, :, 1], store.row, store.length,
                                                 prescaled=pre)
             else:
-                a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, prescaled=pre)
+                a = ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], pos=pos, n_splits=splits, prescaled=pre)
         else:
             cos, sin = self._rotary(off, T, x2d.device)
             ops.rope_(qkv, cos, sin, q_scale=q_scale)
@@ -853,7 +876,7 @@ class StripedHyena(nn.Module):
                 else:
                     a = ops.attention(q, k, v, off, prescaled=pre)
         return self._finish_block(blk, x2d, a.view(B * T, D), mha.out_proj.weight, mha.out_proj.bias, nf, None if mask is None else mask[0],
-                                  mfma=True, w8=w8)
+                                  mfma=True, w8=w8, inv=inv)
 
     def _attn_fp8(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float):
         """_attn_block's attention on an FP8 KV cache (cache.kv_dtype == "fp8"): a fresh prefill attends to its own bf16
@@ -886,7 +909,7 @@ class StripedHyena(nn.Module):
             return ops.attention_decode(q, qkv[:, :, 1], qkv[:, :, 2], prescaled=pre)
         return ops.attention(q, qkv[:, :, 1], qkv[:, :, 2], 0, prescaled=pre)
 
-    def _attn_paged(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float):
+    def _attn_paged(self, i, qkv, B, T, cache: InferenceParams, off: int, pos, mask, pre: bool, q_scale: float, n_splits=None):
         """_attn_block's attention on a paged KV cache (cache.kv_layout == "paged"): the per-row single-token step of a
         decode pool and nothing else -- prompts are prefilled on contiguous caches of their own and copied into pages."""
         ops = self.ops
@@ -906,7 +929,7 @@ class StripedHyena(nn.Module):
                                "attention_decode_paged); this model's backend has none")
         kv = kv.rows(B)
         ops.rope_append_decode_paged(qkv, kv, pos, self._inv_freq(qkv.device), self.rotary_scaling, q_scale=q_scale)
-        return ops.attention_decode_paged(qkv[:, :, 0], kv, pos, prescaled=pre)
+        return ops.attention_decode_paged(qkv[:, :, 0], kv, pos, n_splits=n_splits, prescaled=pre)
 
     # ------------------------------------------------------------------ forward
     max_rows_per_pass = 160 * 1024     # rows (B T) of one stateless pass; larger batches run in row groups (hidden_states)
@@ -992,6 +1015,14 @@ class StripedHyena(nn.Module):
         if T == 1 and mha_c is not None and check_weight_dtype(mha_c.weight_dtype) == "fp8":     # 
             check_weight_rows(B, "batch rows")
             w8s = self.prepare_fp8_weights()._w8
+        inv = T == 1 and mha_c is not None and bool(mha_c.batch_invariant)                         # 
+        if inv:
+            if w8s is not None:
+                raise ValueError('batch_invariant does not combine with weight_dtype="fp8": the row-invariant launches are bf16')
+            check_rowinv_rows(B, "batch rows")
+            if not self.ops.supports("row_invariant", "hyena_step"):
+                raise RuntimeError('batch_invariant needs a compute backend with the "row_invariant" kernels ('
+                                   + ", ".join(Backend.OPTIONAL["row_invariant"]) + ") and hyena_step; this model's backend has none")
         taps, tap_idxs = self.block_taps, self.block_tap_idxs
         for i in range(stop):
             blk = self.blocks[i]
@@ -999,9 +1030,9 @@ class StripedHyena(nn.Module):
                 taps.append(h.clone())
             # rs: 1 / (rms + eps) of every row of h, from the epilogue of the dense layer that wrote it (None: the block norms h itself)
             if isinstance(blk, _AttentionBlock):
-                rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs, w8=None if w8s is None else w8s[i])
+                rs = self._attn_block(i, blk, h, B, T, mha_c, mask, rs, w8=None if w8s is None else w8s[i], inv=inv)
             else:
-                rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs, w8=None if w8s is None else w8s[i])
+                rs = self._hyena_block(i, blk, h, B, T, hy_c, mask, rs, w8=None if w8s is None else w8s[i], inv=inv)
             if after_block is not None:
                 after_block(i, h)
         if stop == self.num_layers and taps is not None and (tap_idxs is None or self.num_layers in tap_idxs):
@@ -1141,6 +1172,13 @@ class StripedHyena(nn.Module):
         """False once `model.unembed` has been replaced by another module (the identity-unembed embedding recipe)."""
         return isinstance(self.unembed, _Unembed)
 
+    def unembed_rows(self, h: torch.Tensor, ipd) -> torch.Tensor:
+        """The logits [rows, V] of final-norm rows h of a single-token step on the caches `ipd`: the row-invariant launch when the step
+        is batch-invariant, the plain dense layer otherwise."""
+        if ipd is not None and ipd["mha"].batch_invariant:
+            return self.ops.linear_rowinv(h, self.unembed.weight, None)
+        return self.ops.linear(h, self.unembed.weight, None)
+
     def _unembed_output(self, h: torch.Tensor, B: int, T: int) -> torch.Tensor:
         """What forward returns for the final-norm hidden states h [B T, D]: the logits [B, T, V], or -- with `model.unembed` replaced --
         whatever the replacement's unembed() makes of h [B, T, D] (upstream users swap in an identity module to get embeddings)."""
@@ -1180,6 +1218,7 @@ class StripedHyena(nn.Module):
         # neither recycle a CPython id() nor a caching-allocator address of a freed buffer.
         same_bufs = (st is not None and st["B"] == B and st["mha"] is mha and st["hyena"] is hy and st["kv_dtype"] == mha.kv_dtype
                      and st["kv_layout"] == mha.kv_layout and st["weight_dtype"] == mha.weight_dtype
+                     and st["batch_invariant"] == bool(mha.batch_invariant)
                      and all(mha.key_value_memory_dict.get(i) is t for i, t in st["kv"].items())
                      and all(hy.state_dict.get(i) is t for i, t in st["iir"].items())
                      and all(hy.fir_state_dict.get(i) is t for i, t in st["fir"].items()))
@@ -1197,7 +1236,7 @@ class StripedHyena(nn.Module):
                     return None
                 dev = self.device
                 st = {"B": B, "mha": mha, "hyena": hy, "kv_dtype": mha.kv_dtype, "kv_layout": mha.kv_layout,
-                      "weight_dtype": mha.weight_dtype,
+                      "weight_dtype": mha.weight_dtype, "batch_invariant": bool(mha.batch_invariant),
                       "ids": torch.zeros(B, 1, dtype=torch.int64, device=dev),
                       "pos": torch.zeros(B, dtype=torch.int64, device=dev),
                       "kv": {i: mha.key_value_memory_dict[i] for i in self.attn_layer_idxs},
@@ -1214,7 +1253,7 @@ class StripedHyena(nn.Module):
                 try:
                     with capture_graph(g):
                         h = self.hidden_states(st["ids"], ipd)
-                        st["logits"] = self.ops.linear(h, self.unembed.weight, None).view(B, 1, self.vocab_size)
+                        st["logits"] = self.unembed_rows(h, ipd).view(B, 1, self.vocab_size)
                         st["pos"].add_(1)
                 finally:
                     mha.pos_tensor = None

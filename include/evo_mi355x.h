@@ -80,7 +80,10 @@ extern "C" {
  *      quantising stores and the decode attention that reads them, csrc/kv_fp8.hip); no signature changed.
  *  20: evo_w_quant_fp8, evo_linear_small_m_w8, evo_norm_linear_small_m_w8, evo_hyena_decode_fused_small_m_w8, evo_mlp_gate_small_m_w8
  *      and evo_norm_mlp_gate_small_m_w8 added (opt-in FP8 e4m3fn WEIGHTS for the decode step at 1-8 rows, csrc/gemv_fp8.hip); no
- *      signature changed. */
+ *      signature changed.
+ *      Added since under ABI 20, no signature changed: the paged KV entries, the beam search entries, and evo_linear_rowinv_bf16 /
+ *      evo_mlp_gate_rowinv_bf16 (the row-invariant dense launches of the decode pool's opt-in batch-invariant step, csrc/gemv_inv.hip).
+ *      A binding that needs them finds out at load time: every entry it declares must be exported. */
 #define EVO_ABI_VERSION 20
 int evo_abi_version(void);
 
@@ -785,6 +788,22 @@ int evo_beam_select_f32(const void* logits, int64_t logits_f32, int64_t ld, cons
                         int64_t W, int64_t S, int64_t V, void* stream);
 int evo_gather_rows(const int64_t* table, int64_t n_entries, const int64_t* parent, const int64_t* own_pos, void* scratch,
                     int64_t scratch_row_bytes, int64_t max_row_bytes, int64_t S, int64_t back, void* stream);
+
+/* ---- row-invariant weight-streaming dense layers (added under ABI 20, no signature changed; csrc/gemv_inv.hip; no counterpart in the reference) -------
+ * The dense launches of a decode step whose results must not depend on how many rows ride along.  For 1 <= M <= 64 every output element is
+ * computed by ONE fixed sequence of operations that is a function of (N, K) alone -- launch form, partition of K, reduction order: row i of
+ * an M-row call is bit for bit the M = 1 call on row i, whatever the other rows hold (NaN included).  fp32 accumulate, one rounding.
+ *   evo_linear_rowinv_bf16:   y [M, N] = x [M, K] . w [N, K]^T (+ bias [N]) (+ residual [M, N], may alias y).  K % 256 == 0, N % 64 == 0.
+ *       N >= 8192: one launch, a wave per 16-row n tile sums the whole K in k order; `ws` is not read.
+ *       N <  8192: K is cut into s = min(8, K / 256, ceil(256 / g)) slices of whole 256-k units (g = N / 64 workgroup columns; N / 32 below
+ *       N = 2048); the slices' fp32 partial sums go through `ws` (16-byte aligned, ws_bytes >= s M N 4; 8 M N 4 always suffices) and a
+ *       second launch adds them in slice order, then bias, then residual.
+ *   evo_mlp_gate_rowinv_bf16: a [M, I] = gelu(bf16(x . W1^T)) * bf16(x . W2^T), w12 = [W1; W2] ([2 I, K]; `grouped` != 0: in
+ *       pack_gate_weights' row order), as evo_mlp_gate_small_m_bf16 computes it at 5-64 rows.  K % 256 == 0, I % 32 == 0.
+ * Both return -1 for a shape outside the contract (and the linear entry for a missing or short workspace): there is no second form. */
+int evo_linear_rowinv_bf16(const void* x, const void* w, const void* bias, const void* residual, void* y, int64_t M, int64_t N,
+                           int64_t K, void* ws, int64_t ws_bytes, void* stream);
+int evo_mlp_gate_rowinv_bf16(const void* x, const void* w12, void* a, int64_t M, int64_t I, int64_t K, int64_t grouped, void* stream);
 
 /* ---- box-calibration probes (measurement infrastructure; no reference counterpart) -----------------------------------
  * Two FIXED kernels whose rates depend on the box (HBM, the clocks its power cap allows) and on nothing else in this library:

@@ -85,6 +85,9 @@ def main(argv=None):
     ap.add_argument("--kv-page-tokens", type=int, default=256, metavar="N", help="tokens per page with --kv-paged (a power of two >= 64)")
     ap.add_argument("--kv-budget-tokens", type=int, default=None, metavar="N", help="with --kv-paged: cap the page pool at N tokens; jobs "
                                                                                     "then wait for free pages, in order")
+    ap.add_argument("--batch-invariant", action="store_true", help="with --seed: every generation is the same bits at any --n-slots from 1 to 64 "
+                                                                   "(one launch sequence at every slot count; not with --prefill-batch > 1, "
+                                                                   "--share-prompt-kv, --kv-dtype fp8 or --weight-dtype fp8)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -96,6 +99,10 @@ def main(argv=None):
         ap.error("--kv-page-tokens must be a power of two >= 64")
     if args.weight_dtype != "bf16" and args.n_slots > 8:
         ap.error("--weight-dtype fp8 serves pools of up to 8 slots")
+    if args.batch_invariant and (args.n_slots > 64 or args.prefill_batch > 1 or args.share_prompt_kv or args.kv_dtype != "bf16"
+                                 or args.weight_dtype != "bf16"):
+        ap.error("--batch-invariant serves pools of up to 64 slots and does not combine with --prefill-batch > 1, --share-prompt-kv, "
+                 "--kv-dtype fp8 or --weight-dtype fp8")
     if args.kv_dtype != "bf16" and args.share_prompt_kv:
         ap.error("--kv-dtype fp8 does not combine with --share-prompt-kv (the prompt store is bf16)")
     if sum(x is not None for x in (args.template, args.encode_protein, args.orf_min_codons)) > 1:
@@ -115,7 +122,8 @@ def main(argv=None):
                       **({} if args.kv_dtype == "bf16" else {"kv_dtype": args.kv_dtype}),
                       **({"kv_paged": True, "kv_page_tokens": args.kv_page_tokens, "kv_budget_tokens": args.kv_budget_tokens}
                          if args.kv_paged else {}),
-                      **({} if args.weight_dtype == "bf16" else {"weight_dtype": args.weight_dtype}))
+                      **({} if args.weight_dtype == "bf16" else {"weight_dtype": args.weight_dtype}),
+                      **({"batch_invariant": True} if args.batch_invariant else {}))
     ctl = {}                                                  # any of these moves the job onto the job-control path
     if args.stop_tokens:
         ctl["stop_tokens"] = args.stop_tokens
