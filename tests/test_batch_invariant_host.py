@@ -1,7 +1,9 @@
 """CPU: the host side of the decode pool's opt-in batch-invariant step on the oracle backend -- what is refused and
 when, where the flag travels, that the pool with the option still generates what per-prompt greedy `generate` does, and that a pool
 WITHOUT the option asks its backend for exactly what it asked before.  The kernels' own statements (row invariance, exactness) need the
-GPU: tests/test_gpu_rowinv.py, tests/test_gpu_batch_invariant.py."""
+GPU: tests/test_gpu_rowinv.py, tests/test_gpu_rowinv_rows.py, tests/test_gpu_step_rows.py, tests/test_gpu_batch_invariant.py.  Their CPU
+companion is at the end of this module: the routing of the row-invariant launches restated in plain Python (tests/rowinv_ref.py), held
+to the source, to the figures DESIGN.md section 25 quotes and to the shapes those GPU modules run."""
 import os
 import re
 
@@ -192,3 +194,80 @@ def test_rowinv_kernels_need_no_scratch():
     for name, r in kernels.items():
         assert r["spill"] == 0 and r["scratch"] == 0 and r["sgpr_spill"] == 0, (name, r)
         assert r["lds"] <= 160 * 1024 and r["vgpr"] <= 256, (name, r)                   # (a CU holds 160 KiB of LDS)
+
+
+# ================================================================================================ the routing, restated (tests/rowinv_ref.py)
+import rowinv_ref as RI  # noqa: E402
+
+
+def _rowinv_source():
+    src = open(os.path.join(ROOT, "evo_amd", "csrc", "gemv_inv.hip")).read() + open(os.path.join(ROOT, "evo_amd", "csrc", "skinny_nw.h")).read()
+    return re.sub(r"\s+", " ", src)
+
+
+def test_the_restatement_reads_like_the_source():
+    """The constants the restatement is built from, where the source states them (a change of the rule has to touch both)."""
+    src = _rowinv_source()
+    for needle in ("if (N >= 8192) {", "const int64_t groups = N / (N < 2048 ? 32 : 64);", "int64_t slices = (256 + groups - 1) / groups;",
+                   "if (slices > K / 256) slices = K / 256;", "return slices > 8 ? 8 : slices;",
+                   "if (N >= 256 * 64) launch(mt, gv_int<4>{}); else if (N >= 256 * 48) launch(mt, gv_int<3>{}); else launch(mt, gv_int<2>{});",
+                   "if (N < 2048) launch(mt, gv_int<2>{}); else launch(mt, gv_int<4>{});", "constexpr int KC = MT <= 2 ? 8 : 4;",
+                   "constexpr int CPU = 8 / KC;", "const int n_cut = SLICE256 ? n_chunk_all / CPU : n_chunk_all, cut = SLICE256 ? CPU : 1;",
+                   "(int)((int64_t)n_cut * blockIdx.y / gridDim.y) * cut",
+                   "skinny_nw_kernel<decltype(mt)::value, WV, true, false, true>",
+                   "if (M <= 16) f(gv_int<1>{}); else if (M <= 32) f(gv_int<2>{}); else if (M <= 48) f(gv_int<3>{}); else f(gv_int<4>{});"):
+        assert needle in src, needle
+    assert [RI.mt_of(M) for M in (1, 16, 17, 32, 33, 48, 49, 64)] == [1, 1, 2, 2, 3, 3, 4, 4] and [RI.kc_of(t) for t in (1, 2, 3, 4)] == [8, 8, 4, 4]
+
+
+def test_slices_do_not_move_with_the_chunk_length_under_the_256_k_cut():
+    """Every K that is a multiple of 256 up to 11,008 and every slice count 1 .. min(8, K / 256): cut in 256-k units the boundaries are the
+    same at both chunk lengths; cut in chunks (the default SPLITK) they differ for 202 pairs, (11008, 4) among them -- 2,560 against
+    2,688, the figure DESIGN.md section 25 quotes."""
+    cuts = RI.all_cuts()
+    assert len(cuts) == 316 and cuts[0] == (256, 1) and cuts[-1] == (11008, 8)
+    for K, s in cuts:
+        for unit256 in (True, False):
+            for kc in (8, 4):
+                b = RI.boundaries(K, s, kc, unit256)
+                assert b[0] == 0 and b[-1] == K and b == sorted(b) and all(v % (32 * kc) == 0 for v in b), (K, s, kc, unit256, b)
+        assert all(v % 256 == 0 for v in RI.boundaries(K, s, 4, True))
+    assert [c for c in cuts if RI.boundaries(*c, 8, True) != RI.boundaries(*c, 4, True)] == []
+    differ = [c for c in cuts if RI.boundaries(*c, 8, False) != RI.boundaries(*c, 4, False)]
+    assert len(differ) == 202 and (11008, 4) in differ
+    assert RI.boundaries(11008, 4, 8, False)[1] == 2560 and RI.boundaries(11008, 4, 4, False)[1] == 2688
+    assert RI.boundaries(11008, 4, 8, True) == RI.boundaries(11008, 4, 4, True) == [0, 2560, 5376, 8192, 11008]
+    # what a build without the 256-k cut would show to tests/test_gpu_rowinv_rows.py (M >= 33 against the one-row call): the shapes
+    # whose boundaries move, and the two 7B shapes whose boundaries do not
+    moves = {(N, K): RI.boundaries(K, RI.rowinv_slices(N, K), 8, False) != RI.boundaries(K, RI.rowinv_slices(N, K), 4, False)
+             for N, K in RI.LINEAR_7B + RI.LINEAR_SMALL if N < RI.WIDE_N}
+    assert moves == {(4096, 4096): False, (4096, 11008): True, (512, 4096): False, (512, 2304): True, (4096, 2816): True}
+    src = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "k = 2,560 up to 32 rows and at 2,688 from 33" in src
+
+
+def test_routes_of_the_test_shapes():
+    assert (RI.route(12288, 4096), RI.rowinv_slices(12288, 4096)) == ("wide3", 0)
+    assert (RI.route(4096, 4096), RI.slice_units(4096, 4096)) == ("split4", [4, 4, 4, 4])
+    assert (RI.route(4096, 11008), RI.slice_units(4096, 11008)) == ("split4", [10, 11, 11, 11])
+    assert (RI.route(512, 4096), RI.slice_units(512, 4096)) == ("split2", [2] * 8)
+    assert (RI.route(512, 2304), RI.slice_units(512, 2304)) == ("split2", [1] * 7 + [2])
+    assert (RI.route(4096, 2816), RI.slice_units(4096, 2816)) == ("split4", [2, 3, 3, 3])
+    assert [RI.route(N, 256) for N in (8192, 12288, 16384)] == ["wide2", "wide3", "wide4"]
+    # the existing module's shapes (tests/test_gpu_rowinv.py SHAPES), for the record
+    assert [(RI.route(N, K), RI.rowinv_slices(N, K)) for N, K in ((8192, 256), (16384, 256), (2048, 512), (4096, 1792), (512, 512))] == \
+        [("wide2", 0), ("wide4", 0), ("split4", 2), ("split4", 4), ("split2", 2)]
+    assert RI.slice_units(4096, 1792) == [1, 2, 2, 2]
+    # the workspace the binding hands over (8 M N floats) always suffices
+    assert all(0 <= RI.rowinv_slices(N, K) <= 8 for N in range(64, 16448, 64) for K in (256, 2304, 4096, 11008))
+
+
+def test_every_route_meets_every_m_tile_count_in_the_gpu_modules():
+    """Every route (2 / 3 / 4 waves wide; 2 / 4 waves split over K; gate) x every MT (1 .. 4) is reached by some (shape, M) the every-M
+    tests of tests/test_gpu_rowinv_rows.py run -- the lists are the restatement's own, which that module imports."""
+    cases = [(N, K, M) for N, K in RI.LINEAR_7B + RI.LINEAR_SMALL for M in RI.EVERY_M]
+    got = RI.reached(cases, RI.EVERY_M)
+    assert got == {(r, t) for r in RI.ROUTES for t in (1, 2, 3, 4)}, sorted({(r, t) for r in RI.ROUTES for t in (1, 2, 3, 4)} - got)
+    assert {RI.route(N, K) for N, K in RI.LINEAR_7B} == {"wide3", "split4", "split2"}
+    mod = open(os.path.join(ROOT, "tests", "test_gpu_rowinv_rows.py")).read()
+    assert "SHAPES = RI.LINEAR_7B + RI.LINEAR_SMALL" in mod and "GATES = [RI.GATE_7B]" in mod and "for M in RI.EVERY_M" in mod
