@@ -29,6 +29,10 @@ would be NaN by IEEE.  Everything behind the tensors / a row's position is 0xFF 
 The reference is general: `expected(levels, v, mult)` takes the exponent LEVEL of every key and a multiplicity matrix (how often query
 i counts key j) and returns the fp64 mean of V over the visible keys of the highest level -- for the true causal multiplicities these
 are the closed forms above; with an edited matrix it says what a kernel with that defect would return (the host tests' wrong key sets).
+
+A fifth design, G (graded weights: every weight an exact power of two, so the WEIGHTING of keys is judged to the bit as well), with its
+own reference `expected_graded`, judge `judge_graded` and case lists stands at the end of this file; tests/test_attn_graded_host.py
+pins it on the CPU, tests/test_gpu_attn_graded.py uses it.
 """
 import math
 
@@ -280,11 +284,12 @@ def judge(got, ref, single, adjacent_rows=None):
 
 
 # ------------------------------------------------------------------------------------------------ the w64 bookkeeping in plain torch
-def emulate_w64(q, k, v, q_pos0, pre):
+def emulate_w64(q, k, v, q_pos0, pre, c=None, defect=None):
     """fp32 emulation of attn_fwd_w64_kernel's arithmetic for one (batch row, head): q [Tq, 128], k / v [Tk, 128] bf16 -> [Tq, 128] bf16.
     64-key tiles in order; a row's exponents are taken relative to a reference point: PRE -- 0 while the tile's largest exponent stays
     inside +-W_THRP (a first visible tile may also pull it down), the tile maximum beyond; plain -- the first visible tile's maximum,
-    moved when a tile exceeds it by more than W_THR.  P is rounded to bf16 for P.V, l sums the UNROUNDED fp32 weights."""
+    moved when a tile exceeds it by more than W_THR.  P is rounded to bf16 for P.V, l sums the UNROUNDED fp32 weights.
+    c: the plain form's scale_log2 (default C_LOG2; design G runs it at 1).  defect: a wrong arithmetic (tests/test_attn_graded_host.py)."""
     Tq, Tk = q.shape[0], k.shape[0]
     qf, kf, vf = q.float(), k.float(), v.float()
     lim = (q_pos0 + torch.arange(Tq)).clamp_max(Tk - 1)
@@ -292,7 +297,7 @@ def emulate_w64(q, k, v, q_pos0, pre):
     seen = torch.zeros(Tq, dtype=torch.bool)
     l = torch.zeros(Tq)
     o = torch.zeros(Tq, HD)
-    c = torch.tensor(C_LOG2, dtype=torch.float32)
+    c = torch.tensor(C_LOG2 if c is None else c, dtype=torch.float32)
     for k0 in range(0, int(lim.max()) + 1, 64):
         kt, vt = kf[k0:k0 + 64], vf[k0:k0 + 64]
         s = (qf.double() @ kt.double().T).float()                                    # exact: see scores_int
@@ -310,8 +315,24 @@ def emulate_w64(q, k, v, q_pos0, pre):
         e = e - dl[:, None]
         seen = seen | (got if pre else upd)
         p = torch.exp2(e)
-        l = l * alpha + p.sum(-1)
-        o = o * alpha[:, None] + p.to(BF).float() @ vt
+        pb = p.to(BF)
+        a_l = a_o = alpha
+        if defect is not None:
+            if defect in ("skip8", "skip12"):
+                p = torch.where(e < e.max(-1, keepdim=True).values - float(defect[4:]), torch.zeros_like(p), p)
+                pb = p.to(BF)
+            elif defect == "alpha_err":
+                a_l = a_o = alpha * (1 + 2.0 ** -10)
+            elif defect == "alpha_l_only":
+                a_o = torch.where(seen, torch.ones_like(alpha), alpha)
+            elif defect == "alpha_o_only":
+                a_l = torch.where(seen, torch.ones_like(alpha), alpha)
+            elif defect == "trunc_p":
+                pb = (p.view(torch.int32) & -65536).view(torch.float32).to(BF)
+            else:
+                raise ValueError(defect)
+        l = l * a_l + p.sum(-1)
+        o = o * a_o[:, None] + pb.float() @ vt
     inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
     return (o * inv[:, None]).to(BF)
 
@@ -409,3 +430,262 @@ def build_decode(design, positions, H, dims, n_splits, device="cpu", alt=False, 
     if design == "S":
         planted = [ts[1:] if b % 2 and len(ts) > 1 else ts for b, ts in enumerate(planted)]      # odd rows: the U mean in front of t_1
     return build_case(design, B, H, 1, 0, Tk, dims, device, planted=planted, alt=alt, mult=decode_mult(positions, Tk, device))
+
+
+# ================================================================================================ design G: graded weights
+# The designs above make every softmax weight 1 or 0; they pin WHICH keys a row sees and cannot see how keys are WEIGHTED (every
+# rescale factor is 0 or 1).  G makes every weight an exact power of two instead: a score is an integer exponent in log2 units,
+#   k[j] = (e_j div 16, e_j mod 16) in two dims, q_i = (16 mu_i, mu_i): score = mu_i e_j, mu_i = G_MUS[i mod 3] (neighbouring rows rank
+#   the keys differently), e_j = base_j - g_j with g_j a hash of the key in 0 .. win and base_j piecewise constant (0: FLAT; a list of
+#   levels between fixed cuts: STAIR),
+# and V = V_hist: output dim d is its own accumulator of s_bh sum 2^(mu e_j) over the keys j = d mod 128.  One data set serves PRE (the
+# score IS the exponent) and the plain form at softmax_scale = G_LN2, where the entries' own scale_log2 = softmax_scale * log2(e) is
+# 1.0f exactly (tests/test_attn_graded_host.py pins that).
+# Exactness (graded_check): ceil(log2(n_keys + 1)) + max|mu| win <= 24.  Then for a flat row every weight 2^n, its bf16 rounding, every
+# partial sum of l and of any output dim is exact in fp32 in any order under any common power-of-two reference; only 1 / l and the last
+# multiply round (< 1.5 * 2^-24: inside the judge's 2^-21 boundary rule).
+# Stair rows mix levels.  Two levels of one list that can meet inside one 64-key tile differ by <= 3 (exact as above: win = 4, <= 640
+# keys: 10 + 2 (4 + 3) = 24 bits) or by >= 30 (the lower level's whole tile weighs < 2^-24 of one upper key); across tiles any
+# difference costs one fp32 rounding per accumulation.  Hence the allowance of a stair row (graded_allow): (64-key blocks visited +
+# non-empty splits + 2) * 2^-24 relative, on the boundary rule, nothing tensor-wide.
+# A row's exponents span at most G_SPAN = 100 log2 units (v_exp_f32 flushes below 2^-126; outputs stay normal bf16 numbers), which mu = 2
+# allows only for the narrow list N: the wide lists carry mu in (1, -1, 1).
+G_MUS = (1, -1, 2)
+G_LN2 = 0.6931471824645996                  # an fp32 number; fl32(G_LN2 * 1.4426950408889634f) == 1.0f
+G_SPAN = 100
+G_SEED = 206                                # of the hash g: one under which no case of the lists has a short row whose common mantissa sits
+                                            # on a rounding boundary (a condition on the inputs: test_allowance_zone_share_is_under_the_cap)
+G_CUTS = (64, 128, 168, 256, 300, 384, 512, 555)        # tile seams 64 / 128 / 256 (= 64 * 4 splits) / 384 / 512 (= 64 * 8) and mid-tile 168 / 300 / 555
+G_MID = (2, 4, 7)                                        # the cuts (by number) that lie inside a tile
+# levels between the cuts and the rows' mu.  N: +31 / +32 / +33 around W_THR for mu = +-1 and 62 / 64 / 66 around W_THRP for mu = 2.
+# W1: +63 / +64 / +65 around W_THRP, drops of 40 and 70, a rise of 65 from below.  W2: a first visible tile at -65 (PRE pulls its
+# reference down), then +32 / +33 / +64 / +65 relative to it; for mu = -1 every list is its mirror image (a first tile at +65, ...).
+G_STAIRS = {
+    "N": ((0, 31, 32, 33, 1, 33, 0, 32, 33), (1, -1, 2)),
+    "W1": ((0, 63, 64, 65, 25, -5, 60, -10, -9), (1, -1, 1)),
+    "W2": ((-65, -33, -32, -1, 0, -40, 25, -45, -44), (1, -1, 1)),
+}
+G_WIN_STAIR = 4                             # stair rows (<= 641 keys)
+
+
+def graded_win(n_keys):
+    """Flat rows: the widest window the exactness condition allows -- 7 up to 1,023 keys (2^-14 for mu = 2: a kernel that skipped weights
+    12 or more log2 units down would show), 6 up to 2,049, 5 up to 8,229."""
+    return 7 if n_keys <= 1023 else (6 if n_keys <= 2049 else 5)
+G_STAIR_MAX_KEYS = 641                      # 11 blocks at most: the prefix case P 320 + Tq 321; the allowance stays <= 2^-20 for prefill
+
+
+def graded_check(n_keys, win, mus, stair=None, cuts=G_CUTS):
+    """The builder's conditions (see above); raises AssertionError."""
+    amax = max(abs(m) for m in mus)
+    near = 0
+    if stair is not None:
+        lv = G_STAIRS[stair][0]
+        assert n_keys <= G_STAIR_MAX_KEYS and len(lv) == len(cuts) + 1
+        assert amax * (max(lv) - min(lv) + win) <= G_SPAN, "a row's exponents leave the span"
+        for n in range(len(cuts)):
+            d = abs(lv[n + 1] - lv[n])
+            if cuts[n] % 64:
+                assert d <= 3 or d >= 30, f"levels {lv[n]} | {lv[n + 1]} meet inside a tile"
+                near = max(near, d if d <= 3 else 0)
+    else:
+        assert amax * win <= G_SPAN
+    assert math.ceil(math.log2(n_keys + 1)) + amax * (win + near) <= 24, "the integer sums do not fit 24 bits"
+
+
+def graded_exponents(B, Tk, win, stair=None, cuts=G_CUTS, device="cpu"):
+    """e [B, Tk] int64: base - g.  g: a hash of (batch row, key) in 0 .. win, 0 at key 0 and on both sides of every cut (so a level is
+    reached where it begins and ends)."""
+    j = torch.arange(Tk, dtype=torch.int64, device=device)
+    b = torch.arange(B, dtype=torch.int64, device=device)[:, None]
+    g = mix31(b * (1 << 20) + j[None, :], G_SEED) % (win + 1)
+    base = torch.zeros(Tk, dtype=torch.int64, device=device)
+    g[:, 0] = 0
+    if stair is not None:
+        lv = torch.tensor(G_STAIRS[stair][0], dtype=torch.int64, device=device)
+        base = lv[torch.bucketize(j, torch.tensor(cuts, dtype=torch.int64, device=device), right=True)]
+        for t in cuts:
+            if t < Tk:
+                g[:, t - 1:t + 1] = 0
+    return base[None, :] - g
+
+
+def build_graded(B, H, nq, q_pos0, Tk, dims, win, stair=None, device="cpu", mult=None, cuts=G_CUTS, shared_prefix=0, row_mu=False):
+    """One G case: q [B, nq, H, 128], k, v [B, Tk, H, 128] bf16, e [B, Tk] int64, mu [B, nq] int64, mult [B, nq, Tk] (causal from q_pos0
+    unless given).  row_mu: mu goes by BATCH ROW (decode: one query per row), else by query.  shared_prefix = P: keys 0 .. P - 1 are
+    batch row 0's in every row."""
+    mus = G_MUS if stair is None else G_STAIRS[stair][1]
+    graded_check(Tk, win, mus, stair, cuts)
+    e = graded_exponents(B, Tk, win, stair, cuts, device)
+    if shared_prefix:
+        e[:, :shared_prefix] = e[:1, :shared_prefix]
+    sel = torch.arange(B, device=device)[:, None].expand(B, nq) if row_mu else torch.arange(nq, device=device)[None, :].expand(B, nq)
+    mu = torch.tensor(mus, dtype=torch.int64, device=device)[sel % 3]
+    q = torch.zeros(B, nq, H, HD, dtype=torch.float64, device=device)
+    k = torch.zeros(B, Tk, H, HD, dtype=torch.float64, device=device)
+    d0, d1 = dims[0], dims[1]
+    k[..., d0] = torch.div(e, 16, rounding_mode="floor").double()[:, :, None]
+    k[..., d1] = (e % 16).double()[:, :, None]
+    q[..., d0] = 16.0 * mu.double()[:, :, None]
+    q[..., d1] = mu.double()[:, :, None]
+    if mult is None:
+        mult = causal_mult(B, nq, Tk, q_pos0, device)
+    return {"q": q.to(BF), "k": k.to(BF), "v": v_hist(B, Tk, H, device), "e": e, "mu": mu, "mult": mult, "dims": (d0, d1), "win": win,
+            "stair": stair}
+
+
+def expected_graded(e, mu, v, mult):
+    """e [B, Tk] int64, mu [B, nq] int64, v [B, Tk, H, 128] bf16, mult [B, nq, Tk] int64 -> ref [B, nq, H, 128] fp64: the softmax of the
+    integer exponents mu_i e_j over the keys with mult > 0, each counted mult times (as in expected(): an edited matrix or an edited mu
+    describes a defect).  Weights are exact powers of two (ldexp); the fp64 sums carry 2^-53 relative."""
+    B, nq, Tk = mult.shape
+    H = v.shape[2]
+    ref = torch.zeros(B, nq, H, HD, dtype=torch.float64, device=v.device)
+    one = torch.ones((), dtype=torch.float64, device=v.device)
+    for b in range(B):
+        ex = mu[b][:, None] * e[b][None, :]
+        vis = mult[b] > 0
+        top = torch.where(vis, ex, torch.full_like(ex, -(1 << 40))).max(-1, keepdim=True).values
+        w = torch.where(vis, torch.ldexp(one, (ex - top).clamp_min(-1000).to(torch.int32)), torch.zeros_like(one)) * mult[b].double()
+        ref[b] = ((w @ v[b].double().reshape(Tk, H * HD)) / w.sum(-1, keepdim=True).clamp_min(2.0 ** -1000)).reshape(nq, H, HD)
+    return ref
+
+
+def graded_allow(mult, stair, n_splits=0):
+    """[B, nq] fp64: the relative half-width of the boundary rule per row.  Flat: ALLOW_REL (two roundings, < 1.5 * 2^-24, sit inside).
+    Stair: (64-key blocks visited + non-empty splits + 2) * 2^-24, at most 2^-24 * 22 with <= 640 keys."""
+    if stair is None:
+        return torch.full(mult.shape[:2], ALLOW_REL, dtype=torch.float64, device=mult.device)
+    j = torch.arange(mult.shape[2], device=mult.device)
+    last = torch.where(mult > 0, j, torch.zeros_like(j)).max(-1).values
+    blocks = last // 64 + 1
+    return (blocks + torch.minimum(blocks, torch.full_like(blocks, n_splits)) + 2).double() * 2.0 ** -24
+
+
+def judge_graded(got, ref, allow):
+    """got [B, nq, H, 128] bf16 against expected_graded()'s ref: got == bf16(ref); the adjacent pattern on ref's side only where ref lies
+    within allow |ref| of the rounding boundary, and (Verdict.ok) for at most 0.1 % of the case's elements.  Every element is judged."""
+    e, nb, dist = bf16_neighbourhood(ref)
+    gd = got.double()
+    eq = gd == e
+    allowed = (~eq) & (gd == nb) & (dist <= allow[:, :, None, None] * ref.abs())
+    ok = eq | allowed
+    return Verdict((~ok).any(-1).any(-1), int((~ok).sum()), int(allowed.sum()), 0, got.numel())
+
+
+def zone_share(ref, allow):
+    """The share of a case's elements whose ref lies inside its allowance zone (a condition on the INPUTS)."""
+    _, _, dist = bf16_neighbourhood(ref)
+    return float(((dist <= allow[:, :, None, None] * ref.abs()) & (ref != 0)).sum()) / ref.numel()
+
+
+def old_pin_count(got, ref):
+    """Elements the tolerance tests' pin |err| <= 2^-8 |ref| + 2e-2 would flag."""
+    return int(((got.double() - ref).abs() > 2.0 ** -8 * ref.abs() + 2e-2).sum())
+
+
+def stream_partials_expected(c, positions, n_splits):
+    """FLAT decode cases: the exact per-split partials of attn_decode_stream_kernel -- split s takes blocks s, s + n_splits, ...; m is
+    the split's largest exponent, l = sum 2^(ex - m), part_o[d] = sum 2^(ex - m) v[d] (UNNORMALISED, relative to the split's own m); an
+    empty split holds (-inf, 0, 0).  Every number is exact in fp32.  -> part_o [B, H, n_splits, 128], part_ml [B, H, n_splits, 2] fp32"""
+    B, H = len(positions), c["v"].shape[2]
+    po = torch.zeros(B, H, n_splits, HD, dtype=torch.float64)
+    pml = torch.zeros(B, H, n_splits, 2, dtype=torch.float64)
+    pml[..., 0] = float("-inf")
+    one = torch.ones((), dtype=torch.float64)
+    for b, p in enumerate(positions):
+        ex = (int(c["mu"][b, 0]) * c["e"][b, :p + 1]).cpu()
+        blk = torch.arange(p + 1) // 64
+        vb = c["v"][b, :p + 1].double().cpu()
+        for s in range(min(n_splits, int(blk.max()) + 1)):
+            mine = blk % n_splits == s
+            m = ex[mine].max()
+            w = torch.ldexp(one, (ex[mine] - m).to(torch.int32))
+            pml[b, :, s, 0], pml[b, :, s, 1] = float(m), w.sum()
+            po[b, :, s] = torch.einsum("j,jhd->hd", w, vb[mine])
+    return po.float(), pml.float()
+
+
+# ------------------------------------------------------------------------------------------------ the stream kernel + combine in plain torch
+def combine_tail_splits(n_splits):
+    """The splits that attn_decode_combine_kernel's TAIL loop handles (group g = s mod 4 walks s = g, g + 4, ...; eight per trip while
+    s + 28 < n_splits)."""
+    out = []
+    for g in range(4):
+        s = g
+        while s + 28 < n_splits:
+            s += 32
+        out += list(range(s, n_splits, 4))
+    return sorted(out)
+
+
+def emulate_stream(q, k, v, n_splits, c=1.0, defect=None):
+    """fp32 emulation of attn_decode_stream_kernel + attn_decode_combine_kernel for one (batch row, head): q [128], k / v [n_keys, 128]
+    bf16 -> (o [128] bf16, part_o [n_splits, 128], part_ml [n_splits, 2]).  32-key halves, a running maximum per split, alpha = 2^(m_old
+    - m_new); the combine weights split s by 2^(m_s - M).  defect: a wrong arithmetic (tests/test_attn_graded_host.py)."""
+    n = k.shape[0]
+    sc_all = (k.double() @ q.double()).float() * torch.tensor(c, dtype=torch.float32)
+    vf = v.float()
+    nblk = (n + 63) // 64
+    part_o = torch.zeros(n_splits, HD)
+    part_ml = torch.zeros(n_splits, 2)
+    ninf = torch.tensor(float("-inf"))
+    for s in range(n_splits):
+        m, l, o = ninf, torch.zeros(()), torch.zeros(HD)
+        for blk in range(s, nblk, n_splits):
+            for k0 in (64 * blk, 64 * blk + 32):
+                if k0 >= n:
+                    continue
+                sc = sc_all[k0:k0 + 32]
+                m_new = torch.maximum(m, sc.max())
+                alpha = torch.exp2(m - m_new)
+                a_l = a_o = alpha * (1 + 2.0 ** -10) if defect == "alpha_err" else alpha
+                if defect == "alpha_l_only":
+                    a_o = torch.ones(())
+                if defect == "alpha_o_only":
+                    a_l = torch.ones(())
+                pw = torch.exp2(sc - m_new)
+                if defect in ("skip8", "skip12"):
+                    pw = torch.where(sc < sc.max() - float(defect[4:]), torch.zeros_like(pw), pw)
+                l = l * a_l + pw.sum()
+                o = o * a_o + pw @ vf[k0:k0 + 32]
+                m = m_new
+        part_o[s], part_ml[s, 0], part_ml[s, 1] = o, m, l
+    ms = part_ml[:, 0]
+    M = ms.max()
+    mw = torch.roll(ms, -1) if defect == "combine_m_next" else ms
+    w = torch.where(ms == float("-inf"), torch.zeros_like(ms), torch.exp2(torch.where(mw == float("-inf"), M, mw) - M))
+    if defect == "tail_unweighted":
+        w[combine_tail_splits(n_splits)] = 1.0
+    L = (part_ml[:, 1] * w).sum()
+    acc = (part_o * w[:, None]).sum(0)
+    return (acc / L if L > 0 else torch.zeros(HD)).to(BF), part_o, part_ml
+
+
+# ------------------------------------------------------------------------------------------------ G cases (shared by the CPU and the GPU module)
+G_VARIANTS = (None, "N", "W1", "W2")                                     # flat + the three stair lists
+G_W64 = [(W64_SHAPES[n], 3, 2) for n in (0, 3, 4, 6, 8)] + [(W64_SHAPES[0], 1, 8), (W64_SHAPES[6], 1, 8)]
+G_PIPE = PIPE_SHAPES[:3]
+G_QB128 = [(1, 199, 0), (37, 163, 0), (64, 136, 0), (128, 72, 0), (128, 63, 0)]      # Tk 200 (the last: 191)
+G_QB128_LONG = (128, 1921, 0)                                            # Tk 2,049: flat only
+G_PREFIX = [(P, Tq) for P in (64, 320) for Tq in (129, 321)]
+G_DECODE_STAIR = [p for p in DECODE_POSITIONS if p <= 639] + [299, 555, 639]         # + three rows that reach the later levels
+G_DECODE_SPLITS = [1, 4, 8, 40, None]
+
+
+def graded_cuts(P=0):
+    """The prefix cases put a cut on the P - 1 | P seam: 64 is one; for 320 the cut at 300 moves there (still a rise or drop >= 30)."""
+    return tuple(P if (t == 300 and P == 320) else t for t in G_CUTS)
+
+
+def graded_prefill(shape, B, H, dims, stair, device="cpu", P=0):
+    Tq, q_pos0, dTk = shape
+    Tk = q_pos0 + Tq + dTk
+    win = G_WIN_STAIR if stair else graded_win(Tk)
+    return build_graded(B, H, Tq, q_pos0, Tk, dims, win, stair, device, cuts=graded_cuts(P), shared_prefix=P)
+
+
+def graded_decode(positions, H, dims, stair, device="cpu"):
+    Tk = max(positions) + 1
+    win = G_WIN_STAIR if stair else graded_win(Tk)
+    return build_graded(len(positions), H, 1, 0, Tk, dims, win, stair, device, mult=decode_mult(positions, Tk, device), row_mu=True)
