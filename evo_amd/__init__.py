@@ -18,6 +18,7 @@ from .scoring import score_variants, single_substitutions, plan_variants, Varian
 from .embeddings import embed_sequences
 from .pool import beam_search, BeamResult
 from .constraints import TokenConstraint, iupac_template, encode_protein, open_reading_frame, concat
+from .sh.sample import RepeatControl
 
 SHIM_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "shim")
 

@@ -33,6 +33,7 @@ EXPORTS = [
     "evo_rope_append_decode_paged_bf16", "evo_attn_decode_paged_bf16",
     "evo_beam_select_f32", "evo_gather_rows",
     "evo_linear_rowinv_bf16", "evo_mlp_gate_rowinv_bf16",
+    "evo_repeat_rows_f32",
 ]
 
 

@@ -53,6 +53,8 @@ class Backend:
         "row_invariant": ("linear_rowinv", "linear_residual_rowinv_", "mlp_gate_rowinv"),
         # beam search (DecodePool.beam_search): the step's selection, and the copy that moves a slot's records to the slot that continues it
         "beam": ("beam_select", "gather_rows"),
+        # k-mer repeat control (DecodePool.generate(repeat=...)): the launch in front of the job-control sampler launch
+        "repeat": ("repeat_rows",),
     }   # (single kernels go by their own name: rope_append_decode, unembed_profile, attention_prefix, attention_prefix_vt, attention_decode_prefix)
 
     def supports(self, *names: str) -> bool:

@@ -87,6 +87,7 @@ _SIGNATURES = {
     "evo_gather_rows": ([_PTR, _I64, _PTR, _PTR, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
     "evo_linear_rowinv_bf16": ([_PTR] * 5 + [_I64] * 3 + [_PTR, _I64, _PTR], _c.c_int),
     "evo_mlp_gate_rowinv_bf16": ([_PTR] * 3 + [_I64] * 4 + [_PTR], _c.c_int),
+    "evo_repeat_rows_f32": ([_PTR, _I64, _I64] + [_PTR] * 8 + [_I64] + [_PTR] * 4 + [_I64] * 5 + [_PTR], _c.c_int),
 }
 
 _LIB = None
@@ -1672,6 +1673,63 @@ class HipOps(Backend):
                 limit.data_ptr(), _ptr(stop_mask), seq_ptr, len_ptr, n_seq, int(stop_frame), length.data_ptr(), finish.data_ptr(), *extra,
                 S, V, _stream()), entry)
         return ids_out, logprob_out
+
+    # ---- k-mer repeat control: the optional group "repeat" (csrc/repeat.hip) ------------------------------------------
+    def repeat_rows(self, logits: torch.Tensor, out: torch.Tensor, active: torch.Tensor, counts: torch.Tensor, ctx: torch.Tensor,
+                    stat: torch.Tensor, levels: torch.Tensor, alphabet: torch.Tensor, k: int, fed_ids: Optional[torch.Tensor] = None,
+                    end_num: Optional[torch.Tensor] = None, end_min_tokens: int = 1, count: Optional[torch.Tensor] = None,
+                    length: Optional[torch.Tensor] = None, finish: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The launch in front of the job-control sampler launch (specification: sh/sample.py repeat_row): logits [S, 512] bf16 | f32 ->
+        `out` [S, 512] f32, the row the sampler draws from.  Per row with `active` [S] bool set: the token `fed_ids` [S] (or [S, 1]) int64
+        is folded into `counts` [S, M] int32, `ctx` [S, 2] int32 and `stat` [S, 2] int64 (None: nothing is folded); with `end_num` [S]
+        int32 the rule may end the job (active cleared, length[s] = count[s], finish[s] = 6, the row of `out` left alone); otherwise the
+        row is widened and levels[s][min(c, 7)] (`levels` [S, 8] f32) is subtracted on every symbol of `alphabet` (HOST int32, 1 ... 8
+        distinct ids), c the count of the k-mer it would complete.  M = len(alphabet) ** k.  One launch, nothing read back: capturable."""
+        me = "repeat_rows"
+        if logits.dtype not in (torch.bfloat16, torch.float32) or logits.dim() != 2 or not logits.is_cuda:
+            raise RuntimeError(f"{me}: logits must be a [S, 512] bf16 or f32 device matrix")
+        S, V = logits.shape
+        if logits.stride(1) != 1 or logits.stride(0) % 8 or logits.stride(0) < V or logits.data_ptr() % 16:
+            logits = logits.contiguous()
+        dev = logits.device
+        if not isinstance(alphabet, torch.Tensor) or alphabet.dtype != torch.int32 or alphabet.is_cuda or alphabet.dim() != 1 \
+                or not alphabet.is_contiguous() or not 1 <= alphabet.numel() <= 8:
+            raise RuntimeError(f"{me}: alphabet must be a host int32 vector of 1 to 8 token ids")
+        ids = alphabet.tolist()
+        if len(set(ids)) != len(ids) or any(not 0 <= t < 512 for t in ids):
+            raise RuntimeError(f"{me}: alphabet must hold distinct token ids in [0, 512)")
+        n_sym, k = len(ids), int(k)
+        if k < 1 or (n_sym > 1 and (k > 20 or n_sym ** k > 1 << 20)):
+            raise RuntimeError(f"{me}: k = {k} over {n_sym} symbols is outside 1 <= n_sym ** k <= 2^20")
+        M = n_sym ** k if n_sym > 1 else 1
+
+        def need(t, dtype, shape, what, required=False):
+            if t is None and not required:
+                return
+            if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f"{me}: {what} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        need(out, torch.float32, (S, V), "out", True)
+        if out.data_ptr() % 16:
+            raise RuntimeError(f"{me}: out must be 16-byte aligned")
+        need(active, torch.bool, (S,), "active", True)
+        need(counts, torch.int32, (S, M), "counts", True)
+        need(ctx, torch.int32, (S, 2), "ctx", True)
+        need(stat, torch.int64, (S, 2), "stat", True)
+        need(levels, torch.float32, (S, 8), "levels", True)
+        need(None if fed_ids is None else fed_ids.view(-1), torch.int64, (S,), "fed_ids")
+        need(end_num, torch.int32, (S,), "end_num")
+        armed = end_num is not None
+        need(count, torch.int64, (S,), "count", armed)
+        need(length, torch.int64, (S,), "length", armed)
+        need(finish, torch.uint8, (S,), "finish", armed)
+        if armed and int(end_min_tokens) < 1:
+            raise RuntimeError(f"{me}: end_min_tokens must be >= 1")
+        with self._t(me):
+            _check(self.lib.evo_repeat_rows_f32(logits.data_ptr(), int(logits.dtype == torch.float32), logits.stride(0), out.data_ptr(),
+                                                _ptr(fed_ids), active.data_ptr(), counts.data_ptr(), ctx.data_ptr(), stat.data_ptr(),
+                                                levels.data_ptr(), _ptr(end_num), int(end_min_tokens), _ptr(count), _ptr(length),
+                                                _ptr(finish), alphabet.data_ptr(), n_sym, k, M, S, V, _stream()), "evo_repeat_rows_f32")
+        return out
 
     # ---- beam search: the optional group "beam" (csrc/beam.hip; DESIGN.md section 24) ---------------------------------------------------------
     def beam_select(self, logits: torch.Tensor, cum: torch.Tensor, ended: torch.Tensor, length: torch.Tensor, ids: torch.Tensor,

@@ -68,6 +68,16 @@ row-invariant output projection, norm, row-invariant gate and l3, final norm, ro
 launches of 1-8 slots.  Refused (ValueError, each has row-count- or group-dependent arithmetic of its own): `n_slots` > 64,
 `prefill_batch` > 1, `share_prompt_kv`, `kv_dtype="fp8"`, `weight_dtype="fp8"`, and `beam_search` on such a pool.
 
+k-mer repeat control (opt-in): `generate(repeat=RepeatControl(...))` also takes the job-control path and puts ONE more
+launch, `evo_repeat_rows_f32`, in front of its sampler launch.  Every job keeps the counts of the k-mers of its prompt and of what it has
+generated; the launch folds the token the step is fed (`DecodePool.ids`: what the previous step drew) into them, subtracts a level from
+the logit of every nucleotide that would complete a k-mer seen before, and -- with `end_fraction` -- ends a job once more than that
+fraction of its tokens were such repeats (`last_finish` "repeat"; the job keeps all its tokens).  The sampler draws from the penalised
+row, so the recorded logits and `last_logprobs` of such a run are the penalised ones (`score_sequences` on the output gives the model's
+own).  `last_repeats` holds one (generated tokens folded, repeats among them) per job, read when the job is fetched: a job the sampler
+ended (limit, stop rule, constraint) has its last token not yet folded, a job the rule ended has all of them.  Row-local and outside the
+forward, it composes with everything the job-control path composes with.
+
 Beam search: `beam_search(prompts, n_tokens, beam_width)` on a pool built with `share_prompt_kv=True` returns the
 `beam_width` most likely continuations of every prompt.  A prompt owns a group of `beam_width` consecutive slots behind one store row; the
 captured step is forward, `beam_select` (the group's W x 512 candidates ranked on the device; parents, tokens and scores written where the
@@ -88,8 +98,8 @@ from .sh.cache import (Fp8KV, PagedKV, PromptStore, check_kv_dtype, check_page_t
                        check_weight_rows)
 from .sh.model import capture_graph
 from .constraints import TokenConstraint
-from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_ALL, FINISH_STOP_TOKEN, allowed_mask, sample,
-                        stop_patterns)
+from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINISH_NAMES_REPEAT, FINISH_REPEAT, FINISH_STOP_TOKEN, RepeatControl,
+                        allowed_mask, sample, stop_patterns)
 
 
 class DecodePool:
@@ -535,9 +545,60 @@ class DecodePool:
                hist_logprob=self.hist_logprob[rows], stop_mask=c["stop_mask"], stop_seq=c["stop_seq"],
                stop_frame=c["stop_frame"], **dfa)
 
+    # ------------------------------------------------------------------ k-mer repeat control (opt-in)
+    def _allocate_repeat(self, rc) -> None:
+        """Per-pool state of the repeat launch: counts [S, M] (4 M bytes per slot; 4 MiB at the cap M = 2^20), window, statistics, levels, the
+        armed fraction, and the f32 rows the sampler reads.  A new table size makes new state and drops the captured step."""
+        S, dev = self.n_slots, self.device
+        if getattr(self, "s_rep_counts", None) is not None and tuple(self.s_rep_counts.shape) == (S, rc.M):
+            return
+        self.s_rep_counts = torch.zeros(S, rc.M, dtype=torch.int32, device=dev)
+        self.s_rep_ctx = torch.zeros(S, 2, dtype=torch.int32, device=dev)
+        self.s_rep_stat = torch.zeros(S, 2, dtype=torch.int64, device=dev)
+        self.s_rep_levels = torch.zeros(S, 8, dtype=torch.float32, device=dev)
+        self.s_rep_end = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.s_rep_logits = torch.zeros(S, self.model.vocab_size, dtype=torch.float32, device=dev)
+        self._graph = None
+
+    def _repeat_init(self, ids: torch.Tensor, rc) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`repeat_init` (sh/sample.py) of one prompt with torch ops on the pool's device, outside the captured step: ids [P] -> (counts [M]
+        int32, (code, len) int32 [2]).  A k-mer counts when its k tokens are consecutive alphabet symbols; the window is the last
+        min(k - 1, trailing run of symbols) of them."""
+        dev, n, k = ids.device, rc.n_sym, rc.k
+        lut = torch.full((512,), -1, dtype=torch.int64, device=dev)
+        lut[torch.tensor(rc.ids, dtype=torch.int64, device=dev)] = torch.arange(n, dtype=torch.int64, device=dev)
+        ids = ids.reshape(-1).to(torch.int64)
+        inside = (ids >= 0) & (ids < 512)
+        sym = torch.where(inside, lut[ids.clamp(0, 511)], torch.full_like(ids, -1))
+        P = int(sym.numel())
+        counts = torch.zeros(rc.M, dtype=torch.int64, device=dev)
+        if rc.count_prompt and P >= k:
+            w = sym.unfold(0, k, 1)                                   # [P - k + 1, k], oldest symbol first
+            ok = (w >= 0).all(-1)
+            place = n ** torch.arange(k - 1, -1, -1, dtype=torch.int64, device=dev) if n > 1 else torch.zeros(k, dtype=torch.int64, device=dev)
+            counts = torch.bincount((w.clamp(min=0) * place).sum(-1)[ok], minlength=rc.M)
+        tail = sym[max(0, P - (k - 1)):].tolist() if k > 1 else []
+        code = ln = 0
+        for a in tail:                                                # at most k - 1 <= 19 symbols (n_sym = 1: the code stays 0)
+            code, ln = (0, 0) if a < 0 else (code * n + a, ln + 1)
+        return counts.clamp(max=2 ** 31 - 1).to(torch.int32), torch.tensor([code, ln], dtype=torch.int32, device=dev)
+
+    def _repeat_rows(self, logits: torch.Tensor, rows: slice, fed: bool) -> None:
+        """The repeat launch on the slots `rows`: model rows in, `s_rep_logits[rows]` out.  `fed`: fold `self.ids`, the token the step is fed."""
+        r = self._ctl["repeat"]
+        end = dict(end_num=self.s_rep_end[rows], end_min_tokens=r["end_min_tokens"], count=self.s_count[rows], length=self.s_length[rows],
+                   finish=self.s_finish[rows]) if r["armed"] else {}
+        self.model.ops.repeat_rows(logits, self.s_rep_logits[rows], self.s_active[rows], self.s_rep_counts[rows], self.s_rep_ctx[rows],
+                                   self.s_rep_stat[rows], self.s_rep_levels[rows], r["alphabet"], r["k"],
+                                   fed_ids=self.ids[rows] if fed else None, **end)
+
     def _step_sample_eager(self) -> None:
         if self._ctl is not None:
-            self._sample_rows_ctl(self._step_eager(), slice(0, self.n_slots))
+            logits = self._step_eager()
+            if self._ctl["repeat"] is not None:                      # self.ids still holds the token this step was fed
+                self._repeat_rows(logits, slice(0, self.n_slots), fed=True)
+                logits = self.s_rep_logits
+            self._sample_rows_ctl(logits, slice(0, self.n_slots))
         else:
             self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
         self._advance()
@@ -581,7 +642,7 @@ class DecodePool:
     def generate(self, prompts: Sequence[str], n_tokens=1000, n_sample_per_prompt: int = 1,
                  prepend_bos: bool = False, sampling: Optional[Sequence[Optional[dict]]] = None,
                  streams: Optional[Sequence[int]] = None, stop_tokens=None, stop_sequences=None, stop_frame: int = 1,
-                 return_logits: bool = True, constraints=None) \
+                 return_logits: bool = True, constraints=None, repeat: Optional[RepeatControl] = None) \
             -> Tuple[List[str], List[float], List[int]]:
         """Returns (generated strings, mean log-likelihood scores, index of the prompt each came from), in job
         order: prompt 0's samples first.  `sampling` (device sampler only): one dict of `top_k` / `top_p` / `temperature`
@@ -596,11 +657,18 @@ class DecodePool:
 
         Constrained generation (also on the job-control path): `constraints` is one `TokenConstraint` for every prompt, or
         a list with one (or None: that prompt is free) per prompt.  It governs the GENERATED tokens: every sample starts in state 0, the
-        prompt is not walked.  A job ends with the token that completes its constraint (`last_finish` "constraint", kept in its string)."""
+        prompt is not walked.  A job ends with the token that completes its constraint (`last_finish` "constraint", kept in its string).
+
+        k-mer repeat control (also on the job-control path): `repeat` is one `RepeatControl` for the call.  The sampler
+        then draws from rows with a level subtracted on every symbol that would complete a k-mer the job has seen (its prompt's included,
+        unless `count_prompt=False`); the recorded logits and `last_logprobs` are those penalised rows.  With `end_fraction` a job ends
+        (`last_finish` "repeat", all its tokens kept) once more than that fraction of its generated tokens were repeats.  `last_repeats`:
+        one (n_gen, rep) per job -- the generated tokens folded into its counts and the repeats among them; the last token of a job the
+        sampler ended is not folded, every token of a job the rule ended is."""
         if (not isinstance(n_tokens, (int, np.integer)) or stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1
-                or not return_logits or constraints is not None):
+                or not return_logits or constraints is not None or repeat is not None):
             return self._generate_ctl(prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                                      stop_frame, return_logits, constraints)
+                                      stop_frame, return_logits, constraints, repeat)
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
         if hasattr(m, "eval"):
             m.eval()
@@ -745,7 +813,7 @@ class DecodePool:
                 self._release_pages(ended)
 
         self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
-        for name in ("last_lengths", "last_finish", "last_logprobs"):    # (an earlier job-control run's: they would describe that run)
+        for name in ("last_lengths", "last_finish", "last_logprobs", "last_repeats"):    # (an earlier job-control run's: they would describe that run)
             self.__dict__.pop(name, None)
         seqs = list(tok.detokenize_batch(out_ids))
         lp = logits_to_logprobs(out_logits, out_ids).float().numpy()   # the reference's shifted pairing
@@ -805,7 +873,7 @@ class DecodePool:
         return {"alphabet": torch.tensor(distinct[0].alphabet, dtype=torch.int32), "next": self.s_dfa_next}, bases
 
     def _generate_ctl(self, prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                      stop_frame, return_logits, constraints=None):
+                      stop_frame, return_logits, constraints=None, repeat=None):
         """`generate` on the job-control path: the sampler launch (`evo_sample_rows_ctl_f32`) ends a row's job on the device.  The host
         knows the step by which a slot MUST have finished (its limit) and, with a stop rule, reads the [S] lengths every `poll_every`
         steps to learn which slots finished sooner; a finished slot's history rows [:length] are fetched, its store row released, the
@@ -843,6 +911,14 @@ class DecodePool:
         per_prompt, distinct = self._constraints_of(constraints, len(prompts)) if constraints is not None else (None, [])
         if distinct and not hasattr(m.ops, "sample_rows_dfa"):
             raise RuntimeError("constraints need a compute backend with sample_rows_dfa; this model's backend has none")
+        rc = None
+        if repeat is not None:                                       #  every refusal before any device work
+            if not isinstance(repeat, RepeatControl):
+                raise ValueError("repeat: one RepeatControl for the call")
+            rc = repeat.resolve(tok, self.allow_mask)
+            if not Backend.adopt(m.ops).supports("repeat"):
+                raise RuntimeError('repeat needs a compute backend with the "repeat" kernels (' + ", ".join(Backend.OPTIONAL["repeat"])
+                                   + "); this model's backend has none")
         encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
         if sampling is not None:
             sampling = list(sampling)
@@ -851,6 +927,7 @@ class DecodePool:
         if streams is not None and len(streams) != len(prompts) * n_spp:
             raise ValueError("streams: one id per output")
         has_stop = stop_set is not None or bool(patterns) or bool(distinct)      # (a job may end by completing its constraint: the host polls)
+        has_stop = has_stop or (rc is not None and rc.end_num > 0)   # (... or by the repeat rule)
         L = max(limits)
         was_device = self.device_sampler
         self.device_sampler = True                                   # (as with allowed_tokens alone: no seed means seed 0)
@@ -870,20 +947,31 @@ class DecodePool:
                 self.s_stop_mask.copy_(m.ops.pack_allow_mask(stop_set, dev))
             dfa, bases = self._upload_constraints(per_prompt, distinct) if distinct else (None, None)
             self._ctl = {"stop_mask": None if stop_set is None else self.s_stop_mask,
-                         "stop_seq": m.ops.pack_stop_sequences(patterns) if patterns else None, "stop_frame": int(stop_frame), "dfa": dfa}
+                         "stop_seq": m.ops.pack_stop_sequences(patterns) if patterns else None, "stop_frame": int(stop_frame), "dfa": dfa,
+                         "repeat": None}
+            if rc is not None:                                       # alphabet, k, end_min_tokens and "armed" travel by value: part of the key
+                self._allocate_repeat(rc)
+                self._ctl["repeat"] = {"alphabet": torch.tensor(rc.ids, dtype=torch.int32), "k": rc.k, "end_min_tokens": rc.end_min_tokens,
+                                       "armed": rc.end_num > 0}
             # (the alphabet travels by value; the table is read by address and its size is an argument)
             key = ("ctl", tuple(map(tuple, patterns)), int(stop_frame), stop_set is not None) \
-                + ((distinct[0].alphabet, dfa["next"].data_ptr(), int(dfa["next"].shape[0])) if distinct else ())
+                + ((distinct[0].alphabet, dfa["next"].data_ptr(), int(dfa["next"].shape[0])) if distinct else ()) \
+                + (("repeat", rc.k, rc.ids, rc.end_min_tokens, rc.end_num > 0) if rc is not None else ())
             if key != self._graph_key:
                 self._graph, self._graph_key = None, key
-            for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps") + (("constraint_ends",) if distinct else ()):
+            for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps") + (("constraint_ends",) if distinct else ()) \
+                    + (("repeat_ends",) if rc is not None else ()):
                 self.stats.setdefault(name, 0)
-            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, bases)
+            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, bases, rc)
         finally:
             self.device_sampler = was_device
 
-    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, dfa_bases=None):
+    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, dfa_bases=None, rc=None):
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+        rep_init: Dict[int, tuple] = {}                              # repeat control: a prompt's starting state, shared by its copies
+        if rc is not None:                                           # one RepeatControl per call: every slot's levels and fraction
+            self.s_rep_levels.copy_(rc.levels.to(dev)[None, :].expand(S, 8))
+            self.s_rep_end.fill_(rc.end_num)
         L = max(limits)
         jobs = deque((pi * n_spp + c, pi) for pi in range(len(prompts)) for c in range(n_spp))
         n_jobs = len(jobs)
@@ -891,6 +979,7 @@ class DecodePool:
         out_logprobs = torch.zeros(n_jobs, L, dtype=torch.float32)
         out_logits = torch.zeros(n_jobs, L, m.vocab_size, dtype=torch.float32) if return_logits else None
         out_len, out_fin = [0] * n_jobs, [0] * n_jobs
+        out_rep: List[Tuple[int, int]] = [(0, 0)] * n_jobs
         slot_job: List[Optional[int]] = [None] * S
         slot_n = [0] * S                                             # tokens the slot's job has if it is still running
         slot_limit = [0] * S
@@ -923,6 +1012,14 @@ class DecodePool:
                 self.s_dfa_base[slot] = dfa_bases[pi]
                 self.s_dfa_state[slot] = 0
             self.s_active[slot] = True
+            if rc is not None:                                       # the prompt's k-mers; nothing generated yet; the first row through the launch
+                if pi not in rep_init:
+                    rep_init.clear()
+                    rep_init[pi] = self._repeat_init(encoded[pi][0], rc)
+                self.s_rep_counts[slot], self.s_rep_ctx[slot] = rep_init[pi]
+                self.s_rep_stat[slot] = 0
+                self._repeat_rows(last_logits[None], slice(slot, slot + 1), fed=False)
+                last_logits = self.s_rep_logits[slot]
             self._sample_rows_ctl(last_logits[None], slice(slot, slot + 1))      # the first token; with limit 1 (or a stop) also the last
             self.pos[slot] = P
             slot_job[slot], slot_n[slot], slot_limit[slot] = j, 1, limits[pi]
@@ -943,13 +1040,16 @@ class DecodePool:
             n_max = max(lengths)
             ids_cpu, lp_cpu = self.hist_ids[idx, :n_max].cpu(), self.hist_logprob[idx, :n_max].cpu()
             lg_cpu = self.hist_logits[idx, :n_max].cpu() if return_logits else None
+            rep_cpu = self.s_rep_stat[idx].cpu().tolist() if rc is not None else None
             for r, s in enumerate(slots):
                 j, n = slot_job[s], int(lengths[r])
+                if rc is not None:
+                    out_rep[j] = (int(rep_cpu[r][0]), int(rep_cpu[r][1]))
                 out_ids[j, :n], out_logprobs[j, :n] = ids_cpu[r, :n], lp_cpu[r, :n]
                 if return_logits:
                     out_logits[j, :n] = lg_cpu[r, :n]
                 out_len[j], out_fin[j] = n, int(fins[r])
-                self.stats[{FINISH_LENGTH: "length_ends", FINISH_CONSTRAINT: "constraint_ends"}.get(fins[r], "stop_ends")] += 1
+                self.stats[{FINISH_LENGTH: "length_ends", FINISH_CONSTRAINT: "constraint_ends", FINISH_REPEAT: "repeat_ends"}.get(fins[r], "stop_ends")] += 1
                 self.stats["idle_slot_steps"] += slot_n[s] - n
                 self.stats["tokens"] -= slot_n[s] - n                # (steps a finished slot sat through generate nothing)
                 slot_job[s] = None
@@ -1005,7 +1105,10 @@ class DecodePool:
                 done += len(finished)
 
         self.last_ids, self.last_logits, self.last_logprobs = out_ids, out_logits, out_logprobs
-        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES_ALL[f] for f in out_fin]
+        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES_REPEAT[f] for f in out_fin]
+        self.__dict__.pop("last_repeats", None)
+        if rc is not None:
+            self.last_repeats = list(out_rep)
         seqs, scores = [], []
         for j in range(n_jobs):
             n = out_len[j] - (1 if out_fin[j] == FINISH_STOP_TOKEN else 0)      # a stop token is trimmed, a stop sequence stays
@@ -1271,7 +1374,8 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
                 device: Optional[str] = None, seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False,
                 prefill_batch: int = 1, stop_tokens=None, stop_sequences=None, stop_frame: int = 1, return_logits: bool = True,
                 poll_every: int = 8, constraints=None, kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_paged: bool = False,
-                kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None, batch_invariant: bool = False):
+                kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None, batch_invariant: bool = False,
+                repeat: Optional[RepeatControl] = None):
     """`semantic_design.run_model` / `sample_model` without the equal-length restriction: (prompts repeated per
     sample, generated sequences, scores).  `seed` makes the run reproducible (for a fixed `n_slots`), `allowed_tokens`
     (e.g. "ACGT") restricts what may be drawn; either moves the sampler onto the device.  `share_prompt_kv`: the
@@ -1283,7 +1387,9 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     (not with `share_prompt_kv`).  `kv_paged=True`: the KV cache is a pool of pages of `kv_page_tokens` tokens, a job
     holds what its own prompt and limit need, and `kv_budget_tokens` caps the pool (not with `share_prompt_kv` or
     `kv_dtype="fp8"`).  `batch_invariant=True`: with a `seed`, every job's result is the same bits at any `n_slots` from 1 to 64 (DESIGN.md
-    section 25; not with `prefill_batch` > 1, `share_prompt_kv`, `kv_dtype="fp8"` or `weight_dtype="fp8"`)."""
+    section 25; not with `prefill_batch` > 1, `share_prompt_kv`, `kv_dtype="fp8"` or `weight_dtype="fp8"`).  `repeat`: one
+    `RepeatControl` -- a penalty on nucleotides that would complete a k-mer the job has seen, and optionally an early end for jobs that
+    turned repetitive."""
     pool = DecodePool(model, tokenizer, n_slots=n_slots, top_k=top_k, top_p=top_p, temperature=temp, device=device, seed=seed,
                       allowed_tokens=allowed_tokens, share_prompt_kv=share_prompt_kv, prefill_batch=prefill_batch, poll_every=poll_every,
                       kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_paged=kv_paged, kv_page_tokens=kv_page_tokens,
@@ -1293,6 +1399,8 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
         ctl = dict(stop_tokens=stop_tokens, stop_sequences=stop_sequences, stop_frame=stop_frame, return_logits=return_logits)
     if constraints is not None:
         ctl["constraints"] = constraints
+    if repeat is not None:
+        ctl["repeat"] = repeat
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos, **ctl)
     return [prompts[i] for i in owner], seqs, scores

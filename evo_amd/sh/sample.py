@@ -359,3 +359,192 @@ def beam_select(logits: torch.Tensor, cum: torch.Tensor, ended: torch.Tensor, le
             new_end[s] = bool(old_end[b]) or bool(stop[v])
             new_len[s] = old_len[b] + (0 if bool(old_end[b]) else 1)
     return parent, new_ids, new_cum, new_end, new_len
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k-mer repeat control: the written specification of `evo_repeat_rows_f32` (csrc/repeat.hip).  The launch sits in
+# front of the sampler launch of the job-control path.  A job keeps, over an alphabet of n_sym (1 ... 8) distinct token ids and a context
+# length k >= 1 (M = n_sym ** k <= 2 ** 20): `counts` int32 [M], how often each k-mer has been seen; the window (code, len): the last
+# len <= k - 1 alphabet symbols in base n_sym, newest in the lowest digit; n_gen, the generated tokens folded in, and rep, how many of
+# them completed a k-mer that had been seen before.  Per step the token the step is fed is folded in, the rule may end the job
+# (FINISH_REPEAT), and otherwise the row the sampler draws from is the model's row minus levels[min(count, 7)] on every symbol, count
+# being that of the k-mer the symbol would complete.  Integers and ONE f32 subtraction per symbol: nothing to round differently.
+
+FINISH_REPEAT = 6
+FINISH_NAMES_REPEAT = {**FINISH_NAMES_ALL, FINISH_REPEAT: "repeat"}
+REPEAT_MAX_SYMBOLS = 8
+REPEAT_MAX_TABLE = 1 << 20
+REPEAT_LEVELS = 8
+REPEAT_END_SCALE = 1024
+_COUNT_MAX = 2 ** 31 - 1
+
+
+class RepeatState:
+    """One job's state: counts int32 [M], the window (code, len), (n_gen, rep); `ids` are the alphabet's token ids, `k` the context length."""
+
+    def __init__(self, ids, k: int, counts=None, code: int = 0, length: int = 0, n_gen: int = 0, rep: int = 0):
+        self.ids, self.k = tuple(int(t) for t in ids), int(k)
+        self.n_sym = len(self.ids)
+        self.M = repeat_table_size(self.n_sym, self.k)
+        self.counts = torch.zeros(self.M, dtype=torch.int32) if counts is None else torch.as_tensor(counts, dtype=torch.int32).cpu().clone()
+        self.code, self.len, self.n_gen, self.rep = int(code), int(length), int(n_gen), int(rep)
+
+    def clone(self):
+        return RepeatState(self.ids, self.k, self.counts, self.code, self.len, self.n_gen, self.rep)
+
+    def window(self):
+        """(code, len) as the rule reads them: a window outside its invariants (len outside [0, k - 1], code outside [0, n_sym ** (k - 1)))
+        reads as the empty one, so that no k-mer index ever leaves [0, M)."""
+        if not 0 <= self.len <= self.k - 1 or not 0 <= self.code < self.M // self.n_sym:
+            return 0, 0
+        return self.code, self.len
+
+
+def repeat_table_size(n_sym: int, k: int) -> int:
+    """M = n_sym ** k; a ValueError outside 1 <= n_sym <= 8, k >= 1, M <= 2 ** 20."""
+    n_sym, k = int(n_sym), int(k)
+    if not 1 <= n_sym <= REPEAT_MAX_SYMBOLS:
+        raise ValueError(f"repeat: the alphabet has 1 to {REPEAT_MAX_SYMBOLS} symbols, got {n_sym}")
+    if k < 1:
+        raise ValueError(f"repeat: k must be >= 1, got {k}")
+    if n_sym == 1:
+        return 1
+    if k > 20 or n_sym ** k > REPEAT_MAX_TABLE:
+        raise ValueError(f"repeat: n_sym ** k = {n_sym} ** {k} exceeds {REPEAT_MAX_TABLE} table cells")
+    return n_sym ** k
+
+
+def repeat_fold(state: RepeatState, token: int, generated: bool) -> RepeatState:
+    """Fold one token into `state` (in place; returned for convenience).  A token outside the alphabet empties the window; a symbol at
+    len == k - 1 completes the k-mer idx = code * n_sym + a: its count goes up by one (saturating at 2 ** 31 - 1), a GENERATED token that
+    completes a k-mer seen before counts as a repeat, and the window moves on; a symbol at len < k - 1 only extends the window.  Every
+    generated token, whatever it is, counts in n_gen."""
+    code, ln = state.window()
+    tok = int(token)
+    a = state.ids.index(tok) if tok in state.ids else None
+    if a is None:
+        code, ln = 0, 0
+    elif ln == state.k - 1:
+        idx = code * state.n_sym + a
+        old = int(state.counts[idx])
+        state.counts[idx] = min(old + 1, _COUNT_MAX)
+        if generated and old >= 1:
+            state.rep += 1
+        code = idx % (state.M // state.n_sym)
+    else:
+        code, ln = code * state.n_sym + a, ln + 1
+    if generated:
+        state.n_gen += 1
+    state.code, state.len = code, ln
+    return state
+
+
+def repeat_init(prompt_ids, control) -> RepeatState:
+    """The state a job starts from: every prompt token folded with generated=False (BOS, tag characters and anything else outside the
+    alphabet empty the window); with control.count_prompt False the counts are zeroed afterwards -- the window stays, so the first
+    generated token completes a k-mer with the prompt's tail.  `control`: anything with `ids`, `k`, `count_prompt` (a resolved
+    `RepeatControl`)."""
+    state = RepeatState(control.ids, control.k)
+    for t in prompt_ids:
+        repeat_fold(state, int(t), False)
+    if not control.count_prompt:
+        state.counts.zero_()
+    return state
+
+
+def repeat_penalise(row: torch.Tensor, state: RepeatState, levels) -> torch.Tensor:
+    """row f32 [512] -> a new f32 row.  With len == k - 1, for every symbol a: c = counts[code * n_sym + a] and row[id_a] = row[id_a] -
+    levels[min(c, 7)] (a negative c reads as 0) -- one f32 subtraction, nothing else; every other id is untouched.  With len < k - 1 the
+    row is unchanged.  `levels`: f32 [8], levels[0] == 0."""
+    if row.dtype != torch.float32:
+        raise ValueError("repeat_penalise: the row is f32 (a bf16 row is widened first, which is exact)")
+    out = row.detach().to("cpu").clone()
+    lv = torch.as_tensor(levels, dtype=torch.float32).reshape(REPEAT_LEVELS)
+    code, ln = state.window()
+    if ln == state.k - 1:
+        for a, t in enumerate(state.ids):
+            c = int(state.counts[code * state.n_sym + a])
+            out[t] = out[t] - lv[min(max(c, 0), REPEAT_LEVELS - 1)]
+    return out
+
+
+def repeat_ended(state: RepeatState, end_num: int, end_min_tokens: int) -> bool:
+    """The early end, in integers: armed (end_num > 0), at least end_min_tokens generated tokens folded, and more than end_num / 1024 of
+    them repeats."""
+    return int(end_num) > 0 and state.n_gen >= int(end_min_tokens) and state.rep * REPEAT_END_SCALE > int(end_num) * state.n_gen
+
+
+def repeat_row(row: torch.Tensor, state: RepeatState, levels, fed=None, end_num=None, end_min_tokens: int = 1):
+    """One ACTIVE row of one launch: fold `fed` (the token the step is fed; None: nothing, a job's first row), then the end rule (`end_num`
+    None: not armed), then the penalty -> the f32 row the sampler draws from, or None when the rule ended the job (the caller then clears
+    `active`, sets length = count and finish = FINISH_REPEAT)."""
+    if fed is not None:
+        repeat_fold(state, int(fed), True)
+    if end_num is not None and repeat_ended(state, end_num, end_min_tokens):
+        return None
+    return repeat_penalise(row.detach().to("cpu").float(), state, levels)
+
+
+class RepeatControl:
+    """What `DecodePool.generate(repeat=...)` takes.  `k`: the k-mer length.  `levels`: what is subtracted from a
+    symbol's logit when the k-mer it would complete has been seen 0, 1, ... 7 (or more) times -- by default penalty * min(j, max_count),
+    otherwise 1 to 8 values, the last one repeated; levels[0] must be 0.  `alphabet`: a string or token ids, 1 to 8 distinct single-byte
+    tokens (None: the pool's `allowed_tokens`, else "ACGT").  `count_prompt`: whether the prompt's own k-mers count.  `end_fraction`: a
+    job ends (finish "repeat") once more than this fraction of its generated tokens completed a k-mer seen before, after at least
+    `end_min_tokens` tokens; None: no early end.  The fraction is held as end_num / 1024."""
+
+    def __init__(self, k: int = 8, penalty: float = 1.0, max_count: int = 4, levels=None, alphabet=None, count_prompt: bool = True,
+                 end_fraction=None, end_min_tokens: int = 64):
+        self.k, self.penalty, self.max_count, self.levels, self.alphabet = k, penalty, max_count, levels, alphabet
+        self.count_prompt, self.end_fraction, self.end_min_tokens = count_prompt, end_fraction, end_min_tokens
+
+    def __repr__(self):
+        return (f"RepeatControl(k={self.k!r}, penalty={self.penalty!r}, max_count={self.max_count!r}, levels={self.levels!r}, "
+                f"alphabet={self.alphabet!r}, count_prompt={self.count_prompt!r}, end_fraction={self.end_fraction!r}, "
+                f"end_min_tokens={self.end_min_tokens!r})")
+
+    def resolve(self, tokenizer=None, allow_mask=None):
+        """Everything checked (ValueError) and turned into what the launch takes: `ids` (tuple), `k`, `M`, `levels` (f32 [8], host),
+        `end_num` (0: no early end), `end_min_tokens`, `count_prompt`.  `allow_mask`: the pool's bool [512] or None."""
+        import math
+        from types import SimpleNamespace
+        alphabet = self.alphabet
+        if alphabet is None:
+            alphabet = torch.nonzero(allow_mask).flatten().tolist() if allow_mask is not None else "ACGT"
+        if isinstance(alphabet, torch.Tensor):
+            alphabet = alphabet.tolist()
+        ids = [int(t) for t in tokenizer.tokenize(alphabet)] if isinstance(alphabet, str) and tokenizer is not None \
+            else [ord(c) for c in alphabet] if isinstance(alphabet, str) else [int(t) for t in alphabet]
+        if not 1 <= len(ids) <= REPEAT_MAX_SYMBOLS or len(set(ids)) != len(ids) or any(not 0 <= t < 256 for t in ids):
+            raise ValueError(f"repeat: the alphabet is 1 to {REPEAT_MAX_SYMBOLS} distinct single-byte tokens, got {alphabet!r}")
+        if allow_mask is not None and not all(bool(allow_mask[t]) for t in ids):
+            raise ValueError("repeat: an alphabet symbol outside allowed_tokens could never be drawn")
+        if isinstance(self.k, (bool, float, str)) or int(self.k) != self.k:
+            raise ValueError(f"repeat: k must be an integer >= 1, got {self.k!r}")
+        M = repeat_table_size(len(ids), int(self.k))
+        if self.levels is None:
+            if int(self.max_count) < 0:
+                raise ValueError("repeat: max_count must be >= 0")
+            lv = [float(self.penalty) * min(j, int(self.max_count)) for j in range(REPEAT_LEVELS)]
+        else:
+            lv = [float(v) for v in self.levels]
+            if not 1 <= len(lv) <= REPEAT_LEVELS:
+                raise ValueError(f"repeat: levels takes 1 to {REPEAT_LEVELS} values, got {len(lv)}")
+            lv = lv + [lv[-1]] * (REPEAT_LEVELS - len(lv))
+        levels = torch.tensor(lv, dtype=torch.float64).to(torch.float32)
+        if not bool(torch.isfinite(levels).all()):
+            raise ValueError(f"repeat: levels must be finite in f32, got {lv}")
+        if float(levels[0]) != 0.0:
+            raise ValueError(f"repeat: levels[0] (a k-mer never seen) must be 0, got {lv[0]}")
+        end_num = 0
+        if self.end_fraction is not None:
+            f = float(self.end_fraction)
+            if not (math.isfinite(f) and 0.0 < f < 1.0):
+                raise ValueError(f"repeat: end_fraction must lie in (0, 1), got {self.end_fraction!r}")
+            end_num = int(round(f * REPEAT_END_SCALE))
+            if not 1 <= end_num <= REPEAT_END_SCALE - 1:
+                raise ValueError(f"repeat: end_fraction {f} is held as a multiple of 1 / {REPEAT_END_SCALE} in 1 ... {REPEAT_END_SCALE - 1}")
+        if int(self.end_min_tokens) < 1:
+            raise ValueError("repeat: end_min_tokens must be >= 1")
+        return SimpleNamespace(ids=tuple(ids), n_sym=len(ids), k=int(self.k), M=M, levels=levels, end_num=end_num,
+                               end_min_tokens=int(self.end_min_tokens), count_prompt=bool(self.count_prompt))

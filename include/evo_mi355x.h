@@ -83,6 +83,7 @@ extern "C" {
  *      signature changed.
  *      Added since under ABI 20, no signature changed: the paged KV entries, the beam search entries, and evo_linear_rowinv_bf16 /
  *      evo_mlp_gate_rowinv_bf16 (the row-invariant dense launches of the decode pool's opt-in batch-invariant step, csrc/gemv_inv.hip).
+ *      evo_repeat_rows_f32 (k-mer repeat control in front of the decode pool's sampler launch, csrc/repeat.hip).
  *      A binding that needs them finds out at load time: every entry it declares must be exported. */
 #define EVO_ABI_VERSION 20
 int evo_abi_version(void);
@@ -748,6 +749,54 @@ int evo_sample_rows_dfa_f32(const void* logits, int64_t logits_f32, int64_t ld, 
                             int64_t* length, uint8_t* finish, const int32_t* dfa_alphabet, int64_t n_sym,
                             const int32_t* dfa_next, int64_t n_states, const int64_t* dfa_base, int32_t* dfa_state,
                             int64_t S, int64_t V, void* stream);
+
+/* ---- k-mer repeat control in front of the sampler launch (added under ABI 20, no signature changed; csrc/repeat.hip) ----
+ * no device counterpart in the reference: its design pipeline generates, then discards sequences whose most frequent k-mer covers too much
+ * of them, and its generation script hands a token-level repetition_penalty to the sampler
+ *                                                           [REF semantic_design/semantic_design.py:565-590,613; scripts/generation_to_folding.py:43,94]
+ * Call site: DecodePool's job-control path when `repeat` is given (evo_amd/pool.py: _repeat_rows, the node in front of the sampler launch of
+ * the captured pooled step, and the one-row launch in front of the one that draws a job's first token).  Written specification:
+ * evo_amd/sh/sample.py repeat_fold / repeat_ended / repeat_penalise / repeat_row.  One launch, one 64-lane wave per row, no host reads, no
+ * allocation, no LDS, plain vector stores, no atomics: capturable.
+ *   logits      [S, 512] bf16, or f32 with logits_f32 != 0; row pitch ld (>= 512, a multiple of 8); 16-byte aligned.  Read only
+ *   out         f32 [S, 512], 16-byte aligned, row pitch 512: the row the sampler launch that follows draws from
+ *   fed_ids     device int64 [S] or NULL: the token this step is fed (the one the previous step drew).  NULL: nothing is folded (a job's
+ *               first row, computed from the prefill's last logits)
+ *   active      device bytes [S]: rows with 0 read and write nothing
+ *   counts      device int32 [S, M], in/out: how often each k-mer has been seen (saturating at 2^31 - 1)
+ *   ctx         device int32 [S, 2], in/out: (code, len), the last len <= k - 1 alphabet symbols in base n_sym, newest in the lowest digit.
+ *               A window outside its invariants (len outside [0, k - 1], code outside [0, M / n_sym)) reads as the empty one (0, 0): no index
+ *               ever leaves the row's M cells
+ *   stat        device int64 [S, 2], in/out: (n_gen, rep), the generated tokens folded in and how many of them completed a k-mer seen before
+ *   levels      device f32 [S, 8]: what is subtracted at a count of 0 ... 7 (or more); the caller keeps levels[s][0] == 0
+ *   end_num     device int32 [S] or NULL: the early end is armed for rows with end_num[s] > 0 (a fraction end_num / 1024); NULL: for none
+ *   end_min_tokens  >= 1 when end_num is given
+ *   count       device int64 [S], read only: the tokens the row's job has recorded (the sampler's counter); length / finish as the sampler's
+ *   alphabet    HOST int32 [n_sym], 1 <= n_sym <= 8 distinct token ids in [0, 512).  Read before the launch, it travels in its arguments (a
+ *               captured graph keeps the alphabet it was captured with), exactly as dfa_alphabet
+ *   k >= 1, M == n_sym ** k <= 2^20
+ * Per ACTIVE row, in this order (a = the symbol index of the token, if it is one):
+ *   1. with fed_ids: no symbol: ctx = (0, 0).  A symbol at len == k - 1: idx = code * n_sym + a, old = counts[idx], counts[idx] =
+ *      min(old + 1, 2^31 - 1), rep += 1 if old >= 1, code = idx % (M / n_sym).  A symbol at len < k - 1: code = code * n_sym + a, len += 1.
+ *      n_gen += 1 in every case.  (k == 1: len == 0 == k - 1 always and idx = a: a per-token count.)
+ *   2. with end_num: if end_num[s] > 0 and n_gen >= end_min_tokens and rep * 1024 > end_num[s] * n_gen (int64): active[s] = 0, length[s] =
+ *      count[s], finish[s] = EVO_FINISH_REPEAT; out[s] is NOT written (the sampler launch skips the row).
+ *   3. otherwise out[s] = the row widened to f32 (exact) and, if len == k - 1, for every symbol a: c = counts[code * n_sym + a] and
+ *      out[s][alphabet[a]] -= levels[s][min(max(c, 0), 7)] -- ONE f32 subtraction, no multiply.  Every other id, and the whole row when
+ *      len < k - 1, is the widened value bit for bit.
+ * The per-row vectors need only their element's alignment (one-row slices).  Returns -1 before any launch, without dereferencing a device
+ * pointer, for: a null logits / out / active / counts / ctx / stat / levels / alphabet; logits or out not 16-byte aligned, another operand
+ * not aligned to its element; n_sym outside 1 ... 8; an alphabet id outside [0, 512) or given twice; k < 1; M != n_sym ** k or M > 2^20;
+ * V != 512; ld < V or ld % 8 != 0; S < 1; end_num given with a null count / length / finish or end_min_tokens < 1. */
+#define EVO_REPEAT_V 512
+#define EVO_REPEAT_MAX_SYMBOLS 8
+#define EVO_REPEAT_MAX_TABLE (1 << 20)
+#define EVO_REPEAT_LEVELS 8
+#define EVO_FINISH_REPEAT 6
+int evo_repeat_rows_f32(const void* logits, int64_t logits_f32, int64_t ld, float* out, const int64_t* fed_ids, uint8_t* active,
+                        int32_t* counts, int32_t* ctx, int64_t* stat, const float* levels, const int32_t* end_num, int64_t end_min_tokens,
+                        const int64_t* count, int64_t* length, uint8_t* finish, const int32_t* alphabet, int64_t n_sym, int64_t k,
+                        int64_t M, int64_t S, int64_t V, void* stream);
 
 /* ---- beam search on the device (csrc/beam.hip; specification: evo_amd/sh/sample.py beam_select) ----------------
  * evo_beam_select_f32: one step of beam search over logits [S, 512] (bf16, or f32 with logits_f32 != 0; row stride ld), one launch,

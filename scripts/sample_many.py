@@ -15,6 +15,12 @@ Constrained generation: every generation fills an IUPAC t
     python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --template ATGNNNNNNRRYNNNTAA
     python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --encode-protein MKLS*
     python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --orf-min-codons 50
+
+k-mer repeat control: nucleotides that would complete an 8-mer the generation (or its prompt) already holds are
+penalised, and a generation of which more than 30 % is such repeats ends early
+
+    python -m scripts.sample_many --prompts prompts.fasta --output-csv out.csv --allowed-tokens ACGT --repeat-k 8 \
+        --repeat-end-fraction 0.3 --extra-columns
 """
 import argparse
 import csv
@@ -63,8 +69,8 @@ def main(argv=None):
                                                               "tokens (3: in-frame codons)")
     ap.add_argument("--scores-only", action="store_true", help="keep no logits, on the device or on the host: the scores come from the "
                                                                "sampler's own log-probabilities")
-    ap.add_argument("--extra-columns", action="store_true", help="append Length and Finish (stop_token | stop_sequence | constraint | length) "
-                                                                 "to the CSV")
+    ap.add_argument("--extra-columns", action="store_true", help="append Length and Finish (stop_token | stop_sequence | constraint | length | "
+                                                                 "repeat) to the CSV, and Repeats with --repeat-k")
     ap.add_argument("--template", default=None, metavar="IUPAC", help="every generation fills this template of IUPAC nucleotide codes, "
                                                                       "e.g. ATGNNNNNNRRYNNNTAA")
     ap.add_argument("--encode-protein", default=None, metavar="SEQ", help="every generation is DNA that encodes this protein (one-letter "
@@ -88,6 +94,15 @@ def main(argv=None):
     ap.add_argument("--batch-invariant", action="store_true", help="with --seed: every generation is the same bits at any --n-slots from 1 to 64 "
                                                                    "(one launch sequence at every slot count; not with --prefill-batch > 1, "
                                                                    "--share-prompt-kv, --kv-dtype fp8 or --weight-dtype fp8)")
+    ap.add_argument("--repeat-k", type=int, default=None, metavar="N", help="turn k-mer repeat control on: a nucleotide that would complete an "
+                                                                            "N-mer the generation or its prompt already holds is penalised")
+    ap.add_argument("--repeat-penalty", type=float, default=None, help="what is subtracted from such a nucleotide's logit per earlier "
+                                                                       "occurrence of the N-mer (default 1.0)")
+    ap.add_argument("--repeat-max-count", type=int, default=None, metavar="C", help="occurrences beyond C add nothing (default 4, at most 7)")
+    ap.add_argument("--repeat-ignore-prompt", action="store_true", help="count the k-mers of the generation only, not those of its prompt")
+    ap.add_argument("--repeat-end-fraction", type=float, default=None, metavar="F", help="end a generation (Finish: repeat) once more than "
+                                                                                         "this fraction of it completed an N-mer seen before")
+    ap.add_argument("--repeat-end-min-tokens", type=int, default=None, metavar="N", help="... but not before N tokens (default 64)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)
     args = ap.parse_args(argv)
@@ -105,6 +120,10 @@ def main(argv=None):
                  "--kv-dtype fp8 or --weight-dtype fp8")
     if args.kv_dtype != "bf16" and args.share_prompt_kv:
         ap.error("--kv-dtype fp8 does not combine with --share-prompt-kv (the prompt store is bf16)")
+    if args.repeat_k is None and (args.repeat_penalty is not None or args.repeat_max_count is not None or args.repeat_ignore_prompt
+                                  or args.repeat_end_fraction is not None or args.repeat_end_min_tokens is not None):
+        ap.error("--repeat-penalty, --repeat-max-count, --repeat-ignore-prompt, --repeat-end-fraction and --repeat-end-min-tokens apply "
+                 "with --repeat-k only")
     if sum(x is not None for x in (args.template, args.encode_protein, args.orf_min_codons)) > 1:
         ap.error("at most one of --template, --encode-protein and --orf-min-codons")
     if args.then != "end" and args.template is None and args.encode_protein is None:
@@ -139,16 +158,24 @@ def main(argv=None):
         ctl["constraints"] = evo_amd.encode_protein(args.encode_protein, then=args.then)
     elif args.orf_min_codons is not None:
         ctl["constraints"] = evo_amd.open_reading_frame(args.orf_min_codons)
+    if args.repeat_k is not None:
+        ctl["repeat"] = evo_amd.RepeatControl(
+            k=args.repeat_k, penalty=1.0 if args.repeat_penalty is None else args.repeat_penalty,
+            max_count=4 if args.repeat_max_count is None else args.repeat_max_count, count_prompt=not args.repeat_ignore_prompt,
+            end_fraction=args.repeat_end_fraction, end_min_tokens=64 if args.repeat_end_min_tokens is None else args.repeat_end_min_tokens)
     seqs, scores, owner = pool.generate(prompts, n_tokens=args.n_tokens, n_sample_per_prompt=args.n_sample_per_prompt,
                                         prepend_bos=args.prepend_bos, **ctl)
     extra = [[]] * len(seqs)
     if args.extra_columns:                                    # (without any of the options above every job runs to --n-tokens)
         extra = [[str(n), f] for n, f in zip(pool.last_lengths, pool.last_finish)] if ctl else [[str(args.n_tokens), "length"]] * len(seqs)
+        if args.repeat_k is not None:                         # Repeats: generated tokens that completed a k-mer seen before
+            extra = [x + [str(rep)] for x, (_, rep) in zip(extra, pool.last_repeats)]
     rows = [[uuid.uuid4().hex, prompts[o], s, str(sc)] + x for s, sc, o, x in zip(seqs, scores, owner, extra)
             if s.strip() and not math.isnan(sc)]              # the reference drops empty / NaN-scored generations
     with open(args.output_csv, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["UUID", "Prompt", "Generated Sequence", "Score"] + (["Length", "Finish"] if args.extra_columns else []))
+        w.writerow(["UUID", "Prompt", "Generated Sequence", "Score"] + (["Length", "Finish"] if args.extra_columns else [])
+                   + (["Repeats"] if args.extra_columns and args.repeat_k is not None else []))
         w.writerows(rows)
     print(f"{len(rows)} generations of {'at most ' if ctl else ''}{args.n_tokens} tokens from {len(prompts)} prompts -> {args.output_csv} "
           f"({pool.stats['steps']} pooled steps, {pool.stats['prefills']} prefills)")
