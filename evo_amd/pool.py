@@ -49,8 +49,8 @@ for its life, so its captured step is captured on it.  Not with `share_prompt_kv
 
 `weight_dtype="fp8"` (opt-in; pools of up to 8 slots): the step streams FP8 e4m3fn copies of the dense weights (half
 the bytes; the copies sit beside the bf16 weights, which the prefills keep reading).  `stats["weight_dtype"]` and
-`stats["decode_weight_bytes"]` report the format and what a step streams.  It composes with every option above: only the dense
-launches of the step change.
+`stats["decode_weight_bytes"]` report the format and what a step streams.  It composes with every option above, `share_prompt_kv` and
+`beam_search` included (every cache of a pool is built by `_new_caches`, which sets the step flags): only the dense launches of the step change.
 
 `kv_paged=True` (opt-in): the KV cache is a pool of pages of `kv_page_tokens` tokens (`PagedKV`) and ONE device table
 [n_slots, table_width] for all layers.  A job reserves ceil((prompt + its own limit) / page_tokens) pages from a host free list when it is
@@ -83,9 +83,18 @@ Beam search: `beam_search(prompts, n_tokens, beam_width)`
 captured step is forward, `beam_select` (the group's W x 512 candidates ranked on the device; parents, tokens and scores written where the
 next step reads them), `gather_rows` out to a scratch buffer and back (every record of a slot -- FIR history, modal state, the keys it has
 generated -- moves to the slot that continues its hypothesis), advance.  The host walks the recorded back-pointers when a group is fetched.
+
+How the file is laid out.  Refusals and every attribute's declaration are in `DecodePool.__init__`.  `_new_caches` is the
+one constructor of a pool's caches; the three KV layouts (`_RowsKV`: contiguous bf16 / FP8 rows, `_PagedKV`, `_StoreKV`: the shared prompt
+store) add their K/V tensors to it and answer the scheduler's six calls -- `size`, `need` / `can_admit`, `install`, `release`, `advance`,
+`nbytes` -- so that the scheduler never asks which layout it runs on.  `_check_job` validates a call's prompts and arguments for `generate`,
+its job-control path and `beam_search`.  `_run` is the one scheduling loop of `generate` (admit, step, look, fetch) for its three sampler
+modes; `_run_beam` is the beam search's own loop over groups.  `_captured` is the one place a step is captured and replayed; `_step`,
+`_step_sampled` and `_step_beam` go through it.
 """
 from __future__ import annotations
 
+import weakref
 from collections import deque
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -102,77 +111,291 @@ from .sh.sample import (FINISH_CONSTRAINT, FINISH_DEAD_END, FINISH_LENGTH, FINIS
                         allowed_mask, sample, stop_patterns)
 
 
+def _kv_bytes(kvs) -> int:
+    """Bytes held by KV tensors of any of the formats: what stats["kv_bytes"] reports."""
+    return sum(kv.nbytes() if isinstance(kv, (Fp8KV, PagedKV)) else kv.numel() * kv.element_size() for kv in kvs)
+
+
+class _RowsKV:
+    """The KV layouts of a pool.  The scheduler talks to its layout through these calls alone and never asks which
+    one it has: `size` (for a call's jobs), `need` / `can_admit` (what a job reserves; may the head of the queue be admitted now),
+    `install` (a prompt's K/V, from row `row` of a prefill, into a slot), `release` (finished slots), `advance` (every position by one)
+    and `nbytes`.  A layout is chosen once, in DecodePool.__init__; the tensors and host lists it manages are the pool's declared state.
+
+    This one is the contiguous layout, and the base of the other two: `capacity` KV rows per slot and layer, bf16 tensors or `Fp8KV`."""
+    name = "contiguous"                                               # InferenceParams.kv_layout
+
+    def __init__(self, pool: "DecodePool"):
+        # (no cycle: a dropped pool dies by reference count, at once.  Left to the cycle collector, its captured graph would be destroyed
+        # whenever the collector runs -- in the middle of another pool's stream capture, which aborts the process)
+        self.p = weakref.proxy(pool)
+
+    def size(self, lens: Sequence[int], limits: Sequence[int], copies: int, rows: Optional[int] = None) -> None:
+        self.allocate(max(lens) + max(limits))
+
+    def allocate(self, capacity: int) -> None:
+        """Pool-wide caches with `capacity` KV rows per slot (grown geometrically, outside any captured graph)."""
+        p = self.p
+        m, S, dev = p.model, p.n_slots, p.device
+        if p.ipd is not None and capacity <= p.capacity:
+            return
+        capacity = max(capacity, 2 * p.capacity)
+        old = p.ipd
+        ipd = p._new_caches(capacity)
+        H, hd, dt = m.num_heads, m.head_dim, m.embedding_layer.weight.dtype
+        for i in m.attn_layer_idxs:
+            prev = None if old is None else old["mha"].key_value_memory_dict[i]
+            if p.kv_dtype == "fp8":
+                kv = Fp8KV.zeros(S, capacity, H, hd, dev)
+                if prev is not None:
+                    kv.copy_rows_(slice(None), prev, slice(None), prev.shape[1])
+            else:
+                kv = torch.zeros(S, capacity, 2, H, hd, dtype=dt, device=dev)
+                if prev is not None:
+                    kv[:, : prev.shape[1]] = prev
+            ipd["mha"].key_value_memory_dict[i] = kv
+        p.ipd, p.capacity = ipd, capacity
+        p.stats["kv_bytes"] = self.nbytes()
+
+    def need(self, n_keys: int) -> int:
+        """What a job of `n_keys` = prompt + own limit tokens reserves at admission (pages; nothing here)."""
+        return 0
+
+    def can_admit(self, need: int) -> bool:
+        return True
+
+    def install(self, slot: int, pi: int, tmp: dict, P: int, **kw) -> None:
+        """Slot `slot` continues prompt `pi` from row `row` of the prefill's caches `tmp`; `need`: what the job reserves.  (Through the
+        pool's own method: it adds the Hyena states, and it is the name tests and tools hook.)"""
+        self.p._install(slot, tmp, P, **kw)
+
+    def put(self, slot: int, tmp: dict, P: int, row: int, need: int = 0, prompt: Optional[int] = None) -> None:
+        for i in self.p.model.attn_layer_idxs:
+            dst, src = self.p.ipd["mha"].key_value_memory_dict[i], tmp["mha"].key_value_memory_dict[i]
+            if isinstance(dst, Fp8KV):
+                dst.copy_rows_(slot, src, row, P)                        # both tensors of the layer
+            else:
+                dst[slot, :P] = src[row, :P]
+
+    def release(self, slots: Sequence[int]) -> None:
+        pass
+
+    def advance(self) -> None:
+        """Every slot moves on by one token (idle slots drift harmlessly; fill() resets them)."""
+        self.p.pos.add_(1)
+        self.p.pos.clamp_(max=self.p.capacity - 1)
+
+    def nbytes(self) -> int:
+        return _kv_bytes(self.p.ipd["mha"].key_value_memory_dict.values())
+
+
+class _PagedKV(_RowsKV):
+    """kv_paged: pages of `page_tokens` tokens and ONE device table `pool.table` for all layers; the host free list
+    `pool._free_pages` (page 0, the scrap page, is never on it) and the pages of each slot's job `pool._slot_pages`."""
+    name = "paged"
+
+    def need(self, n_keys: int) -> int:
+        return -(-int(n_keys) // self.p.page_tokens)
+
+    def can_admit(self, need: int) -> bool:
+        return need <= len(self.p._free_pages)
+
+    def size(self, lens, limits, copies, rows=None) -> None:
+        """Page pool and table for one call: a job reserves to its OWN limit.  The table is as wide as the largest need; without a budget
+        the pool holds the `n_slots` largest needs (admission never waits), with one it holds the budget.  Runs between calls, when no job
+        is live: a larger pool is allocated afresh and nothing is copied; a wider table or a new pool drops the captured step (it is
+        bound to their addresses)."""
+        p = self.p
+        m, S, dev, pt = p.model, p.n_slots, p.device, p.page_tokens
+        needs = [self.need(P + n) for P, n in zip(lens, limits) for _ in range(int(copies))]
+        width = max(needs)
+        if p.budget_pages is not None:
+            if width > p.budget_pages:
+                raise ValueError(f"kv_paged: a job needs {width} pages of {pt} tokens, the budget kv_budget_tokens holds "
+                                 f"{p.budget_pages}")
+            n_pages = 1 + p.budget_pages
+        else:
+            n_pages = 1 + sum(sorted(needs, reverse=True)[:S])
+        fresh = p.ipd is None
+        if fresh:
+            p.ipd = p._new_caches(0)
+            p._slot_pages = [[] for _ in range(S)]
+        mha = p.ipd["mha"]
+        if p.table is None or p.table.shape[1] < width:
+            p.table = torch.zeros(S, width, dtype=torch.int32, device=dev)
+            for kv in mha.key_value_memory_dict.values():
+                kv.table = p.table
+            p._graph = None
+        if fresh or n_pages > p.stats["kv_pages"]:
+            dt = m.embedding_layer.weight.dtype
+            for i in m.attn_layer_idxs:
+                mha.key_value_memory_dict.pop(i, None)               # (let go of the old pool before the new one is made)
+                mha.key_value_memory_dict[i] = PagedKV.zeros(n_pages, pt, m.num_heads, m.head_dim, p.table, dtype=dt)
+            p._free_pages = list(range(n_pages - 1, 0, -1))          # popped from the end: page 1 first; page 0 stays out
+            p.stats["kv_pages"] = n_pages
+            p.stats["kv_bytes"] = self.nbytes()
+            p._graph = None
+        p.capacity = p.table.shape[1] * pt                           # the bound of a slot's position
+        mha.max_seqlen = p.capacity
+
+    def put(self, slot, tmp, P, row, need=0, prompt=None) -> None:
+        # the job's reservation: `need` pages off the free list, named in its table row (outside the captured step, like all of this)
+        p = self.p
+        pages = [p._free_pages.pop() for _ in range(need)]
+        p._slot_pages[slot] = pages
+        ids = torch.tensor(pages, dtype=torch.int64, device=p.device)
+        p.table[slot, :need] = ids.to(torch.int32)
+        p.stats["kv_pages_peak"] = max(p.stats["kv_pages_peak"], p.stats["kv_pages"] - 1 - len(p._free_pages))
+        for i in p.model.attn_layer_idxs:                            # the prompt's K/V, from row `row` of the prefill's own cache
+            p.ipd["mha"].key_value_memory_dict[i].write_tokens_(ids, tmp["mha"].key_value_memory_dict[i][row, :P])
+
+    def release(self, slots) -> None:
+        """Finished slots give their pages back; their table rows return to zeros (the scrap page)."""
+        p = self.p
+        for s in slots:
+            p._free_pages.extend(reversed(p._slot_pages[s]))
+            p._slot_pages[s] = []
+        p.table[torch.tensor(list(slots), dtype=torch.int64, device=p.device)] = 0
+
+
+class _StoreKV(_RowsKV):
+    """share_prompt_kv: own caches of the generated tokens only, and `pool.store`, R rows of the longest prompt's
+    length, each holding the K/V of one prompt for all its copies.  Host: `pool.store_refs` (live copies per row), `pool._store_prompt`
+    (the prompt a row holds, kept after its last copy finished), `pool._slot_row` (mirror of store.row)."""
+
+    def size(self, lens, limits, copies, rows=None) -> None:
+        """Jobs run in order and have one length, so the live jobs are a window of at most S consecutive jobs: they touch at most
+        ceil(S / n) + 1 prompts (and never more than S).  `rows`: jobs of unequal length break the window -- job 0 may outlive jobs
+        1 ... 40 -- so the caller asks for min(S, number of prompts) rows: one per live slot, or one per prompt (beam: one per group)."""
+        p = self.p
+        m, S, dev = p.model, p.n_slots, p.device
+        p_max, n_tokens = max(lens), max(limits)
+        R = min(S, -(-S // int(copies)) + 1) if rows is None else int(rows)
+        if p.store is not None and p.capacity >= n_tokens and p.store_cap >= p_max and len(p.store_refs) >= R:
+            p._store_prompt = [None] * len(p.store_refs)             # prompt indices belong to one job list
+            return
+        ipd = p._new_caches(n_tokens)
+        H, hd, dt = m.num_heads, m.head_dim, m.embedding_layer.weight.dtype
+        st = PromptStore(row=torch.full((S,), -1, dtype=torch.int64, device=dev), length=torch.ones(R, dtype=torch.int64, device=dev),
+                         own_pos=torch.zeros(S, dtype=torch.int64, device=dev))
+        for i in m.attn_layer_idxs:
+            ipd["mha"].key_value_memory_dict[i] = torch.zeros(S, n_tokens, 2, H, hd, dtype=dt, device=dev)
+            st.kv[i] = torch.zeros(R, p_max, 2, H, hd, dtype=dt, device=dev)
+        ipd["mha"].prompt_store = st
+        p.ipd, p.capacity, p.store, p.store_cap = ipd, n_tokens, st, p_max
+        p.store_refs, p._store_prompt, p._slot_row = [0] * R, [None] * R, [-1] * S
+        p.stats["store_rows"] = R
+        p.stats["kv_bytes"] = self.nbytes()
+
+    def install(self, slot, pi, tmp, P, **kw) -> None:
+        self.p._install_shared(slot, pi, tmp, P, **kw)
+
+    def put(self, slot, tmp, P, row, need=0, prompt=None) -> None:
+        """The prompt's K/V goes into a store row unless one holds it already."""
+        p, st = self.p, self.p.store
+        if prompt in p._store_prompt:
+            r = p._store_prompt.index(prompt)
+        else:
+            r = p.store_refs.index(0)                                # (exists: see size)
+            for i in p.model.attn_layer_idxs:
+                st.kv[i][r, :P] = tmp["mha"].key_value_memory_dict[i][row, :P]
+            st.length[r] = P
+            p._store_prompt[r] = prompt
+            p.stats["prompt_kv_installs"] += 1
+        p.store_refs[r] += 1
+        p._slot_row[slot] = r
+        st.row[slot] = r
+        st.own_pos[slot] = 0
+
+    def release(self, slots) -> None:
+        """Finished slots let go of their store rows (the host knows when: it fetches them) and point at none."""
+        p = self.p
+        for s in slots:
+            p.store_refs[p._slot_row[s]] -= 1
+            p._slot_row[s] = -1
+        p.store.row[torch.tensor(list(slots), dtype=torch.int64, device=p.device)] = -1
+
+    def advance(self) -> None:
+        p = self.p
+        p.pos.add_(1)
+        p.pos.clamp_(max=p.store_cap + p.capacity - 1)
+        p.store.own_pos.add_(1)
+        p.store.own_pos.clamp_(max=p.capacity - 1)
+
+    def nbytes(self) -> int:
+        return _kv_bytes(list(self.p.ipd["mha"].key_value_memory_dict.values()) + list(self.p.store.kv.values()))
+
+
 class DecodePool:
+    # options that do not combine (ValueError), in the order they are refused: (one option, the other, the message)
+    _EXCLUSIVE = (
+        ("batch_invariant", "prefill_batch", "batch_invariant=True does not combine with prefill_batch > 1 (a padded batch's prefill depends on "
+                                             "the prompts admitted together)"),
+        ("batch_invariant", "share_prompt_kv", "batch_invariant=True does not combine with share_prompt_kv=True (the grouped decode attention "
+                                               "splits by group)"),
+        ("batch_invariant", "kv_fp8", 'batch_invariant=True does not combine with kv_dtype="fp8"'),
+        ("batch_invariant", "w_fp8", 'batch_invariant=True does not combine with weight_dtype="fp8"'),
+        ("kv_paged", "share_prompt_kv", "kv_paged=True does not combine with share_prompt_kv=True: the prompt store and its grouped decode "
+                                        "attention read contiguous rows"),
+        ("kv_paged", "kv_fp8", 'kv_paged=True does not combine with kv_dtype="fp8": the paged cache and its two kernels are bf16'),
+        ("kv_fp8", "share_prompt_kv", 'kv_dtype="fp8" does not combine with share_prompt_kv=True: the prompt store and its grouped decode '
+                                      "attention are bf16"),
+    )
+
     def __init__(self, model, tokenizer, n_slots: int = 8, top_k: int = 4, top_p: float = 1.0,
                  temperature: float = 0.7, device: Optional[str] = None, use_graph: Optional[bool] = None,
                  seed: Optional[int] = None, allowed_tokens=None, share_prompt_kv: bool = False, prefill_batch: int = 1,
                  prefill_max_tokens: int = 32768, poll_every: int = 8, kv_dtype: str = "bf16", weight_dtype: str = "bf16",
                  kv_paged: bool = False, kv_page_tokens: int = 256, kv_budget_tokens: Optional[int] = None, batch_invariant: bool = False):
+        # every refusal before any device work (DESIGN.md sections 21-23, 25): values, then pairs of options, then what the backend lacks
         self.model = model
-        self.kv_dtype = check_kv_dtype(kv_dtype)
-        self.batch_invariant = bool(batch_invariant)
-        if self.batch_invariant:                                     #  every refusal before any device work
+        self.kv_dtype, self.weight_dtype = check_kv_dtype(kv_dtype), check_weight_dtype(weight_dtype)
+        self.batch_invariant, self.kv_paged, self.share_prompt_kv = bool(batch_invariant), bool(kv_paged), bool(share_prompt_kv)
+        self.poll_every, self.prefill_batch, self.prefill_max_tokens = int(poll_every), int(prefill_batch), int(prefill_max_tokens)
+        if self.batch_invariant:
             check_rowinv_rows(int(n_slots), "n_slots")
-            for what, bad in (("prefill_batch > 1 (a padded batch's prefill depends on the prompts admitted together)", int(prefill_batch) > 1),
-                              ("share_prompt_kv=True (the grouped decode attention splits by group)", bool(share_prompt_kv)),
-                              ('kv_dtype="fp8"', self.kv_dtype != "bf16"), ('weight_dtype="fp8"', weight_dtype != "bf16")):
-                if bad:
-                    raise ValueError(f"batch_invariant=True does not combine with {what}")
-            ops = getattr(model, "ops", None)
-            if ops is None or not Backend.adopt(ops).supports("row_invariant", "hyena_step"):
-                raise RuntimeError('batch_invariant=True needs a compute backend with the "row_invariant" kernels ('
-                                   + ", ".join(Backend.OPTIONAL["row_invariant"]) + ") and hyena_step; this model's backend has none")
-        self.kv_paged = bool(kv_paged)
-        if self.kv_paged:                                            #  every refusal before any device work
-            if share_prompt_kv:
-                raise ValueError("kv_paged=True does not combine with share_prompt_kv=True: the prompt store and its grouped decode "
-                                 "attention read contiguous rows")
-            if self.kv_dtype != "bf16":
-                raise ValueError('kv_paged=True does not combine with kv_dtype="fp8": the paged cache and its two kernels are bf16')
+        on = {"batch_invariant": self.batch_invariant, "kv_paged": self.kv_paged, "share_prompt_kv": self.share_prompt_kv,
+              "prefill_batch": self.prefill_batch > 1, "kv_fp8": self.kv_dtype != "bf16", "w_fp8": self.weight_dtype != "bf16"}
+        for a, b, message in self._EXCLUSIVE:
+            if on[a] and on[b]:
+                raise ValueError(message)
+        self.page_tokens = self.budget_pages = None
+        if self.kv_paged:
             self.page_tokens = check_page_tokens(kv_page_tokens)
-            self.budget_pages = None
             if kv_budget_tokens is not None:
                 self.budget_pages = int(kv_budget_tokens) // self.page_tokens
                 if self.budget_pages < 1:
                     raise ValueError(f"kv_budget_tokens = {kv_budget_tokens} holds no page of {self.page_tokens} tokens")
-            ops = getattr(model, "ops", None)
-            if ops is None or not Backend.adopt(ops).supports("kv_paged"):
-                raise RuntimeError('kv_paged=True needs a compute backend with the "kv_paged" kernels (rope_append_decode_paged, '
-                                   "attention_decode_paged); this model's backend has none")
-        self.weight_dtype = check_weight_dtype(weight_dtype)
         if self.weight_dtype == "fp8":                               # (DESIGN.md section 22)
             from .generation import check_fp8_weight_model
             check_weight_rows(int(n_slots), "n_slots")
             check_fp8_weight_model(model)
-        self.poll_every = int(poll_every)
         if self.poll_every < 1:
             raise ValueError("poll_every must be >= 1")
-        self.prefill_batch, self.prefill_max_tokens = int(prefill_batch), int(prefill_max_tokens)
         if self.prefill_batch < 1:
             raise ValueError("prefill_batch must be >= 1")
         if self.prefill_batch > 1 and not hasattr(model, "prefill_ragged"):
             raise RuntimeError("prefill_batch > 1 needs a model with prefill_ragged (one forward over prompts of unequal length)")
-        self.share_prompt_kv = bool(share_prompt_kv)
-        if self.share_prompt_kv and not hasattr(getattr(model, "ops", None), "attention_decode_prefix"):
-            raise RuntimeError("share_prompt_kv=True needs a compute backend with attention_decode_prefix (the decode attention over a "
-                               "shared prompt store); this model's backend has none")
-        if self.kv_dtype == "fp8":                                   # 
-            if self.share_prompt_kv:
-                raise ValueError('kv_dtype="fp8" does not combine with share_prompt_kv=True: the prompt store and its grouped decode '
-                                 "attention are bf16")
-            ops = getattr(model, "ops", None)
-            if ops is None or not Backend.adopt(ops).supports("kv_fp8"):
-                raise RuntimeError('kv_dtype="fp8" needs a compute backend with the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, '
-                                   "attention_decode_fp8); this model's backend has none")
+        ops = getattr(model, "ops", None)
+
+        def has(*groups):
+            return ops is not None and Backend.adopt(ops).supports(*groups)
+        for wanted, option, kernels, there in (
+                (self.batch_invariant, "batch_invariant=True", 'the "row_invariant" kernels (' + ", ".join(Backend.OPTIONAL["row_invariant"])
+                 + ") and hyena_step", lambda: has("row_invariant", "hyena_step")),
+                (self.kv_paged, "kv_paged=True", 'the "kv_paged" kernels (rope_append_decode_paged, attention_decode_paged)', lambda: has("kv_paged")),
+                (self.share_prompt_kv, "share_prompt_kv=True", "attention_decode_prefix (the decode attention over a shared prompt store)",
+                 lambda: hasattr(ops, "attention_decode_prefix")),
+                (self.kv_dtype == "fp8", 'kv_dtype="fp8"', 'the "kv_fp8" kernels (kv_quant_fp8, rope_append_decode_fp8, attention_decode_fp8)',
+                 lambda: has("kv_fp8"))):
+            if wanted and not there():
+                raise RuntimeError(f"{option} needs a compute backend with {kernels}; this model's backend has none")
         self.tok = tokenizer
         self.n_slots = int(n_slots)
         self.top_k, self.top_p, self.temperature = top_k, top_p, temperature
         self.device = torch.device(device) if device is not None else model.device
         self.use_graph = (self.device.type == "cuda" and getattr(model, "decode_graph", False)) \
             if use_graph is None else bool(use_graph)
-        self.ipd = None
-        self.capacity = 0
-        self._graph = None
         self.stats = {"steps": 0, "prefills": 0, "tokens": 0, "batch_invariant": self.batch_invariant}
         if hasattr(model, "decode_weight_bytes"):
             self.stats.update({"weight_dtype": self.weight_dtype, "decode_weight_bytes": model.decode_weight_bytes(self.weight_dtype)})
@@ -182,10 +405,17 @@ class DecodePool:
             self.stats.update({"prefill_prompts": 0, "prefill_pad_tokens": 0})
         if self.kv_paged:
             self.stats.update({"kv_pages": 0, "kv_pages_peak": 0, "kv_page_waits": 0})
+        # the KV layout, chosen once: from here on nothing asks which one the pool has
+        self.kv = (_StoreKV if self.share_prompt_kv else _PagedKV if self.kv_paged else _RowsKV)(self)
+        # all state is declared here; the layout and the allocators below fill it in
+        self.ipd = None
+        self.capacity = 0
+        self.pos = self.ids = None                                   # device: every slot's position [S] and the token it is fed [S, 1]
         self.table = None                                            # kv_paged: device int32 [S, table_width], shared by every layer's PagedKV
         self._free_pages: List[int] = []                             # host free list (page 0, the scrap page, is never on it)
         self._slot_pages: List[List[int]] = []                       # host: the pages each slot's job owns
         self.store = None
+        self.store_cap = 0                                           # share_prompt_kv: the keys a store row holds
         self.store_refs: List[int] = []                              # host: live copies per store row
         self._store_prompt: List[Optional[int]] = []                 # host: the prompt a store row holds (kept after its last copy finished)
         self._slot_row: List[int] = []                               # host mirror of store.row
@@ -193,125 +423,65 @@ class DecodePool:
         self.device_sampler = seed is not None or allowed_tokens is not None
         self.seed = 0 if seed is None else int(seed)
         self.allow_mask = None if allowed_tokens is None else allowed_mask(tokenizer, allowed_tokens)
+        # per-slot sampler state (_allocate_sampler_state), the automata table (_upload_constraints), repeat-control state (_allocate_repeat)
+        self.s_top_k = self.s_top_p = self.s_temperature = self.s_stream = self.s_count = self.s_active = self.s_logprob = None
+        self.s_allow = self.s_stop_mask = self.s_limit = self.s_length = self.s_finish = self.s_dfa_base = self.s_dfa_state = None
+        self.s_dfa_next = None
+        self.s_rep_counts = self.s_rep_ctx = self.s_rep_stat = self.s_rep_levels = self.s_rep_end = self.s_rep_logits = None
         self.hist_ids = self.hist_logits = self.hist_logprob = None
+        self._graph = None                                           # the captured step: (graph, its output tensor or None)
         self._ctl = None                                             # job control: the stop rule of the running generate()
         self._graph_key = None                                       # what the captured step's sampler launch was captured with
         self._beam = self._beam_graph = None                         # beam search: its state and its captured step
 
-    # ------------------------------------------------------------------ cache rows
-    def _allocate(self, capacity: int) -> None:
-        """Pool-wide caches with `capacity` KV rows per slot (grown geometrically, outside any captured graph)."""
+    # ------------------------------------------------------------------ caches
+    def _new_caches(self, max_seqlen: int) -> dict:
+        """The one constructor of a pool's caches: the `ipd` pair with every step flag set from the pool's options, the Hyena FIR and modal
+        states, `pos`, `ids` and (with the device sampler) the sampler state.  The layout adds its K/V tensors and keeps the result.  New
+        caches drop the captured step."""
         m, S, dev = self.model, self.n_slots, self.device
-        if self.ipd is not None and capacity <= self.capacity:
-            return
-        capacity = max(capacity, 2 * self.capacity)
-        old = self.ipd
         ipd = m.initialize_inference_params()
-        ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
-        ipd["mha"].max_seqlen = capacity
-        ipd["mha"].kv_dtype = self.kv_dtype
-        ipd["mha"].weight_dtype = self.weight_dtype                  # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
-        ipd["mha"].batch_invariant = self.batch_invariant
-        D, H, hd = m.hidden_size, m.num_heads, m.head_dim
-        dt = m.embedding_layer.weight.dtype
-        for i in m.attn_layer_idxs:
-            prev = None if old is None else old["mha"].key_value_memory_dict[i]
-            if self.kv_dtype == "fp8":
-                kv = Fp8KV.zeros(S, capacity, H, hd, dev)
-                if prev is not None:
-                    kv.copy_rows_(slice(None), prev, slice(None), prev.shape[1])
-            else:
-                kv = torch.zeros(S, capacity, 2, H, hd, dtype=dt, device=dev)
-                if prev is not None:
-                    kv[:, : prev.shape[1]] = prev
-            ipd["mha"].key_value_memory_dict[i] = kv
-        self.stats["kv_bytes"] = self._kv_bytes(ipd)
+        mha = ipd["mha"]
+        mha.max_batch_size = ipd["hyena"].max_batch_size = S
+        mha.max_seqlen = max_seqlen
+        mha.kv_dtype, mha.kv_layout, mha.batch_invariant = self.kv_dtype, self.kv.name, self.batch_invariant
+        mha.weight_dtype = self.weight_dtype                         # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
+        D, dt = m.hidden_size, m.embedding_layer.weight.dtype
         for i in m.hyena_layer_idxs:
-            if old is not None:
-                ipd["hyena"].fir_state_dict[i] = old["hyena"].fir_state_dict[i]
-                ipd["hyena"].state_dict[i] = old["hyena"].state_dict[i]
-            else:
-                ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
-                ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
-        self.ipd, self.capacity = ipd, capacity
-        self._graph = None
+            ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
+            ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
         self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
         self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
         if self.device_sampler:
             self._allocate_sampler_state()
+        self._graph = None
+        return ipd
 
-    @staticmethod
-    def _kv_bytes(ipd, store=None) -> int:
-        """Bytes held by the KV tensors of `ipd` (and of a prompt store): what stats["kv_bytes"] reports."""
-        kvs = list(ipd["mha"].key_value_memory_dict.values()) + ([] if store is None else list(store.kv.values()))
-        return sum(kv.nbytes() if isinstance(kv, (Fp8KV, PagedKV)) else kv.numel() * kv.element_size() for kv in kvs)
+    def _allocate(self, capacity: int) -> None:
+        """Contiguous caches with at least `capacity` KV rows per slot (the layout's own allocator, under the name it always had)."""
+        self.kv.allocate(capacity)
 
-    # ------------------------------------------------------------------ paged KV (opt-in, DESIGN.md section 23)
-    def _page_need(self, n_keys: int) -> int:
-        """Pages a job of `n_keys` = prompt + own limit tokens reserves at admission."""
-        return -(-int(n_keys) // self.page_tokens)
+    def _install(self, slot: int, tmp: dict, P: int, row: int = 0, need: int = 0) -> None:
+        """Row `row` of a prefill's caches `tmp` into slot `slot`: the prompt's K/V by the layout (`need`: the pages the job reserves), the
+        Hyena states per slot."""
+        self.kv.put(slot, tmp, P, row, need=need)
+        self._install_states(slot, tmp, row)
 
-    def _allocate_paged(self, needs: Sequence[int]) -> None:
-        """Page pool and table for one generate() call whose jobs need `needs` pages each (job order).  The table is as wide as the
-        largest need; without a budget the pool holds the `n_slots` largest needs (admission never waits), with one it holds the
-        budget.  Runs between calls, when no job is live: a larger pool is allocated afresh and nothing is copied; a wider table or a
-        new pool drops the captured step (it is bound to their addresses)."""
-        m, S, dev, pt = self.model, self.n_slots, self.device, self.page_tokens
-        width = max(needs)
-        if self.budget_pages is not None:
-            if width > self.budget_pages:
-                raise ValueError(f"kv_paged: a job needs {width} pages of {pt} tokens, the budget kv_budget_tokens holds "
-                                 f"{self.budget_pages}")
-            n_pages = 1 + self.budget_pages
-        else:
-            n_pages = 1 + sum(sorted(needs, reverse=True)[:S])
-        fresh = self.ipd is None
-        if fresh:
-            ipd = m.initialize_inference_params()
-            ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
-            ipd["mha"].kv_layout = "paged"
-            ipd["mha"].weight_dtype = self.weight_dtype
-            ipd["mha"].batch_invariant = self.batch_invariant
-            D = m.hidden_size
-            dt = m.embedding_layer.weight.dtype
-            for i in m.hyena_layer_idxs:
-                ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
-                ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
-            self.ipd = ipd
-            self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
-            self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
-            self._slot_pages = [[] for _ in range(S)]
-            if self.device_sampler:
-                self._allocate_sampler_state()
-        mha = self.ipd["mha"]
-        if self.table is None or self.table.shape[1] < width:
-            self.table = torch.zeros(S, width, dtype=torch.int32, device=dev)
-            for kv in mha.key_value_memory_dict.values():
-                kv.table = self.table
-            self._graph = None
-        if fresh or n_pages > self.stats["kv_pages"]:
-            dt = m.embedding_layer.weight.dtype
-            for i in m.attn_layer_idxs:
-                mha.key_value_memory_dict.pop(i, None)               # (let go of the old pool before the new one is made)
-                mha.key_value_memory_dict[i] = PagedKV.zeros(n_pages, pt, m.num_heads, m.head_dim, self.table, dtype=dt)
-            self._free_pages = list(range(n_pages - 1, 0, -1))       # popped from the end: page 1 first; page 0 stays out
-            self.stats["kv_pages"] = n_pages
-            self.stats["kv_bytes"] = self._kv_bytes(self.ipd)
-            self._graph = None
-        self.capacity = self.table.shape[1] * pt                     # the bound of a slot's position
-        mha.max_seqlen = self.capacity
+    def _install_shared(self, slot: int, pi: int, tmp: dict, P: int, row: int = 0) -> None:
+        """The same for a layout that holds a prompt's K/V once for all its copies: slot `slot` continues prompt `pi`."""
+        self.kv.put(slot, tmp, P, row, prompt=pi)
+        self._install_states(slot, tmp, row)
 
-    def _can_admit(self, need: int) -> bool:
-        return not self.kv_paged or need <= len(self._free_pages)
+    def _install_states(self, slot: int, tmp: dict, row: int) -> None:
+        for i in self.model.hyena_layer_idxs:
+            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
+            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
+                self.ipd["hyena"].state_dict[i][slot].shape)
 
-    def _release_pages(self, slots: Sequence[int]) -> None:
-        """Finished slots give their pages back; their table rows return to zeros (the scrap page)."""
-        if not self.kv_paged:
-            return
-        for s in slots:
-            self._free_pages.extend(reversed(self._slot_pages[s]))
-            self._slot_pages[s] = []
-        self.table[torch.tensor(list(slots), dtype=torch.int64, device=self.device)] = 0
+    def _count_prefix_streams(self) -> None:
+        """The store rows one step streams: per workgroup tile of the grouped kernel, the distinct rows among its slots."""
+        gr = int(self.model.ops.attn_group_rows)
+        self.stats["prefix_streams"] += sum(len({r for r in self._slot_row[t:t + gr] if r >= 0}) for t in range(0, self.n_slots, gr))
 
     def _allocate_sampler_state(self) -> None:
         m, S, dev = self.model, self.n_slots, self.device
@@ -333,85 +503,6 @@ class DecodePool:
         # constrained generation: the table row of the slot's state 0 (-1: the slot's job is free) and its state relative to that row
         self.s_dfa_base = torch.full((S,), -1, dtype=torch.int64, device=dev)
         self.s_dfa_state = torch.zeros(S, dtype=torch.int32, device=dev)
-
-    def _allocate_shared(self, p_max: int, n_tokens: int, n_sample_per_prompt: int, rows: Optional[int] = None) -> None:
-        """share_prompt_kv: own caches of `n_tokens` rows per slot and a store of R rows of the longest prompt's length.  Jobs run in
-        order and have one length, so the live jobs are a window of at most S consecutive jobs: they touch at most ceil(S / n) + 1
-        prompts (and never more than S).  `rows` (job control): jobs of unequal length break the window -- job 0 may outlive jobs 1 ... 40 --
-        so the caller asks for min(S, number of prompts) rows: one per live slot, or one per prompt."""
-        m, S, dev = self.model, self.n_slots, self.device
-        R = min(S, -(-S // int(n_sample_per_prompt)) + 1) if rows is None else int(rows)
-        st = self.store
-        if st is not None and self.capacity >= n_tokens and self.store_cap >= p_max and len(self.store_refs) >= R:
-            self._store_prompt = [None] * len(self.store_refs)       # prompt indices belong to one job list
-            return
-        ipd = m.initialize_inference_params()
-        ipd["mha"].max_batch_size = ipd["hyena"].max_batch_size = S
-        ipd["mha"].max_seqlen = n_tokens
-        D, H, hd = m.hidden_size, m.num_heads, m.head_dim
-        dt = m.embedding_layer.weight.dtype
-        st = PromptStore(row=torch.full((S,), -1, dtype=torch.int64, device=dev), length=torch.ones(R, dtype=torch.int64, device=dev),
-                         own_pos=torch.zeros(S, dtype=torch.int64, device=dev))
-        for i in m.attn_layer_idxs:
-            ipd["mha"].key_value_memory_dict[i] = torch.zeros(S, n_tokens, 2, H, hd, dtype=dt, device=dev)
-            st.kv[i] = torch.zeros(R, p_max, 2, H, hd, dtype=dt, device=dev)
-        for i in m.hyena_layer_idxs:
-            ipd["hyena"].fir_state_dict[i] = torch.zeros(S, 3 * D, m.short_filter_length - 1, dtype=dt, device=dev)
-            ipd["hyena"].state_dict[i] = torch.zeros(S, D, m.state_size, dtype=torch.complex64, device=dev)
-        ipd["mha"].prompt_store = st
-        self.ipd, self.capacity, self.store, self.store_cap = ipd, n_tokens, st, p_max
-        self.store_refs, self._store_prompt, self._slot_row = [0] * R, [None] * R, [-1] * S
-        self.stats["store_rows"] = R
-        self.stats["kv_bytes"] = self._kv_bytes(self.ipd, self.store)
-        self._graph = None
-        self.pos = torch.zeros(S, dtype=torch.int64, device=dev)
-        self.ids = torch.zeros(S, 1, dtype=torch.int64, device=dev)
-        if self.device_sampler:
-            self._allocate_sampler_state()
-
-    def _install_shared(self, slot: int, pi: int, tmp: dict, P: int, row: int = 0) -> None:
-        """Slot `slot` continues prompt `pi` (row `row` of the prefill's caches): its K/V goes into a store row unless one holds it already;
-        the Hyena states stay per slot."""
-        m, st = self.model, self.store
-        if pi in self._store_prompt:
-            r = self._store_prompt.index(pi)
-        else:
-            r = self.store_refs.index(0)                             # (exists: see _allocate_shared)
-            for i in m.attn_layer_idxs:
-                st.kv[i][r, :P] = tmp["mha"].key_value_memory_dict[i][row, :P]
-            st.length[r] = P
-            self._store_prompt[r] = pi
-            self.stats["prompt_kv_installs"] += 1
-        self.store_refs[r] += 1
-        self._slot_row[slot] = r
-        st.row[slot] = r
-        st.own_pos[slot] = 0
-        for i in m.hyena_layer_idxs:
-            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
-            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
-                self.ipd["hyena"].state_dict[i][slot].shape)
-
-    def _release_shared(self, slots: Sequence[int]) -> None:
-        """Finished slots let go of their store rows (the host knows when: a job's length is fixed) and point at none."""
-        for s in slots:
-            self.store_refs[self._slot_row[s]] -= 1
-            self._slot_row[s] = -1
-        self.store.row[torch.tensor(list(slots), dtype=torch.int64, device=self.device)] = -1
-
-    def _advance(self) -> None:
-        """Every slot moves on by one token (idle slots drift harmlessly; fill() resets them)."""
-        self.pos.add_(1)
-        if self.share_prompt_kv:
-            self.pos.clamp_(max=self.store_cap + self.capacity - 1)
-            self.store.own_pos.add_(1)
-            self.store.own_pos.clamp_(max=self.capacity - 1)
-        else:
-            self.pos.clamp_(max=self.capacity - 1)
-
-    def _count_prefix_streams(self) -> None:
-        """The store rows one step streams: per workgroup tile of the grouped kernel, the distinct rows among its slots."""
-        gr = int(self.model.ops.attn_group_rows)
-        self.stats["prefix_streams"] += sum(len({r for r in self._slot_row[t:t + gr] if r >= 0}) for t in range(0, self.n_slots, gr))
 
     def _allocate_history(self, n_tokens: int) -> None:
         """Device-resident record of every slot's current job: tokens [S, L] and the f32 logits that produced them [S, L, V]."""
@@ -468,28 +559,6 @@ class DecodePool:
         self.stats["prefill_pad_tokens"] += len(group) * (-(-T // self.PREFILL_PAD) * self.PREFILL_PAD) - sum(lens)
         return logits.to(logits_dtype), tmp
 
-    def _install(self, slot: int, tmp: dict, P: int, row: int = 0, need: int = 0) -> None:
-        m = self.model
-        if self.kv_paged:
-            # the job's reservation: `need` pages off the free list, named in its table row (outside the captured step, like all of this)
-            pages = [self._free_pages.pop() for _ in range(need)]
-            self._slot_pages[slot] = pages
-            ids = torch.tensor(pages, dtype=torch.int64, device=self.device)
-            self.table[slot, :need] = ids.to(torch.int32)
-            self.stats["kv_pages_peak"] = max(self.stats["kv_pages_peak"], self.stats["kv_pages"] - 1 - len(self._free_pages))
-        for i in m.attn_layer_idxs:
-            dst, src = self.ipd["mha"].key_value_memory_dict[i], tmp["mha"].key_value_memory_dict[i]
-            if self.kv_paged:
-                dst.write_tokens_(ids, src[row, :P])                   # the prompt's K/V, from row `row` of the prefill's own cache
-            elif isinstance(dst, Fp8KV):
-                dst.copy_rows_(slot, src, row, P)                        # both tensors of the layer
-            else:
-                dst[slot, :P] = src[row, :P]
-        for i in m.hyena_layer_idxs:
-            self.ipd["hyena"].fir_state_dict[i][slot] = tmp["hyena"].fir_state_dict[i][row]
-            self.ipd["hyena"].state_dict[i][slot] = tmp["hyena"].state_dict[i][row].reshape(
-                self.ipd["hyena"].state_dict[i][slot].shape)
-
     # ------------------------------------------------------------------ one token for every slot
     def _step_eager(self) -> torch.Tensor:
         m, mha = self.model, self.ipd["mha"]
@@ -501,26 +570,31 @@ class DecodePool:
         finally:
             mha.pos_tensor = None
 
-    def _step(self) -> torch.Tensor:
-        """self.ids [S,1] at positions self.pos [S] -> logits [S, V] f32 (every slot, active or not)."""
-        self.stats["steps"] += 1
+    def _captured(self, held, eager):
+        """One step under `use_graph`: `eager` is the step, `held` its captured form (graph, output) or None -> (what the step returned --
+        the eager run's tensor, or the one the replay writes --, the captured form to keep)."""
         with torch.inference_mode():
             if not self.use_graph:
-                return self._step_eager().float()
-            if self._graph is None:
+                return eager(), None
+            if held is None:
                 # The first step runs eagerly (it also warms the library handles and the M = S GEMM choices) and IS the
                 # step: the caches advance in place, so nothing may run twice.  Capture records without executing.
-                first = self._step_eager().float()
+                first = eager()
                 torch.cuda.synchronize(self.device)
                 self.model._row_index(self.n_slots, self.device)
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    out = self._step_eager()
-                self._graph = (g, out)
-                return first
-            g, out = self._graph
-            g.replay()
-            return out.float()
+                    out = eager()
+                return first, (g, out)
+            held[0].replay()
+            return held[1], held
+
+    def _step(self) -> torch.Tensor:
+        """self.ids [S,1] at positions self.pos [S] -> logits [S, V] f32 (every slot, active or not)."""
+        self.stats["steps"] += 1
+        with torch.inference_mode():
+            logits, self._graph = self._captured(self._graph, self._step_eager)
+            return logits.float()
 
     # ------------------------------------------------------------------ the same step with the sampler as its last node
     def _sample_rows(self, logits: torch.Tensor, rows: slice, active) -> None:
@@ -550,7 +624,7 @@ class DecodePool:
         """Per-pool state of the repeat launch: counts [S, M] (4 M bytes per slot; 4 MiB at the cap M = 2^20), window, statistics, levels, the
         armed fraction, and the f32 rows the sampler reads.  A new table size makes new state and drops the captured step."""
         S, dev = self.n_slots, self.device
-        if getattr(self, "s_rep_counts", None) is not None and tuple(self.s_rep_counts.shape) == (S, rc.M):
+        if self.s_rep_counts is not None and tuple(self.s_rep_counts.shape) == (S, rc.M):
             return
         self.s_rep_counts = torch.zeros(S, rc.M, dtype=torch.int32, device=dev)
         self.s_rep_ctx = torch.zeros(S, 2, dtype=torch.int32, device=dev)
@@ -592,6 +666,7 @@ class DecodePool:
                                    self.s_rep_stat[rows], self.s_rep_levels[rows], r["alphabet"], r["k"],
                                    fed_ids=self.ids[rows] if fed else None, **end)
 
+
     def _step_sample_eager(self) -> None:
         if self._ctl is not None:
             logits = self._step_eager()
@@ -601,24 +676,12 @@ class DecodePool:
             self._sample_rows_ctl(logits, slice(0, self.n_slots))
         else:
             self._sample_rows(self._step_eager(), slice(0, self.n_slots), self.s_active)     # bf16 logits, next ids -> self.ids
-        self._advance()
+        self.kv.advance()
 
     def _step_sampled(self) -> None:
         """One token for every active slot, nothing returned to the host: ids, counters and history advance on the device."""
         self.stats["steps"] += 1
-        with torch.inference_mode():
-            if not self.use_graph:
-                return self._step_sample_eager()
-            if self._graph is None:
-                self._step_sample_eager()                             # the first step runs eagerly and IS the step (see _step)
-                torch.cuda.synchronize(self.device)
-                self.model._row_index(self.n_slots, self.device)
-                g = torch.cuda.CUDAGraph()
-                with capture_graph(g):
-                    self._step_sample_eager()
-                self._graph = (g, None)
-                return None
-            self._graph[0].replay()
+        _, self._graph = self._captured(self._graph, self._step_sample_eager)
 
     def _prefill_for(self, pi: int, jobs, slot_job, encoded, cached_prefill: Dict[int, tuple], logits_dtype=torch.float32) -> None:
         """Prompt `pi` needs a prefill: it, and with `prefill_batch` > 1 the prompts admitted with it, land in `cached_prefill` as
@@ -665,161 +728,52 @@ class DecodePool:
         (`last_finish` "repeat", all its tokens kept) once more than that fraction of its generated tokens were repeats.  `last_repeats`:
         one (n_gen, rep) per job -- the generated tokens folded into its counts and the repeats among them; the last token of a job the
         sampler ended is not folded, every token of a job the rule ended is."""
-        if (not isinstance(n_tokens, (int, np.integer)) or stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1
-                or not return_logits or constraints is not None or repeat is not None):
-            return self._generate_ctl(prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                                      stop_frame, return_logits, constraints, repeat)
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+        ctl = (not isinstance(n_tokens, (int, np.integer)) or stop_tokens is not None or stop_sequences is not None or int(stop_frame) != 1
+               or not return_logits or constraints is not None or repeat is not None)
         if hasattr(m, "eval"):
             m.eval()
+        n_spp = int(n_sample_per_prompt)
+        prompts, limits, sampling = self._check_job(prompts, n_tokens, n_spp, prepend_bos, sampling, streams, ctl=ctl)
+        if ctl:
+            return self._generate_ctl(prompts, limits, n_spp, prepend_bos, sampling, streams, stop_tokens, stop_sequences, stop_frame,
+                                      return_logits, constraints, repeat)
         if self._graph_key is not None:                              # the captured step ends with the job-control launch: capture anew
             self._graph, self._graph_key, self._ctl = None, None, None
-        n_tokens = int(n_tokens)
-        if n_tokens < 1 or int(n_sample_per_prompt) < 1:
-            raise ValueError("n_tokens and n_sample_per_prompt must be >= 1")
-        prompts = list(prompts)
         if not prompts:
             return [], [], []
+        encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
+        self.kv.size([e.shape[1] for e in encoded], limits, n_spp)
+        if self.device_sampler:
+            self._allocate_history(limits[0])
+        return self._run("rows" if self.device_sampler else "host", prompts, encoded, limits, n_spp, sampling, streams)
+
+    def _check_job(self, prompts, n_tokens, n_spp: int = 1, prepend_bos: bool = False, sampling=None, streams=None, ctl: bool = False,
+                   beam: bool = False):
+        """The one validation of a call's jobs, before any device work -> (prompts as a list, one limit per prompt, `sampling` as a list).
+        `ctl`: the job-control path (its sampler is the device's whatever the pool's own is); `beam`: beam_search (an empty list is an
+        error there, and there is no n_sample_per_prompt to name)."""
+        prompts = list(prompts)
+        one = isinstance(n_tokens, (int, np.integer))
+        limits = [int(n_tokens)] * len(prompts) if one else [int(n) for n in n_tokens]
+        if len(limits) != len(prompts):
+            raise ValueError("n_tokens: one limit, or one per prompt")
+        if (one and int(n_tokens) < 1) or any(n < 1 for n in limits) or n_spp < 1:
+            raise ValueError("n_tokens must be >= 1" if beam else "n_tokens and n_sample_per_prompt must be >= 1")
+        if beam and not prompts:
+            raise ValueError("beam_search: the prompt list is empty")
         if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
             raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
-        encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
-        if sampling is not None:
-            if not self.device_sampler:
+        device = self.device_sampler or ctl
+        if sampling is not None and prompts:
+            if not device:
                 raise ValueError("per-prompt sampling settings need the device sampler (give the pool a seed)")
             sampling = list(sampling)
             if len(sampling) != len(prompts) or any(d is not None and set(d) - {"top_k", "top_p", "temperature"} for d in sampling):
                 raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
-        if streams is not None and (not self.device_sampler or len(streams) != len(prompts) * int(n_sample_per_prompt)):
-            raise ValueError("streams: one id per output, and only with the device sampler")
-        need_of = [0] * len(prompts)
-        if self.share_prompt_kv:
-            self._allocate_shared(max(e.shape[1] for e in encoded), n_tokens, int(n_sample_per_prompt))
-        elif self.kv_paged:
-            need_of = [self._page_need(e.shape[1] + n_tokens) for e in encoded]
-            self._allocate_paged([n for n in need_of for _ in range(int(n_sample_per_prompt))])
-        else:
-            self._allocate(max(e.shape[1] for e in encoded) + n_tokens)
-        if self.device_sampler:
-            self._allocate_history(n_tokens)
-        # job = (output index, prompt index); the copies of one prompt are adjacent so that they share a prefill
-        jobs = deque((pi * n_sample_per_prompt + c, pi) for pi in range(len(prompts)) for c in range(n_sample_per_prompt))
-        n_jobs = len(jobs)
-        out_ids = torch.zeros(n_jobs, n_tokens, dtype=torch.long)
-        out_logits = torch.zeros(n_jobs, n_tokens, m.vocab_size, dtype=torch.float32)
-        slot_job: List[Optional[int]] = [None] * S
-        slot_n = [0] * S
-        cached_prefill: Dict[int, tuple] = {}
-
-        def fill(slot: int) -> None:
-            j, pi = jobs.popleft()
-            if pi not in cached_prefill:
-                self._prefill_for(pi, jobs, slot_job, encoded, cached_prefill)
-            last_logits, tmp, row = cached_prefill[pi]
-            P = encoded[pi].shape[1]
-            kw = {"row": row} if row else {}                         # (row 0 of a B = 1 prefill: the call as it always was)
-            if self.kv_paged:
-                kw["need"] = need_of[pi]
-            if self.share_prompt_kv:
-                self._install_shared(slot, pi, tmp, P, **kw)
-            else:
-                self._install(slot, tmp, P, **kw)
-            if self.device_sampler:
-                # the job's settings and its own random stream (its output index); the first token is draw 0 of that stream,
-                # taken by the same kernel from the prefill's last logits
-                cfg = (sampling[pi] if sampling is not None else None) or {}
-                self.s_top_k[slot] = int(cfg.get("top_k", self.top_k))
-                self.s_top_p[slot] = float(cfg.get("top_p", self.top_p))
-                self.s_temperature[slot] = float(cfg.get("temperature", self.temperature))
-                self.s_stream[slot] = j if streams is None else int(streams[j])
-                self.s_count[slot] = 0
-                self.s_active[slot] = True
-                self._sample_rows(last_logits[None], slice(slot, slot + 1), None)
-                self.pos[slot] = P
-                slot_job[slot], slot_n[slot] = j, 1
-                return
-            first = sample(last_logits[None], top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
-            out_ids[j, 0] = int(first[0])
-            out_logits[j, 0] = last_logits.cpu()
-            self.ids[slot, 0] = first[0]
-            self.pos[slot] = P                                        # the sampled token sits at position P
-            slot_job[slot], slot_n[slot] = j, 1
-
-        def fetch(slots: List[int]) -> None:
-            """Finished slots: their history rows leave the device (the only read-back of the device sampler), the slots go idle."""
-            idx = torch.tensor(slots, dtype=torch.int64, device=dev)
-            self.s_active[idx] = False
-            if self.share_prompt_kv:
-                self._release_shared(slots)
-            self._release_pages(slots)
-            ids_cpu, lg_cpu = self.hist_ids[idx, :n_tokens].cpu(), self.hist_logits[idx, :n_tokens].cpu()
-            for r, s in enumerate(slots):
-                out_ids[slot_job[s]], out_logits[slot_job[s]] = ids_cpu[r], lg_cpu[r]
-                slot_job[s] = None
-
-        done = 0
-        while done < n_jobs:
-            waiting = 0                                               # kv_paged: free slots the head of the queue could not take (FIFO)
-            for s in range(S):
-                if slot_job[s] is None and jobs:
-                    if waiting or not self._can_admit(need_of[jobs[0][1]]):
-                        waiting += 1
-                        continue
-                    fill(s)
-                    if n_tokens == 1:
-                        if self.device_sampler:
-                            fetch([s])
-                        else:
-                            if self.share_prompt_kv:
-                                self._release_shared([s])
-                            self._release_pages([s])
-                        slot_job[s] = None
-                        done += 1
-            active = [s for s in range(S) if slot_job[s] is not None]
-            if not active:
-                continue
-            if waiting:
-                self.stats["kv_page_waits"] += waiting
-            if self.share_prompt_kv:
-                self._count_prefix_streams()
-            if self.device_sampler:
-                self._step_sampled()
-                for s in active:
-                    slot_n[s] += 1
-                self.stats["tokens"] += len(active)
-                finished = [s for s in active if slot_n[s] == n_tokens]   # a job's length is fixed: the host knows without reading
-                if finished:
-                    fetch(finished)
-                    done += len(finished)
-                continue
-            logits = self._step()                                     # [S, V]
-            nxt = sample(logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
-            lg_cpu, nxt_cpu = logits.cpu(), nxt.cpu()
-            self.ids[:, 0] = nxt
-            self._advance()
-            ended = []
-            for s in active:
-                j, k = slot_job[s], slot_n[s]
-                out_ids[j, k] = nxt_cpu[s]
-                out_logits[j, k] = lg_cpu[s]
-                slot_n[s] = k + 1
-                self.stats["tokens"] += 1
-                if k + 1 == n_tokens:
-                    slot_job[s] = None
-                    ended.append(s)
-                    done += 1
-            if ended and self.share_prompt_kv:
-                self._release_shared(ended)
-            if ended:
-                self._release_pages(ended)
-
-        self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
-        for name in ("last_lengths", "last_finish", "last_logprobs", "last_repeats"):    # (an earlier job-control run's: they would describe that run)
-            self.__dict__.pop(name, None)
-        seqs = list(tok.detokenize_batch(out_ids))
-        lp = logits_to_logprobs(out_logits, out_ids).float().numpy()   # the reference's shifted pairing
-        scores = [float(np.mean(lp[j])) for j in range(n_jobs)]
-        owner = [pi for pi in range(len(prompts)) for _ in range(n_sample_per_prompt)]
-        return seqs, scores, owner
+        if streams is not None and prompts and (not device or len(streams) != len(prompts) * n_spp):
+            raise ValueError("streams: one id per output" + ("" if ctl else ", and only with the device sampler"))
+        return prompts, limits, sampling
 
 
     # ------------------------------------------------------------------ the job, with jobs that end on their own (DESIGN.md section 19)
@@ -865,32 +819,21 @@ class DecodePool:
             offsets[id(c)] = total
             total += c.n_states
         table = torch.from_numpy(np.concatenate([c.table for c in distinct]).astype(np.int32))
-        if getattr(self, "s_dfa_next", None) is None or tuple(self.s_dfa_next.shape) != tuple(table.shape):
+        if self.s_dfa_next is None or tuple(self.s_dfa_next.shape) != tuple(table.shape):
             self.s_dfa_next = table.to(self.device)
         else:
             self.s_dfa_next.copy_(table)
         bases = [-1 if c is None else offsets[id(c)] for c in per]
         return {"alphabet": torch.tensor(distinct[0].alphabet, dtype=torch.int32), "next": self.s_dfa_next}, bases
 
-    def _generate_ctl(self, prompts, n_tokens, n_sample_per_prompt, prepend_bos, sampling, streams, stop_tokens, stop_sequences,
-                      stop_frame, return_logits, constraints=None, repeat=None):
+
+    def _generate_ctl(self, prompts, limits, n_spp, prepend_bos, sampling, streams, stop_tokens, stop_sequences, stop_frame, return_logits,
+                      constraints=None, repeat=None):
         """`generate` on the job-control path: the sampler launch (`evo_sample_rows_ctl_f32`) ends a row's job on the device.  The host
         knows the step by which a slot MUST have finished (its limit) and, with a stop rule, reads the [S] lengths every `poll_every`
         steps to learn which slots finished sooner; a finished slot's history rows [:length] are fetched, its store row released, the
-        slot re-filled."""
+        slot re-filled.  Here: the rule is checked and copied into the per-pool state the captured launch reads; _run does the rest."""
         m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
-        if hasattr(m, "eval"):
-            m.eval()
-        n_spp = int(n_sample_per_prompt)
-        prompts = list(prompts)
-        if isinstance(n_tokens, (int, np.integer)):
-            limits = [int(n_tokens)] * len(prompts)
-        else:
-            limits = [int(n) for n in n_tokens]
-            if len(limits) != len(prompts):
-                raise ValueError("n_tokens: one limit, or one per prompt")
-        if any(n < 1 for n in limits) or n_spp < 1:
-            raise ValueError("n_tokens and n_sample_per_prompt must be >= 1")
         if int(stop_frame) < 1:
             raise ValueError("stop_frame must be >= 1")
         patterns = stop_patterns(tok, stop_sequences)
@@ -904,8 +847,6 @@ class DecodePool:
                 raise ValueError("stop_sequences: a pattern with a token outside allowed_tokens could never be drawn")
         if not prompts:
             return [], [], []
-        if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
-            raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
         if not hasattr(m.ops, "sample_rows_ctl"):
             raise RuntimeError("stop rules and per-prompt lengths need a compute backend with sample_rows_ctl; this model's backend has none")
         per_prompt, distinct = self._constraints_of(constraints, len(prompts)) if constraints is not None else (None, [])
@@ -920,27 +861,16 @@ class DecodePool:
                 raise RuntimeError('repeat needs a compute backend with the "repeat" kernels (' + ", ".join(Backend.OPTIONAL["repeat"])
                                    + "); this model's backend has none")
         encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
-        if sampling is not None:
-            sampling = list(sampling)
-            if len(sampling) != len(prompts) or any(d is not None and set(d) - {"top_k", "top_p", "temperature"} for d in sampling):
-                raise ValueError("sampling: one dict of top_k / top_p / temperature (or None) per prompt")
-        if streams is not None and len(streams) != len(prompts) * n_spp:
-            raise ValueError("streams: one id per output")
         has_stop = stop_set is not None or bool(patterns) or bool(distinct)      # (a job may end by completing its constraint: the host polls)
         has_stop = has_stop or (rc is not None and rc.end_num > 0)   # (... or by the repeat rule)
-        L = max(limits)
         was_device = self.device_sampler
         self.device_sampler = True                                   # (as with allowed_tokens alone: no seed means seed 0)
         try:
-            if self.share_prompt_kv:
-                self._allocate_shared(max(e.shape[1] for e in encoded), L, n_spp, rows=min(S, len(prompts)))
-            elif self.kv_paged:                                      # a job reserves to its OWN limit
-                self._allocate_paged([self._page_need(e.shape[1] + n) for e, n in zip(encoded, limits) for _ in range(n_spp)])
-            else:
-                self._allocate(max(e.shape[1] for e in encoded) + L)
-            if not hasattr(self, "s_limit"):
+            # jobs of unequal length: a store row per live slot, or one per prompt (a layout without a store sizes itself from the limits)
+            self.kv.size([e.shape[1] for e in encoded], limits, n_spp, rows=min(S, len(prompts)))
+            if self.s_limit is None:
                 self._allocate_sampler_state()
-            self._allocate_history_ctl(L, return_logits)
+            self._allocate_history_ctl(max(limits), return_logits)
             # everything the captured launch reads by address is per-pool state; the rule is copied INTO it.  What travels by value --
             # the patterns, the frame, whether there is a stop mask at all -- is the key the captured step is kept under
             if stop_set is not None:
@@ -962,21 +892,28 @@ class DecodePool:
             for name in ("stop_ends", "length_ends", "polls", "idle_slot_steps") + (("constraint_ends",) if distinct else ()) \
                     + (("repeat_ends",) if rc is not None else ()):
                 self.stats.setdefault(name, 0)
-            return self._run_ctl(prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, bases, rc)
+            return self._run("ctl", prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, bases, rc)
         finally:
             self.device_sampler = was_device
 
-    def _run_ctl(self, prompts, encoded, limits, n_spp, sampling, streams, has_stop, return_logits, dfa_bases=None, rc=None):
-        m, tok, S, dev = self.model, self.tok, self.n_slots, self.device
+    def _run(self, mode, prompts, encoded, limits, n_spp, sampling, streams, has_stop=False, return_logits=True, dfa_bases=None, rc=None):
+        """The one scheduling loop of generate(): admit (FIFO; fill = prefill lookup, install, sampler settings, first token), step, look
+        (who finished), fetch (results out, slots released).  `mode` supplies what a step is, the first token and what fetch copies out:
+        "host" (the reference's sampler on logits read back every step), "rows" (`sample_rows`, every job `limits[0]` tokens long) or
+        "ctl" (`sample_rows_ctl` / `_dfa`, with the repeat launch in front when `rc`); only "ctl" under a stop rule reads the device to
+        learn who finished."""
+        m, tok, S, dev, kv = self.model, self.tok, self.n_slots, self.device, self.kv
+        host, ctl = mode == "host", mode == "ctl"
         rep_init: Dict[int, tuple] = {}                              # repeat control: a prompt's starting state, shared by its copies
         if rc is not None:                                           # one RepeatControl per call: every slot's levels and fraction
             self.s_rep_levels.copy_(rc.levels.to(dev)[None, :].expand(S, 8))
             self.s_rep_end.fill_(rc.end_num)
         L = max(limits)
+        # job = (output index, prompt index); the copies of one prompt are adjacent so that they share a prefill
         jobs = deque((pi * n_spp + c, pi) for pi in range(len(prompts)) for c in range(n_spp))
         n_jobs = len(jobs)
-        out_ids = torch.full((n_jobs, L), -1, dtype=torch.long)
-        out_logprobs = torch.zeros(n_jobs, L, dtype=torch.float32)
+        out_ids = torch.full((n_jobs, L), -1 if ctl else 0, dtype=torch.long)
+        out_logprobs = torch.zeros(n_jobs, L, dtype=torch.float32) if ctl else None
         out_logits = torch.zeros(n_jobs, L, m.vocab_size, dtype=torch.float32) if return_logits else None
         out_len, out_fin = [0] * n_jobs, [0] * n_jobs
         out_rep: List[Tuple[int, int]] = [(0, 0)] * n_jobs
@@ -984,27 +921,20 @@ class DecodePool:
         slot_n = [0] * S                                             # tokens the slot's job has if it is still running
         slot_limit = [0] * S
         cached_prefill: Dict[int, tuple] = {}
-        need_of = [self._page_need(e.shape[1] + n) for e, n in zip(encoded, limits)] if self.kv_paged else [0] * len(prompts)
+        need_of = [kv.need(e.shape[1] + n) for e, n in zip(encoded, limits)]
 
-        def fill(slot: int) -> None:
-            j, pi = jobs.popleft()
-            if pi not in cached_prefill:
-                self._prefill_for(pi, jobs, slot_job, encoded, cached_prefill)
-            last_logits, tmp, row = cached_prefill[pi]
-            P = encoded[pi].shape[1]
-            kw = {"row": row} if row else {}
-            if self.kv_paged:
-                kw["need"] = need_of[pi]
-            if self.share_prompt_kv:
-                self._install_shared(slot, pi, tmp, P, **kw)
-            else:
-                self._install(slot, tmp, P, **kw)
-            cfg = (sampling[pi] if sampling is not None else None) or {}
-            self.s_top_k[slot] = int(cfg.get("top_k", self.top_k))
-            self.s_top_p[slot] = float(cfg.get("top_p", self.top_p))
-            self.s_temperature[slot] = float(cfg.get("temperature", self.temperature))
-            self.s_stream[slot] = j if streams is None else int(streams[j])
-            self.s_count[slot] = 0
+        # ---- what a mode supplies: the first token (from the prefill's last logits), a step, what fetch copies out
+        def first_host(slot: int, j: int, pi: int, last_logits) -> None:
+            first = sample(last_logits[None], top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
+            out_ids[j, 0] = int(first[0])
+            out_logits[j, 0] = last_logits.cpu()
+            self.ids[slot, 0] = first[0]
+
+        def first_rows(slot: int, j: int, pi: int, last_logits) -> None:
+            self.s_active[slot] = True
+            self._sample_rows(last_logits[None], slice(slot, slot + 1), None)
+
+        def first_ctl(slot: int, j: int, pi: int, last_logits) -> None:
             self.s_limit[slot] = limits[pi]
             self.s_length[slot] = -1
             self.s_finish[slot] = 0
@@ -1021,16 +951,27 @@ class DecodePool:
                 self._repeat_rows(last_logits[None], slice(slot, slot + 1), fed=False)
                 last_logits = self.s_rep_logits[slot]
             self._sample_rows_ctl(last_logits[None], slice(slot, slot + 1))      # the first token; with limit 1 (or a stop) also the last
-            self.pos[slot] = P
-            slot_job[slot], slot_n[slot], slot_limit[slot] = j, 1, limits[pi]
 
-        def fetch(slots: List[int], lengths: Optional[List[int]]) -> None:
-            """Finished slots: rows [:length] of their histories leave the device, the slots go idle.  `lengths` None: every one of them
-            ran to its limit (no stop rule: nothing to ask the device)."""
-            idx = torch.tensor(slots, dtype=torch.int64, device=dev)
-            if self.share_prompt_kv:
-                self._release_shared(slots)
-            self._release_pages(slots)
+        def step_host(active: List[int]) -> None:
+            logits = self._step()                                     # [S, V]
+            nxt = sample(logits, top_k=self.top_k, top_p=self.top_p, temperature=self.temperature)
+            lg_cpu, nxt_cpu = logits.cpu(), nxt.cpu()
+            self.ids[:, 0] = nxt
+            kv.advance()
+            for s in active:
+                out_ids[slot_job[s], slot_n[s]] = nxt_cpu[s]
+                out_logits[slot_job[s], slot_n[s]] = lg_cpu[s]
+
+        def collect_rows(slots: List[int], idx, lengths) -> None:
+            """Their history rows leave the device (the only read-back of the device sampler)."""
+            self.s_active[idx] = False
+            ids_cpu, lg_cpu = self.hist_ids[idx, :L].cpu(), self.hist_logits[idx, :L].cpu()
+            for r, s in enumerate(slots):
+                out_ids[slot_job[s]], out_logits[slot_job[s]] = ids_cpu[r], lg_cpu[r]
+
+        def collect_ctl(slots: List[int], idx, lengths) -> None:
+            """Rows [:length] of their histories leave the device.  `lengths` None: every one of them ran to its limit (no stop rule:
+            nothing to ask the device)."""
             if lengths is None:
                 lengths, fins = [slot_limit[s] for s in slots], [FINISH_LENGTH] * len(slots)
             else:
@@ -1052,6 +993,37 @@ class DecodePool:
                 self.stats[{FINISH_LENGTH: "length_ends", FINISH_CONSTRAINT: "constraint_ends", FINISH_REPEAT: "repeat_ends"}.get(fins[r], "stop_ends")] += 1
                 self.stats["idle_slot_steps"] += slot_n[s] - n
                 self.stats["tokens"] -= slot_n[s] - n                # (steps a finished slot sat through generate nothing)
+
+        first, step, collect = {"host": (first_host, step_host, None), "rows": (first_rows, lambda active: self._step_sampled(), collect_rows),
+                                "ctl": (first_ctl, lambda active: self._step_sampled(), collect_ctl)}[mode]
+
+        def fill(slot: int) -> None:
+            j, pi = jobs.popleft()
+            if pi not in cached_prefill:
+                self._prefill_for(pi, jobs, slot_job, encoded, cached_prefill)
+            last_logits, tmp, row = cached_prefill[pi]
+            P = encoded[pi].shape[1]
+            # (row 0 of a B = 1 prefill, nothing to reserve: the call as it always was)
+            kv.install(slot, pi, tmp, P, **{k: v for k, v in (("row", row), ("need", need_of[pi])) if v})
+            if not host:
+                # the job's settings and its own random stream (its output index); the first token is draw 0 of that stream,
+                # taken by the same kernel from the prefill's last logits
+                cfg = (sampling[pi] if sampling is not None else None) or {}
+                self.s_top_k[slot] = int(cfg.get("top_k", self.top_k))
+                self.s_top_p[slot] = float(cfg.get("top_p", self.top_p))
+                self.s_temperature[slot] = float(cfg.get("temperature", self.temperature))
+                self.s_stream[slot] = j if streams is None else int(streams[j])
+                self.s_count[slot] = 0
+            first(slot, j, pi, last_logits)
+            self.pos[slot] = P                                        # the sampled token sits at position P
+            slot_job[slot], slot_n[slot], slot_limit[slot] = j, 1, limits[pi]
+
+        def fetch(slots: List[int], lengths: Optional[List[int]]) -> None:
+            """Finished slots: the layout takes back what they held, their results leave the device, the slots go idle."""
+            kv.release(slots)
+            if collect is not None:
+                collect(slots, torch.tensor(slots, dtype=torch.int64, device=dev), lengths)
+            for s in slots:
                 slot_job[s] = None
 
         done, since_poll = 0, 0
@@ -1059,7 +1031,7 @@ class DecodePool:
             filled, waiting = False, 0
             for s in range(S):
                 if slot_job[s] is None and jobs:
-                    if waiting or not self._can_admit(need_of[jobs[0][1]]):   # kv_paged: the head of the queue waits for pages (FIFO)
+                    if waiting or not kv.can_admit(need_of[jobs[0][1]]):     # the head of the queue waits for what it reserves (FIFO)
                         waiting += 1
                         continue
                     fill(s)
@@ -1079,7 +1051,7 @@ class DecodePool:
                     self._count_prefix_streams()
                 if waiting:
                     self.stats["kv_page_waits"] += waiting
-                self._step_sampled()
+                step(active)
                 since_poll += 1
                 for s in active:
                     slot_n[s] += 1
@@ -1104,9 +1076,14 @@ class DecodePool:
                 fetch(finished, lengths)
                 done += len(finished)
 
-        self.last_ids, self.last_logits, self.last_logprobs = out_ids, out_logits, out_logprobs
-        self.last_lengths, self.last_finish = list(out_len), [FINISH_NAMES_REPEAT[f] for f in out_fin]
-        self.__dict__.pop("last_repeats", None)
+        owner = [pi for pi in range(len(prompts)) for _ in range(n_spp)]
+        self.last_ids, self.last_logits = out_ids, out_logits        # (kept for inspection / tests)
+        for name in ("last_lengths", "last_finish", "last_logprobs", "last_repeats"):    # (an earlier job-control run's: they would describe that run)
+            self.__dict__.pop(name, None)
+        if not ctl:
+            lp = logits_to_logprobs(out_logits, out_ids).float().numpy()   # the reference's shifted pairing
+            return list(tok.detokenize_batch(out_ids)), [float(np.mean(lp[j])) for j in range(n_jobs)], owner
+        self.last_logprobs, self.last_lengths, self.last_finish = out_logprobs, list(out_len), [FINISH_NAMES_REPEAT[f] for f in out_fin]
         if rc is not None:
             self.last_repeats = list(out_rep)
         seqs, scores = [], []
@@ -1114,7 +1091,6 @@ class DecodePool:
             n = out_len[j] - (1 if out_fin[j] == FINISH_STOP_TOKEN else 0)      # a stop token is trimmed, a stop sequence stays
             seqs.append(tok.detokenize(out_ids[j, :n].tolist()))
             scores.append(float(np.mean(out_logprobs[j, :out_len[j]].numpy().astype(np.float64))))
-        owner = [pi for pi in range(len(prompts)) for _ in range(n_spp)]
         return seqs, scores, owner
 
 
@@ -1161,24 +1137,12 @@ class DecodePool:
         b = self._beam
         self._beam_select(self._step_eager(), b["active"])
         self.model.ops.gather_rows(b["table"], b["parent"], self.store.own_pos)
-        self._advance()
+        self.kv.advance()
 
     def _step_beam(self) -> None:
         self.stats["steps"] += 1
         self.stats["beam_steps"] += 1
-        with torch.inference_mode():
-            if not self.use_graph:
-                return self._step_beam_eager()
-            if self._beam_graph is None:
-                self._step_beam_eager()                               # the first step runs eagerly and IS the step (see _step)
-                torch.cuda.synchronize(self.device)
-                self.model._row_index(self.n_slots, self.device)
-                g = torch.cuda.CUDAGraph()
-                with capture_graph(g):
-                    self._step_beam_eager()
-                self._beam_graph = g
-                return None
-            self._beam_graph.replay()
+        _, self._beam_graph = self._captured(self._beam_graph, self._step_beam_eager)
 
     def beam_search(self, prompts: Sequence[str], n_tokens: int, beam_width: int = 4, stop_tokens=None, prepend_bos: bool = False,
                     return_steps: bool = False, **refused) -> List["BeamResult"]:
@@ -1206,13 +1170,7 @@ class DecodePool:
         if self.kv_dtype != "bf16" or self.kv_paged:                 # (such a pool cannot be built with share_prompt_kv; kept for the day it can)
             raise ValueError('beam_search does not combine with kv_dtype="fp8" or kv_paged=True')
         n_tokens = int(n_tokens)
-        if n_tokens < 1:
-            raise ValueError("n_tokens must be >= 1")
-        prompts = list(prompts)
-        if not prompts:
-            raise ValueError("beam_search: the prompt list is empty")
-        if any((not isinstance(p, str)) or (len(p) == 0 and not prepend_bos) for p in prompts):
-            raise ValueError("every prompt must be a non-empty string (or use prepend_bos=True)")
+        prompts, limits, _ = self._check_job(prompts, n_tokens, prepend_bos=prepend_bos, beam=True)
         stop_set = None
         if stop_tokens is not None and len(stop_tokens):
             stop_set = allowed_mask(tok, stop_tokens)
@@ -1222,19 +1180,13 @@ class DecodePool:
         if hasattr(m, "eval"):
             m.eval()
         encoded = [prepare_batch([p], tok, prepend_bos=prepend_bos, device=str(dev))[0] for p in prompts]
-        G = S // W
-        self._allocate_shared(max(e.shape[1] for e in encoded), n_tokens, W, rows=min(G, len(prompts)))
+        self.kv.size([e.shape[1] for e in encoded], limits, W, rows=min(S // W, len(prompts)))     # one store row per group
         b = self._allocate_beam(W, n_tokens, stop_set is not None)
         if stop_set is not None:
             b["stop"].copy_(m.ops.pack_allow_mask(stop_set, dev))
         for name in ("beam_groups", "beam_steps", "beam_rows_moved", "polls"):
             self.stats.setdefault(name, 0)
-        was = self.ipd["mha"].weight_dtype
-        self.ipd["mha"].weight_dtype = self.weight_dtype             # (the steps; a prefill runs on a cache of its own and reads bf16 weights)
-        try:
-            return self._run_beam(prompts, encoded, n_tokens, stop_set, return_steps)
-        finally:
-            self.ipd["mha"].weight_dtype = was
+        return self._run_beam(prompts, encoded, n_tokens, stop_set, return_steps)
 
     def _run_beam(self, prompts, encoded, n_tokens, stop_set, return_steps):
         m, tok, S, dev, b = self.model, self.tok, self.n_slots, self.device, self._beam
@@ -1254,7 +1206,7 @@ class DecodePool:
             P = encoded[pi].shape[1]
             rows = slice(g * W, g * W + W)
             for s in range(g * W, g * W + W):                        # one store row; every slot of the group holds the prompt's states
-                self._install_shared(s, pi, tmp, P, **({"row": row} if row else {}))
+                self.kv.install(s, pi, tmp, P, **({"row": row} if row else {}))
             b["cum"][rows] = neg_inf
             b["cum"][g * W] = 0.0
             b["ended"][rows] = 0
@@ -1276,7 +1228,7 @@ class DecodePool:
             """Finished groups: their back-pointers and final state leave the device; the hypotheses are rebuilt on the host."""
             slots = [s for g in groups for s in range(g * W, g * W + W)]
             idx = torch.tensor(slots, dtype=torch.int64, device=dev)
-            self._release_shared(slots)
+            self.kv.release(slots)
             b["active"][torch.tensor(groups, dtype=torch.int64, device=dev)] = 0
             T = max(min(group_n[g], n_tokens) for g in groups)
             hp, hi, hc = b["hist_parent"][idx, :T].cpu(), b["hist_ids"][idx, :T].cpu(), b["hist_cum"][idx, :T].cpu()
@@ -1404,3 +1356,4 @@ def sample_many(prompts: Sequence[str], model, tokenizer, n_tokens: int = 1000, 
     seqs, scores, owner = pool.generate(prompts, n_tokens=n_tokens, n_sample_per_prompt=n_sample_per_prompt,
                                         prepend_bos=prepend_bos, **ctl)
     return [prompts[i] for i in owner], seqs, scores
+

@@ -187,15 +187,51 @@ def _variants():
     return [vs.score, vs.delta]
 
 
-def _pool(**kw):
+def _pool(gen=None, seed=5, which="SMALL", **kw):
+    """A 4-slot pool on SMALL (or `which`), every step eager: PROMPTS[0] and PROMPTS[2], 2 copies, 4 tokens -- the smallest job that re-fills a slot.
+    `gen`: arguments of generate() (they replace the defaults); `kw`: arguments of the pool."""
     def run():
         from evo_amd.pool import DecodePool
         from evo_amd.tokenizer import CharLevelTokenizer
         from test_gpu_pool import PROMPTS
-        pool = DecodePool(model("SMALL"), CharLevelTokenizer(512), n_slots=4, device=DEV, use_graph=False, seed=5, **kw)
-        pool.generate([PROMPTS[0], PROMPTS[2]], n_tokens=4, n_sample_per_prompt=2)
-        return [pool.last_ids, pool.last_logits]
+        pool = DecodePool(model(which), CharLevelTokenizer(512), n_slots=4, device=DEV, use_graph=False, seed=seed, **kw)
+        pool.generate([PROMPTS[0], PROMPTS[2]], **dict(dict(n_tokens=4, n_sample_per_prompt=2), **(gen or {})))
+        out = [pool.last_ids] + ([] if pool.last_logits is None else [pool.last_logits])
+        if hasattr(pool, "last_lengths"):                        # a job-control run
+            out += [pool.last_logprobs, np.array(pool.last_lengths, dtype=np.int64)]
+        return out
     return run
+
+
+def _job_control():
+    """Jobs that end on their own: one limit per prompt, the three stop codons in frame, ACGT only, no logits kept, a look every 2 steps."""
+    return dict(gen=dict(n_tokens=[4, 2], stop_sequences=["TAA", "TAG", "TGA"], stop_frame=3, return_logits=False),
+                allowed_tokens="ACGT", poll_every=2)
+
+
+def _pool_constrained():
+    from evo_amd.constraints import iupac_template
+    return _pool(gen=dict(constraints=[iupac_template("ANR"), None]), allowed_tokens="ACGT")()
+
+
+def _pool_repeat():
+    from evo_amd.sh.sample import RepeatControl
+    return _pool(gen=dict(repeat=RepeatControl(k=3, penalty=0.5, end_fraction=0.25, end_min_tokens=2)), allowed_tokens="ACGT")()
+
+
+def _pool_w8():
+    model("SMALL")._w8 = None                                # the FP8 copies are quantised inside the scenario, whichever ran before it
+    return _pool(weight_dtype="fp8")()
+
+
+def _beam():
+    from evo_amd.pool import DecodePool
+    from evo_amd.tokenizer import CharLevelTokenizer
+    from test_gpu_pool import PROMPTS
+    pool = DecodePool(model("SMALL"), CharLevelTokenizer(512), n_slots=4, device=DEV, use_graph=False, share_prompt_kv=True,
+                      allowed_tokens="ACGT")
+    res = pool.beam_search([PROMPTS[0], PROMPTS[2]], 4, beam_width=2, stop_tokens="T", return_steps=True)
+    return [t for r in res for t in r.steps] + [np.array([r.scores for r in res], dtype=np.float64)]
 
 
 def _embeddings():
@@ -236,6 +272,19 @@ SCENARIOS = {
     "score_variants 700 nt, 3 substitutions": _variants,
     "pool 2x2, 4 slots, shared prompt K/V, prefill_batch=2": _pool(share_prompt_kv=True, prefill_batch=2),
     "pool 2x2, 4 slots, defaults": _pool(),
+    # the pool's scheduler, one scenario per path through it (pinned before evo_amd/pool.py was restructured)
+    "pool 2x2, 4 slots, host sampler, greedy": _pool(seed=None, top_k=1),
+    "pool 2x2, 4 slots, job control: limits [4, 2], stop codons in frame 3, ACGT, no logits, poll_every=2": _pool(**_job_control()),
+    "pool 2x2, 4 slots, job control on shared prompt K/V (store rows per prompt)": _pool(share_prompt_kv=True, **_job_control()),
+    "pool 2x2, 4 slots, one IUPAC template and one free prompt": _pool_constrained,
+    "pool 2x2, 4 slots, repeat control k=3 with end_fraction": _pool_repeat,
+    "pool 2x2, 4 slots, kv_dtype=fp8": _pool(kv_dtype="fp8"),
+    "pool 2x2, 4 slots, weight_dtype=fp8": _pool_w8,
+    "pool 2x2, 4 slots, kv_paged, 64-token pages, budget 7 pages (the head waits)": _pool(kv_paged=True, kv_page_tokens=64, kv_budget_tokens=448),
+    "pool 2x2, 4 slots, batch_invariant (SMALL4: the row-invariant gate needs I % 32 == 0)": _pool(which="SMALL4", batch_invariant=True),
+    "pool 2x2, 4 slots, n_tokens=1": _pool(gen=dict(n_tokens=1)),
+    "pool 2x2, 4 slots, n_tokens=1, host sampler": _pool(seed=None, top_k=1, gen=dict(n_tokens=1)),
+    "pool beam_search width 2, 4 slots, stop token T": _beam,
     "embeddings [1, final] mean 2x300": _embeddings,
     **{f"sp rank {r} of 2, 2x2050, attn {mode}": _sp("SMALL4", 2, 2050, r, mode) for r in (0, 1) for mode in ("auto", "allgather")},
     **{f"sp rank {r} of 2, 2x60 modal stages": _sp("SMALL", 2, 60, r, "auto") for r in (0, 1)},

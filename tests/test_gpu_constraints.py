@@ -365,7 +365,7 @@ def result(pool, out):
                            last_logprobs=getattr(pool, "last_logprobs", None), last_lengths=getattr(pool, "last_lengths", None),
                            last_finish=getattr(pool, "last_finish", None), stats=dict(pool.stats), captured=pool._graph is not None,
                            kept_logits=pool.hist_logits is not None, idle=not bool(pool.s_active.any()),
-                           table_shape=tuple(pool.s_dfa_next.shape) if hasattr(pool, "s_dfa_next") else None,
+                           table_shape=tuple(pool.s_dfa_next.shape) if pool.s_dfa_next is not None else None,
                            store=(list(pool.store_refs), pool.store.row.tolist()) if pool.store is not None else None)
 
 

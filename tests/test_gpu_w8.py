@@ -448,11 +448,8 @@ THREE = [PROMPTS[0], PROMPTS[1], PROMPTS[4]]
 @pytest.mark.parametrize("dims", ["toy", "d4096"])
 def test_pool_logits_vs_the_fp64_oracle_on_the_dequantised_weights(dims):
     """3 streams x 24 tokens; row 23's rule as tests/test_gpu_fanout_pool.py:65 applies it; captured step = eager step, bit for bit."""
-    from evo_amd.scoring import prepare_batch
     cfg, sd, m = _twin(dims)
     odev = None if dims == "toy" else DEV
-    osd = sd if odev is None else {k: v.to(DEV) for k, v in sd.items()}
-    oracle, oracle_bf16 = R.RefStripedHyena(cfg, osd, "fp64", device=odev), R.RefStripedHyena(cfg, osd, "bf16", device=odev)
     runs = {}
     for graph in (True, False):
         pool = _pool(m, use_graph=graph, seed=11, weight_dtype="fp8")
@@ -460,19 +457,50 @@ def test_pool_logits_vs_the_fp64_oracle_on_the_dequantised_weights(dims):
         assert pool.stats["weight_dtype"] == "fp8" and pool.stats["decode_weight_bytes"] == m.decode_weight_bytes("fp8")
         runs[graph] = (pool.last_ids.clone(), pool.last_logits.clone())
     assert torch.equal(runs[True][0], runs[False][0]) and torch.equal(runs[True][1], runs[False][1])
+    _assert_logits_vs_oracle(f"w8 pool {dims}", cfg, sd, odev, *runs[True])
+
+
+def _assert_logits_vs_oracle(what, cfg, sd, odev, last_ids, last_logits):
+    """The recorded logits of a THREE x N_TOK run against the fp64 oracle on the (dequantised) state dict: the file's criterion."""
+    from evo_amd.scoring import prepare_batch
+    osd = sd if odev is None else {k: v.to(DEV) for k, v in sd.items()}
+    oracle, oracle_bf16 = R.RefStripedHyena(cfg, osd, "fp64", device=odev), R.RefStripedHyena(cfg, osd, "bf16", device=odev)
     worst_oracle = worst_floor = 0.0
     for j in range(len(THREE)):
         ids = prepare_batch([THREE[j]], _tok(), prepend_bos=False, device=DEV)[0]
         P = ids.shape[1]
-        full_ids = torch.cat([ids, runs[True][0][j: j + 1].to(DEV)], dim=1)
+        full_ids = torch.cat([ids, last_ids[j: j + 1].to(DEV)], dim=1)
         oid = full_ids.cpu() if odev is None else full_ids
         ref = oracle(oid)[0][0][P - 1: P - 1 + N_TOK].cpu()
         flo = oracle_bf16(oid)[0][0][P - 1: P - 1 + N_TOK].cpu()
-        worst_oracle = max(worst_oracle, rel_l2(runs[True][1][j], ref))
+        worst_oracle = max(worst_oracle, rel_l2(last_logits[j], ref))
         worst_floor = max(worst_floor, rel_l2(flo, ref))
-    print(f"[w8 pool {dims}] recorded logits vs the fp64 oracle on the dequantised weights: worst rel-L2 {worst_oracle:.3e} "
+    print(f"[{what}] recorded logits vs the fp64 oracle on the dequantised weights: worst rel-L2 {worst_oracle:.3e} "
           f"(eager-bf16 oracle {worst_floor:.3e})")
     assert worst_oracle < max(1.5 * worst_floor, 4e-3), (worst_oracle, worst_floor)
+
+
+def test_shared_prompt_kv_pool_runs_the_fp8_steps():
+    """share_prompt_kv=True, weight_dtype="fp8": the steps make the dense launches of the unshared FP8 pool -- none of the bf16 ones they
+    replace -- and the recorded logits meet the criterion above.  (Three slots, three prompts: every prefill precedes the first step.)"""
+    import forward_trace as FT
+    cfg, sd, m = _twin("toy")
+
+    def entries(**kw):
+        pool = _pool(m, use_graph=False, seed=11, **kw)
+        with FT.recording(m.ops) as calls:
+            pool.generate(THREE, n_tokens=N_TOK, n_sample_per_prompt=1)
+        return {c.split(" ", 1)[0] for c in calls}, pool
+    plain, _ = entries()
+    unshared, _ = entries(weight_dtype="fp8")
+    shared, pool = entries(weight_dtype="fp8", share_prompt_kv=True)
+    w8 = {n for n in unshared if "_w8" in n and "quant" not in n}
+    replaced = plain - unshared                                       # the bf16 dense launches of a step: what the FP8 ones stand in for
+    assert w8 and replaced and all("_w8" not in n for n in replaced)
+    assert {n for n in shared if "_w8" in n and "quant" not in n} == w8
+    assert not shared & replaced, sorted(shared & replaced)
+    assert pool.ipd["mha"].weight_dtype == "fp8" and pool.stats["weight_dtype"] == "fp8"
+    _assert_logits_vs_oracle("w8 pool toy, shared prompt K/V", cfg, sd, None, pool.last_ids, pool.last_logits)
 
 
 def test_seeded_runs_repeat_and_bf16_is_untouched():

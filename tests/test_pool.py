@@ -60,6 +60,24 @@ def test_pool_reuse_and_growth(model_and_reference):
     np.testing.assert_allclose(sb, scores, rtol=1e-9, atol=1e-12)
 
 
+def test_a_dropped_pool_dies_by_reference_count(model_and_reference):
+    """A pool holds a captured graph on the GPU; left to the cycle collector it would be destroyed at an arbitrary moment -- inside another
+    pool's stream capture, which aborts the process.  So nothing in a pool may refer back to it strongly."""
+    import gc
+    import weakref
+    m = model_and_reference[0]
+    gc.collect()
+    gc.disable()
+    try:
+        pool = DecodePool(m, TOK, n_slots=2, top_k=1, top_p=1.0, temperature=0.0, device="cpu")
+        pool.generate(PROMPTS[:3], n_tokens=3)
+        ref = weakref.ref(pool)
+        del pool
+        assert ref() is None
+    finally:
+        gc.enable()
+
+
 def test_sample_many_stochastic_is_well_formed(model_and_reference):
     m, _, _ = model_and_reference
     torch.manual_seed(0)

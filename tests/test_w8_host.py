@@ -339,8 +339,9 @@ def test_which_tensors_got_a_record(small):
     assert len(held) == 4 * small.num_layers
 
 
-def test_pool_of_four_slots_equals_the_dequantised_twin(small, twin):
-    kw = dict(n_slots=4, top_k=1, top_p=1.0, temperature=0.0, device="cpu")
+@pytest.mark.parametrize("share_prompt_kv", [False, True])
+def test_pool_of_four_slots_equals_the_dequantised_twin(small, twin, share_prompt_kv):
+    kw = dict(n_slots=4, top_k=1, top_p=1.0, temperature=0.0, device="cpu", share_prompt_kv=share_prompt_kv)
     twin.ops.w8_calls = dict.fromkeys(twin.ops.w8_calls, 0)
     p8 = DecodePool(twin, TOK, weight_dtype="fp8", **kw)
     s8, sc8, o8 = p8.generate(PROMPTS, n_tokens=5, n_sample_per_prompt=1)
@@ -360,8 +361,24 @@ def test_pool_of_four_slots_equals_the_dequantised_twin(small, twin):
     DecodePool(small, TOK, weight_dtype="fp8", **kw).generate(PROMPTS[:2], n_tokens=3, n_sample_per_prompt=1)
     assert small.ops.w8_calls["gate"] > 0
     # sample_many passes the option on
-    _, seqs, _ = sample_many(PROMPTS[:2], twin, TOK, n_tokens=3, temp=0.0, top_k=1, n_slots=2, device="cpu", weight_dtype="fp8")
+    _, seqs, _ = sample_many(PROMPTS[:2], twin, TOK, n_tokens=3, temp=0.0, top_k=1, n_slots=2, device="cpu", weight_dtype="fp8",
+                             share_prompt_kv=share_prompt_kv)
     assert seqs == [x[:3] for x in s8[:2]]
+
+
+def test_beam_search_runs_fp8_steps_and_leaves_the_flag_as_the_pool_set_it():
+    """A share_prompt_kv pool's caches carry the pool's weight format themselves: the search patches nothing for its run."""
+    from beam_ref import BeamOracleOps
+
+    class BeamW8Ops(W8.W8OracleOps, BeamOracleOps):
+        pass
+    m = _model(BeamW8Ops(torch.float64))
+    pool = DecodePool(m, TOK, n_slots=4, device="cpu", share_prompt_kv=True, weight_dtype="fp8")
+    res = pool.beam_search(PROMPTS[:2], 3, beam_width=2)
+    L, steps = m.num_layers, pool.stats["beam_steps"]
+    assert len(res) == 2 and steps > 0
+    assert m.ops.w8_calls["gate"] == steps * L and m.ops.w8_calls["linear"] == 2 * steps * L
+    assert pool.ipd["mha"].weight_dtype == "fp8"
 
 
 def test_a_set_built_before_fold_norms_is_rebuilt_after_it():
