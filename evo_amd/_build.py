@@ -34,6 +34,7 @@ EXPORTS = [
     "evo_beam_select_f32", "evo_gather_rows",
     "evo_linear_rowinv_bf16", "evo_mlp_gate_rowinv_bf16",
     "evo_repeat_rows_f32",
+    "evo_linear_skinny_w8", "evo_mlp_gate_skinny_w8",
 ]
 
 

@@ -43,7 +43,7 @@ class Backend:
         "norm_fold": ("nf_shape_ok", "zt_stream_rows_ok", "linear_rs", "linear_t_rs", "mlp_gate_rs", "linear_residual_stats_", "linear_residual_yblk_stats_"),
         "unembed_logprob": ("unembed_logprob", "unembed_logprob_ok"),
         "kv_fp8": ("kv_quant_fp8", "rope_append_decode_fp8", "attention_decode_fp8"),     # the FP8 KV cache (InferenceParams.kv_dtype == "fp8")
-        # FP8 weights for the single-token step at 1-8 rows (InferenceParams.weight_dtype == "fp8"): w_quant_fp8(w) -> Fp8Weight; the others
+        # FP8 weights for the single-token step at 1 .. W8_ROWS rows (InferenceParams.weight_dtype == "fp8"): w_quant_fp8(w) -> Fp8Weight; the others
         # are linear / linear_residual_ / norm_linear / hyena_decode_fused / mlp_gate with the record in place of the weight(s)
         "w_fp8": ("w_quant_fp8", "linear_w8", "linear_residual_w8_", "norm_linear_w8", "hyena_decode_fused_w8", "mlp_gate_w8"),
         "kv_paged": ("rope_append_decode_paged", "attention_decode_paged"),               # the paged KV cache (InferenceParams.kv_layout == "paged")
@@ -68,6 +68,7 @@ class Backend:
 
     # ---- pure host functions ---------------------------------------------------------------------------------------------------------
     DECODE_ROWS = 8     # batches this small take the fused single-token launches (csrc/gemv.hip; 5-8 rows at a width of 4096 only)
+    W8_ROWS = 8         # batch rows the "w_fp8" launches serve (a routing fact, declared, not probed for: HipOps serves 64)
     YBLK = 128          # rows per block of the blocked y layout (csrc/hyena_ct.hip)
     ZT_ALIGN = 64       # positions a batch row of z^T is padded to (% 8 == 0: 16-byte loads; 64 = whole cache lines -- tools/hc_bench.py A/B)
 

@@ -23,19 +23,28 @@ import numpy as np
 import torch
 
 from .scoring import logits_to_logprobs, prepare_batch
-from .sh.cache import check_kv_dtype, check_weight_dtype, check_weight_rows
+from .sh.cache import W8_MAX_ROWS, check_kv_dtype, check_weight_dtype, check_weight_rows
 from .sh.sample import allowed_mask, sample
 from .tokenizer import CharLevelTokenizer
 
 
-def check_fp8_weight_model(model) -> None:
-    """weight_dtype="fp8" on this model: RuntimeError without the "w_fp8" kernels, ValueError for a streamed layer the launches cannot
-    take (K % 16 != 0) -- from shapes alone, before any device work."""
+def w8_rows(model) -> int:
+    """Batch rows the FP8-weight launches of this model's backend serve (Backend.W8_ROWS; 8 where a backend declares nothing)."""
+    return int(getattr(getattr(model, "ops", None), "W8_ROWS", W8_MAX_ROWS))
+
+
+def check_fp8_weight_model(model, rows: int = 1) -> None:
+    """weight_dtype="fp8" on this model at `rows` batch rows: RuntimeError without the "w_fp8" kernels, ValueError for a streamed layer
+    the launches cannot take (K % 16 != 0; above 8 rows K % 256 != 0) -- from shapes alone, before any device
+    work."""
     ops = getattr(model, "ops", None)
     if ops is None or not hasattr(ops, "supports") or not ops.supports("w_fp8"):
         raise RuntimeError('weight_dtype="fp8" needs a compute backend with the "w_fp8" kernels (w_quant_fp8 and the *_w8 dense launches); '
                            "this model's backend has none")
-    model.check_fp8_weights()
+    if rows > W8_MAX_ROWS:
+        model.check_fp8_weights(rows)
+    else:
+        model.check_fp8_weights()
 
 
 class Generator:
@@ -46,7 +55,8 @@ class Generator:
         the device sampler `evo_sample_rows_f32` -- row b of a batch draws from random stream `stream_offset + b`, reproducibly
         under `seed`, and only from `allowed_tokens` (e.g. "ACGT") when given.  `kv_dtype="fp8"`: the caches this
         generator creates hold their K/V in FP8 e4m3fn.  `weight_dtype="fp8"`: the single-token steps on those caches
-        stream FP8 e4m3fn copies of the dense weights (batches of up to 8 prompts; DESIGN.md section 22: more memory, less time per token)."""
+        stream FP8 e4m3fn copies of the dense weights (batches of up to 64 prompts on the HIP backend; DESIGN.md sections 22 and 28: more memory,
+        fewer bytes per token)."""
         self.kv_dtype = check_kv_dtype(kv_dtype)
         self.weight_dtype = check_weight_dtype(weight_dtype)
         if self.weight_dtype == "fp8":
@@ -92,7 +102,8 @@ class Generator:
         num_tokens = int(num_tokens)
         B, P = x.shape
         if self.weight_dtype == "fp8":
-            check_weight_rows(B, "prompts in the batch")
+            check_weight_rows(B, "prompts in the batch", w8_rows(self.model))
+            check_fp8_weight_model(self.model, B)
         x_force = None
         n_forced = 0
         if force_prompt_threshold is not None and P > force_prompt_threshold:
@@ -189,8 +200,8 @@ def generate(prompt_seqs: List[str], model, tokenizer: CharLevelTokenizer, n_tok
     """Generate `n_tokens` after each prompt.  Equal-length prompts run as one batch when `batched`.
     Returns (generated strings, mean log-likelihood score per generation).  `seed`: the same call gives the same strings
     (prompt number i draws from random stream i); `allowed_tokens`: the characters that may be generated, e.g. "ACGT"; `kv_dtype="fp8"`
-    (with `cached_generation`): the KV cache in FP8 e4m3fn; `weight_dtype="fp8"` (with `cached_generation`, batches of up to 8 prompts): the
-    decode steps stream FP8 copies of the dense weights."""
+    (with `cached_generation`): the KV cache in FP8 e4m3fn; `weight_dtype="fp8"` (with `cached_generation`, batches of up to 64 prompts): the
+    decode steps stream FP8 copies of the dense weights (DESIGN.md sections 22 and 28)."""
     if hasattr(model, "eval"):
         model.eval()
     g = Generator(model, tokenizer, top_k=top_k, top_p=top_p, temperature=temperature, seed=seed, allowed_tokens=allowed_tokens,
@@ -199,7 +210,8 @@ def generate(prompt_seqs: List[str], model, tokenizer: CharLevelTokenizer, n_tok
     same_len = all(len(s) == len(prompt_seqs[0]) for s in prompt_seqs)
     if batched and same_len:
         if weight_dtype == "fp8":
-            check_weight_rows(len(prompt_seqs), "prompts in the batch")
+            check_weight_rows(len(prompt_seqs), "prompts in the batch", w8_rows(model))
+            check_fp8_weight_model(model, len(prompt_seqs))
         batches = [prepare_batch(prompt_seqs, tokenizer, prepend_bos=prepend_bos, device=device)[0]]
     else:
         if verbose:

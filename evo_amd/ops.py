@@ -81,6 +81,8 @@ _SIGNATURES = {
     "evo_hyena_decode_fused_small_m_w8": ([_PTR] * 13 + [_I64] * 3 + [_F32, _PTR], _c.c_int),
     "evo_mlp_gate_small_m_w8": ([_PTR] * 4 + [_I64] * 4 + [_PTR], _c.c_int),
     "evo_norm_mlp_gate_small_m_w8": ([_PTR] * 5 + [_I64] * 3 + [_F32, _I64, _PTR], _c.c_int),
+    "evo_linear_skinny_w8": ([_PTR] * 6 + [_I64] * 3 + [_PTR, _I64, _PTR], _c.c_int),
+    "evo_mlp_gate_skinny_w8": ([_PTR] * 4 + [_I64] * 4 + [_PTR], _c.c_int),
     "evo_rope_append_decode_paged_bf16": ([_PTR] * 5 + [_F32] + [_I64] * 10 + [_F32, _PTR], _c.c_int),
     "evo_attn_decode_paged_bf16": ([_PTR] * 4 + [_I64] * 11 + [_PTR] * 3 + [_I64, _F32, _PTR], _c.c_int),
     "evo_beam_select_f32": ([_PTR, _I64, _I64] + [_PTR] * 11 + [_I64, _PTR] + [_I64] * 4 + [_PTR], _c.c_int),
@@ -201,6 +203,7 @@ class HipOps(Backend):
     """The gfx950 op set (the contract: evo_amd/backend.py).  All tensors must live on the same ROCm device."""
 
     name = "hip-gfx950"
+    W8_ROWS = 64        # the FP8-weight launches serve 1-8 rows (csrc/gemv_fp8.hip) and 9-64 rows (csrc/skinny_fp8.hip)
 
     def __init__(self):
         self.lib = load_library()
@@ -234,7 +237,7 @@ class HipOps(Backend):
         # operands, no input window in LDS); False: the modal three-launch kernels (the tests' yardstick, padding masks, tiny inputs)
         self.hyena_mfma = True
         self.hyena_ct_flag = True
-        self._xpad = threading.local()  # per thread: the zero-initialised padded input of the swapped-operand projection (_xpad_buffer)
+        self._xpad = threading.local()  # per thread: the zero-initialised padded input of the swapped-operand projection (_xpad_buffer), and the split-K workspaces of the 9-64-row FP8 launches (_skinny_w8_ws)
         self.last_hyena_io = {}
 
     def _t(self, name):
@@ -462,8 +465,10 @@ class HipOps(Backend):
         return cur[1]
 
     def release_workspaces(self) -> None:
-        """Frees this thread's cached rmsnorm_rows workspace (0.5 GB at 8 x 8,193, 1 GB at 1 x 131,073 for D = 4096)."""
+        """Frees this thread's cached rmsnorm_rows workspace (0.5 GB at 8 x 8,193, 1 GB at 1 x 131,073 for D = 4096) and the split-K
+        workspaces of the 9-64-row FP8 launches (_skinny_w8_ws)."""
         self._xpad.entry = None
+        self._xpad.w8_ws = None
 
     def rmsnorm_rows(self, x: torch.Tensor, scale: torch.Tensor, eps: float, B: int, T: int) -> torch.Tensor:
         """RMSNorm of x [B T, D] written in the row order of zt_layout: -> [Mp + 16, D], row b T + t at its z^T position for t < Tm, the
@@ -1194,19 +1199,23 @@ class HipOps(Backend):
         self._launch("gemv_gate_rowinv", "evo_mlp_gate_rowinv_bf16", x.data_ptr(), wsrc.data_ptr(), a.data_ptr(), M, I, K, 1 if w12 is None else 0)
         return a
 
-    # ---- FP8 (e4m3fn) weights for the single-token step at 1-8 rows: the optional group "w_fp8" (csrc/gemv_fp8.hip) ----
+    # ---- FP8 (e4m3fn) weights for the single-token step: the optional group "w_fp8" (1-8 rows: csrc/gemv_fp8.hip, DESIGN.md section 22;
+    # 9-64 rows: csrc/skinny_fp8.hip, the MFMA weight-streaming forms) ----
     # Each method is its bf16 namesake with an Fp8Weight record in place of the weight, and takes the same route: fused where the bf16
     # launch is fused (Backend.fused_rows_ok), norm pass + plain launch where it is not.  Nothing here falls back to bf16 weights.
     def _w8_args(self, op: str, x: torch.Tensor, rec) -> tuple:
-        """(data ptr, scale ptr) of `rec` checked against x [M, K]: uint8 [N, K] + f32 [N] on x's device, K % 16 == 0, 1 <= M <= 8."""
+        """(data ptr, scale ptr) of `rec` checked against x [M, K]: uint8 [N, K] + f32 [N] on x's device, K % 16 == 0, 1 <= M <= 64 (from
+        9 rows on K % 256 == 0: the MFMA forms of csrc/skinny_fp8.hip)."""
         self._need(x, torch.bfloat16, f"{op} x")
         d, sc = rec.data, rec.scale
         M, K = x.shape
         if not d.is_cuda or not sc.is_cuda or d.dtype != torch.uint8 or sc.dtype != torch.float32 or d.dim() != 2 or not d.is_contiguous() \
                 or not sc.is_contiguous() or tuple(sc.shape) != (d.shape[0],):
             raise RuntimeError(f"{op}: an FP8 weight is data [N, K] uint8 + scale [N] f32, contiguous, on a ROCm device")
-        if d.shape[1] != K or K % 16 or not 1 <= M <= 8:
-            raise RuntimeError(f"{op}: x {tuple(x.shape)} against an FP8 weight {tuple(d.shape)}: need matching K % 16 == 0 and 1-8 rows")
+        if d.shape[1] != K or K % 16 or not 1 <= M <= self.W8_ROWS:
+            raise RuntimeError(f"{op}: x {tuple(x.shape)} against an FP8 weight {tuple(d.shape)}: need matching K % 16 == 0 and 1-{self.W8_ROWS} rows")
+        if M > 8 and K % 256:
+            raise RuntimeError(f"{op}: x {tuple(x.shape)} against an FP8 weight {tuple(d.shape)}: 9-{self.W8_ROWS} rows need K % 256 == 0")
         self._check_address(d.data_ptr(), f"{op} weight data")
         self._check_address(sc.data_ptr(), f"{op} weight scale", 4)
         return d.data_ptr(), sc.data_ptr()
@@ -1229,11 +1238,32 @@ class HipOps(Backend):
         if res is not None:
             self._need(res, torch.bfloat16, "linear_w8 residual")
         y = res if res is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        if M > 8:                                                # 9-64 rows: the MFMA weight-streaming forms (csrc/skinny_fp8.hip)
+            part = self._skinny_w8_ws(x.device, M, N, K)
+            self._launch("skinny_w8", "evo_linear_skinny_w8", x.data_ptr(), wd, ws, _ptr(b), _ptr(res), y.data_ptr(), M, N, K, _ptr(part),
+                         0 if part is None else part.numel() * 4)
+            return y
         self._launch("gemv_w8", "evo_linear_small_m_w8", x.data_ptr(), wd, ws, _ptr(b), _ptr(res), y.data_ptr(), M, N, K, None, 0)
         return y
 
+    def _skinny_w8_ws(self, device, M: int, N: int, K: int) -> Optional[torch.Tensor]:
+        """The workspace of evo_linear_skinny_w8's split over K (narrow layers: N < 8192, N % 64 == 0, two 256-k units or more), one per
+        (thread, device, M, N) until release_workspaces(): a decode step calls this twice per block, and inside a graph capture every
+        fresh tensor is memory the graph's pool keeps.  A thread's launches on its stream run in order, so they share it.  (A captured
+        graph holds the address: release_workspaces() is for code that owns no live graph, as with the rmsnorm_rows workspace.)"""
+        if N >= 8192 or N % 64 or K < 512:
+            return None
+        cache = getattr(self._xpad, "w8_ws", None)
+        if cache is None:
+            cache = self._xpad.w8_ws = {}
+        key = (device.index, M, N)
+        part = cache.get(key)
+        if part is None:
+            part = cache[key] = torch.empty(8 * M * N, dtype=torch.float32, device=device)
+        return part
+
     def linear_w8(self, x: torch.Tensor, rec, b: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [M, K] @ W^T (+ b) -> [M, N] bf16, W an Fp8Weight, 1 <= M <= 8."""
+        """x [M, K] @ W^T (+ b) -> [M, N] bf16, W an Fp8Weight, 1 <= M <= 64 (K % 256 == 0 from 9 rows on)."""
         return self._linear_w8(x, rec, b, None)
 
     def linear_residual_w8_(self, res: torch.Tensor, x: torch.Tensor, rec, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1284,6 +1314,11 @@ class HipOps(Backend):
         if I % 2 or (grouped and I % 32):
             raise RuntimeError(f"mlp_gate_w8: inner size {I} does not fit the launch (even; a multiple of 32 in the grouped order)")
         a = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
+        if M > 8:                                                # (norm_scale is None here: fused_rows_ok ends at 8 rows)
+            if I % 32:
+                raise RuntimeError(f"mlp_gate_w8: inner size {I} is not a multiple of 32 (the 9-{self.W8_ROWS}-row launch)")
+            self._launch("skinny_gate_w8", "evo_mlp_gate_skinny_w8", x.data_ptr(), wd, ws, a.data_ptr(), M, I, K, int(bool(grouped)))
+            return a
         if norm_scale is None:
             self._launch("gemv_gate_w8", "evo_mlp_gate_small_m_w8", x.data_ptr(), wd, ws, a.data_ptr(), M, I, K, int(bool(grouped)))
         else:

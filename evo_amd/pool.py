@@ -47,7 +47,7 @@ bytes per key and layer at 32 heads instead of 16,384; `stats["kv_bytes"]` repor
 and only store quantised; the step appends with `rope_append_decode_fp8` and attends with `attention_decode_fp8`.  A pool has one format
 for its life, so its captured step is captured on it.  Not with `share_prompt_kv` (ValueError): the prompt store stays bf16.
 
-`weight_dtype="fp8"` (opt-in; pools of up to 8 slots): the step streams FP8 e4m3fn copies of the dense weights (half
+`weight_dtype="fp8"` (opt-in, DESIGN.md sections 22 and 28; pools of up to 64 slots on the HIP backend): the step streams FP8 e4m3fn copies of the dense weights (half
 the bytes; the copies sit beside the bf16 weights, which the prefills keep reading).  `stats["weight_dtype"]` and
 `stats["decode_weight_bytes"]` report the format and what a step streams.  It composes with every option above, `share_prompt_kv` and
 `beam_search` included (every cache of a pool is built by `_new_caches`, which sets the step flags): only the dense launches of the step change.
@@ -367,9 +367,9 @@ class DecodePool:
                 if self.budget_pages < 1:
                     raise ValueError(f"kv_budget_tokens = {kv_budget_tokens} holds no page of {self.page_tokens} tokens")
         if self.weight_dtype == "fp8":                               # 
-            from .generation import check_fp8_weight_model
-            check_weight_rows(int(n_slots), "n_slots")
-            check_fp8_weight_model(model)
+            from .generation import check_fp8_weight_model, w8_rows
+            check_weight_rows(int(n_slots), "n_slots", w8_rows(model))
+            check_fp8_weight_model(model, int(n_slots))
         if self.poll_every < 1:
             raise ValueError("poll_every must be >= 1")
         if self.prefill_batch < 1:

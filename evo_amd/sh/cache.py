@@ -147,7 +147,8 @@ class PagedKV:
 
 
 WEIGHT_DTYPES = ("bf16", "fp8")
-W8_MAX_ROWS = 8        # batch rows the FP8-weight launches serve (csrc/gemv_fp8.hip: the dot2 forms; the 9-64-row MFMA forms are bf16 only)
+W8_MAX_ROWS = 8        # batch rows the FP8-weight launches of a backend serve unless it declares more (Backend.W8_ROWS; csrc/gemv_fp8.hip: the dot2 forms)
+W8_WIDE_K = 256        # above W8_MAX_ROWS rows every streamed layer's K is a multiple of this (csrc/skinny_fp8.hip: whole 256-k units)
 
 
 def check_weight_dtype(weight_dtype) -> str:
@@ -157,11 +158,11 @@ def check_weight_dtype(weight_dtype) -> str:
     return weight_dtype
 
 
-def check_weight_rows(rows: int, what: str) -> None:
-    """ValueError when `rows` decode streams are more than the FP8-weight launches serve."""
-    if rows > W8_MAX_ROWS:
-        raise ValueError(f'weight_dtype="fp8" serves at most {W8_MAX_ROWS} rows per decode step, got {what} = {rows} (the 9-64-row launches '
-                         "are bf16 only)")
+def check_weight_rows(rows: int, what: str, max_rows: int = W8_MAX_ROWS) -> None:
+    """ValueError when `rows` decode streams are more than the backend's FP8-weight launches serve (`max_rows`: its Backend.W8_ROWS)."""
+    if rows > max_rows:
+        why = " (the 9-64-row launches are bf16 only)" if max_rows == W8_MAX_ROWS else ""
+        raise ValueError(f'weight_dtype="fp8" serves at most {max_rows} rows per decode step, got {what} = {rows}{why}')
 
 
 ROWINV_MAX_ROWS = 64    # batch rows the row-invariant dense launches serve (csrc/gemv_inv.hip)

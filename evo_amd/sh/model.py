@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..backend import Backend                            # (the contract of `ops`, and the pure host rules every backend shares)
-from .cache import (ROWINV_SPLITS, Fp8KV, InferenceParams, PagedKV, RecurrentInferenceParams, check_kv_dtype, check_rowinv_rows, check_weight_dtype,
+from .cache import (ROWINV_SPLITS, W8_MAX_ROWS, W8_WIDE_K, Fp8KV, InferenceParams, PagedKV, RecurrentInferenceParams, check_kv_dtype, check_rowinv_rows, check_weight_dtype,
                     check_weight_rows)
 from .utils import dotdict
 
@@ -375,14 +375,19 @@ class StripedHyena(nn.Module):
         inner = self.inner_size
         return ((inner + 255) // 256) * 256 if inner >= 1024 else inner
 
-    def check_fp8_weights(self) -> None:
-        """ValueError naming the first streamed layer whose K is not a multiple of 16 (the FP8 launches' contract); shapes only."""
+    def check_fp8_weights(self, rows: int = 1) -> None:
+        """ValueError naming the first streamed layer the FP8 launches cannot take at `rows` batch rows -- K not a multiple of 16; above 8
+        rows (the MFMA forms, csrc/skinny_fp8.hip) K not a multiple of 256; shapes only.  (The gate launch's I % 32 == 0 needs no line of
+        its own: the inner size is l3's K.)"""
         D, ipad = self.hidden_size, self._padded_inner()
         for i, blk in enumerate(self.blocks):
             names = ("projections", "out_filter_dense") if isinstance(blk, _HyenaBlock) else ("inner_mha_cls.Wqkv", "inner_mha_cls.out_proj")
             for n, K in ((names[0], D), (names[1], D), ("mlp.l1 | mlp.l2", D), ("mlp.l3", ipad)):
                 if K % 16:
                     raise ValueError(f'weight_dtype="fp8": blocks.{i}.{n} has K = {K}, not a multiple of 16 (include/evo_mi355x.h, ABI 20)')
+                if rows > W8_MAX_ROWS and K % W8_WIDE_K:
+                    raise ValueError(f'weight_dtype="fp8" at {rows} rows: blocks.{i}.{n} has K = {K}, not a multiple of {W8_WIDE_K} (the '
+                                     f"launches for more than {W8_MAX_ROWS} rows; include/evo_mi355x.h, evo_linear_skinny_w8)")
 
     def prepare_fp8_weights(self) -> "StripedHyena":
         """Builds the FP8 (e4m3fn) copies of the dense weights a single-token step streams -- Hyena projections, Wqkv, out_filter_dense /
@@ -1013,7 +1018,9 @@ class StripedHyena(nn.Module):
         rs = None
         w8s = None
         if T == 1 and mha_c is not None and check_weight_dtype(mha_c.weight_dtype) == "fp8":     # 
-            check_weight_rows(B, "batch rows")
+            check_weight_rows(B, "batch rows", self.ops.W8_ROWS)
+            if B > W8_MAX_ROWS:
+                self.check_fp8_weights(B)
             w8s = self.prepare_fp8_weights()._w8
         inv = T == 1 and mha_c is not None and bool(mha_c.batch_invariant)                         # 
         if inv:

@@ -84,6 +84,7 @@ extern "C" {
  *      Added since under ABI 20, no signature changed: the paged KV entries, the beam search entries, and evo_linear_rowinv_bf16 /
  *      evo_mlp_gate_rowinv_bf16 (the row-invariant dense launches of the decode pool's opt-in batch-invariant step, csrc/gemv_inv.hip).
  *      evo_repeat_rows_f32 (k-mer repeat control in front of the decode pool's sampler launch, csrc/repeat.hip).
+ *      evo_linear_skinny_w8 / evo_mlp_gate_skinny_w8 (FP8 weights at 5-64 rows on the MFMA weight-streaming forms, csrc/skinny_fp8.hip).
  *      A binding that needs them finds out at load time: every entry it declares must be exported. */
 #define EVO_ABI_VERSION 20
 int evo_abi_version(void);
@@ -460,6 +461,30 @@ int evo_mlp_gate_small_m_w8(const void* x, const void* w12_data, const float* w1
 /* evo_norm_mlp_gate_small_m_bf16: the same with RMSNorm folded in front; rows as evo_norm_linear_small_m_w8. */
 int evo_norm_mlp_gate_small_m_w8(const void* x, const void* scale, const void* w12_data, const float* w12_scale, void* a,
                                  int64_t M, int64_t I, int64_t K, float eps, int64_t grouped, void* stream);
+
+/* ---- FP8 weights at 5-64 rows: the MFMA weight-streaming forms (added under ABI 20, no signature changed; csrc/skinny_fp8.hip) ----------
+ * The record, the rule and the layout are the ones above.  The kernels are the n-split forms of evo_linear_small_m_bf16 /
+ * evo_mlp_gate_small_m_bf16 at 5-64 rows (csrc/skinny_nw.h) with one byte per weight to stream: the bytes of a chunk are requested as
+ * contiguous row pieces, parked in LDS as bytes, converted to bf16 in registers (exactly) and multiplied against the bf16 x rows with
+ * v_mfma_f32_16x16x32_bf16, fp32 accumulation.  The row's scale multiplies the reduced fp32 sum once per output element -- under a
+ * split over K once per partial sum -- before bias, residual or gate; one rounding at the end.  With power-of-two scales an entry
+ * returns what its sibling's arithmetic returns on the dequantised weight, up to the order of the fp32 additions.
+ *
+ * Both return -1 without a launch on a null or misaligned pointer (16 bytes; 4 for the scale; bias / residual / ws may be NULL),
+ * M outside 5-64, K < 256 or K % 256 != 0, N < 1 (I < 32 or I % 32 != 0), or a size whose element counts leave 32-bit indices.
+ *
+ * evo_linear_skinny_w8: y [M, N] = x [M, K] W^T (+ bias [N]) (+ residual [M, N], which may alias y).  The dense layers of a decode
+ * step [REF stripedhyena/model.py: projections, Wqkv, out_filter_dense, out_proj; layers.py ParallelGatedMLP.l3].  ws (16-byte
+ * aligned, ws_bytes long, or NULL): with N < 8192, N % 64 == 0 and room for slices * M * N floats -- slices = min(8, K / 256,
+ * ceil(256 / (N / 64))) >= 2 -- K is split across workgroups, the partial sums go through ws and a second launch adds them in slice
+ * order; otherwise one launch, whole K per wave, any N.  Nothing but y and ws is written. */
+int evo_linear_skinny_w8(const void* x, const void* w_data, const float* w_scale, const void* bias, const void* residual, void* y,
+                         int64_t M, int64_t N, int64_t K, void* ws, int64_t ws_bytes, void* stream);
+/* evo_mlp_gate_skinny_w8: a [M, I] = gelu(x W1^T) * (x W2^T) [REF stripedhyena/layers.py ParallelGatedMLP], w12 = [W1; W2] ([2 I, K])
+ * plain, or (`grouped` != 0) in evo_mlp_gate_mfma_bf16's row order.  Both scaled sums are rounded to bf16, the gate is evaluated in
+ * fp32 and rounded once: evo_mlp_gate_small_m_bf16's arithmetic at these rows.  Nothing but a is written. */
+int evo_mlp_gate_skinny_w8(const void* x, const void* w12_data, const float* w12_scale, void* a, int64_t M, int64_t I, int64_t K,
+                           int64_t grouped, void* stream);
 
 /* decode behind SHARED prompts (ABI 15): row b attends to the keys [0, pre_len[pre_row[b]]) of row pre_row[b] of a prompt store and
  * then to its OWN keys [0, own_pos[b]] -- what evo_attn_decode_bf16 returns on the concatenation, without a copy of the prompt per

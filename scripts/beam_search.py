@@ -26,7 +26,7 @@ def main(argv=None):
     ap.add_argument("--allowed-tokens", default=None, help='characters that may be generated, e.g. "ACGT" (default: any byte)')
     ap.add_argument("--stop-tokens", default=None, help='characters that end a hypothesis and are trimmed from it, e.g. "N"')
     ap.add_argument("--prefill-batch", type=int, default=1, help="prefill up to N prompts admitted together in one forward")
-    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the decode step streams (fp8: up to 8 slots)")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the decode step streams (fp8: up to 64 slots)")
     ap.add_argument("--prepend-bos", action="store_true")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--weights", default=None)

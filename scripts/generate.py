@@ -37,10 +37,10 @@ def main():
     ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the decode steps of a cached generation "
                                                                                     "stream; fp8 (e4m3fn, one scale per output row) halves "
                                                                                     "the bytes per token and adds an FP8 copy to memory; "
-                                                                                    "up to 8 samples per batch")
+                                                                                    "up to 64 samples per batch")
     args = ap.parse_args()
-    if args.weight_dtype != "bf16" and args.batched and args.n_samples > 8:
-        ap.error("--weight-dtype fp8 serves batches of up to 8 samples")
+    if args.weight_dtype != "bf16" and args.batched and args.n_samples > 64:
+        ap.error("--weight-dtype fp8 serves batches of up to 64 samples")
 
     import evo_amd
     m = evo_amd.Evo(args.model_name, device=args.device, weights=args.weights)

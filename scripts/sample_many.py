@@ -84,7 +84,7 @@ def main(argv=None):
                                                                                 "--share-prompt-kv")
     ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16", help="dense weights the pool's decode step streams; fp8 (e4m3fn, "
                                                                                     "one scale per output row) halves the bytes per step and "
-                                                                                    "adds an FP8 copy to memory; --n-slots up to 8")
+                                                                                    "adds an FP8 copy to memory; --n-slots up to 64")
     ap.add_argument("--kv-paged", action="store_true", help="keep the pool's KV cache in pages: a job holds what its own prompt and "
                                                             "limit need, not the longest job's; not with --share-prompt-kv or "
                                                             "--kv-dtype fp8")
@@ -112,8 +112,8 @@ def main(argv=None):
         ap.error("--kv-page-tokens and --kv-budget-tokens apply with --kv-paged only")
     if args.kv_page_tokens < 64 or args.kv_page_tokens & (args.kv_page_tokens - 1):
         ap.error("--kv-page-tokens must be a power of two >= 64")
-    if args.weight_dtype != "bf16" and args.n_slots > 8:
-        ap.error("--weight-dtype fp8 serves pools of up to 8 slots")
+    if args.weight_dtype != "bf16" and args.n_slots > 64:
+        ap.error("--weight-dtype fp8 serves pools of up to 64 slots")
     if args.batch_invariant and (args.n_slots > 64 or args.prefill_batch > 1 or args.share_prompt_kv or args.kv_dtype != "bf16"
                                  or args.weight_dtype != "bf16"):
         ap.error("--batch-invariant serves pools of up to 64 slots and does not combine with --prefill-batch > 1, --share-prompt-kv, "

@@ -1,15 +1,17 @@
 #!/usr/bin/env python
-"""Times the FP8 (e4m3fn) decode weights against the bf16 weights, legs alternated in one process (not part of bench.py).
+"""Times the FP8 (e4m3fn) decode weights against the bf16 weights, legs alternated in one process (not part of bench.py; DESIGN.md sections 22 and 28).
 
-    python tools/bench_w8.py [--legs kernel,step,quality] [--runs 5] [--warmup 2] [--streams 1,4,8] [--prompt-len 8192] [--tokens 64]
-                             [--small] [--tree PATH --label NAME --weight-dtypes bf16]
+    python tools/bench_w8.py [--legs kernel,step,quality] [--runs 5] [--warmup 2] [--streams 1,4,8] [--rows 1,4,8] [--prompt-len 8192]
+                             [--tokens 64] [--quality-streams 1] [--small] [--tree PATH --label NAME --weight-dtypes bf16]
 
-kernel   every launch class of a 7B decode step at M in {1, 4, 8}, FP8 beside bf16 on the same values: microseconds (device events) and
-         the achieved TB/s of the weight bytes each form reads (FP8: bytes + 4 per row).
+kernel   every launch class of a 7B decode step at the M of --rows (1-64), FP8 beside bf16 on the same values: microseconds (device
+         events) and the achieved TB/s of the weight bytes each form reads (FP8: bytes + 4 per row).  Above 8 rows neither format folds
+         the norm or the Hyena step into the dense launch: the classes are then timed as the dense launches alone.
 step     DecodePool, evo-1-8k dimensions, synthetic weights, --streams slots behind prompts of --prompt-len nt, --tokens tokens: the median
          device time of a captured step and stats["decode_weight_bytes"], for weight_dtype bf16 and fp8.
 quality  the trained-like weight set (synthetic profile "contractive") at 7B width: last-position logits rel-L2 and greedy agreement over
-         96 tokens behind a --prompt-len prompt, FP8 against bf16 weights (and, with --small, the toy model).
+         96 tokens behind --quality-streams prompts of --prompt-len nt in one batch, FP8 against bf16 weights (and, with --small, the
+         toy model).
 Every figure is the median of --runs timed repetitions after --warmup untimed ones, with (min, max) beside it.  One JSON line, the box's
 copy probe beside the figures.  --tree PATH imports evo_amd from another checkout (with its own build of the library) and --weight-dtypes
 bf16 restricts the legs to the default weights: the parent commit's tree run the same way shows that the default path is where it was."""
@@ -32,7 +34,9 @@ def main(argv=None):
     ap.add_argument("--legs", default="kernel,step")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--streams", default="1,4,8")
+    ap.add_argument("--streams", default="1,4,8", help="pool sizes of the step leg, 1-64")
+    ap.add_argument("--rows", default="1,4,8", help="batch rows of the kernel leg, 1-64")
+    ap.add_argument("--quality-streams", type=int, default=1, help="prompts in the quality leg's batch, 1-64")
     ap.add_argument("--prompt-len", type=int, default=8192)
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--tree", default=None, help="import evo_amd from this checkout instead of the one the tool lives in")
@@ -103,13 +107,17 @@ def main(argv=None):
             copies = max(2, -(-(1 << 30) // (N * K)))
             ws = [(torch.randn(N, K, generator=gen, device=dev) / K ** 0.5).bfloat16() for _ in range(copies)]
             recs = [ops.w_quant_fp8(w) for w in ws] if "fp8" in fmts else [None] * copies
-            for M in (1, 4, 8):
+            for M in [int(r) for r in args.rows.split(",") if r]:
                 x = torch.randn(M, K, generator=gen, device=dev).bfloat16()
                 res = torch.zeros(M, D, dtype=torch.bfloat16, device=dev)
                 fs = torch.zeros(M, 3 * D, 2, dtype=torch.bfloat16, device=dev)
                 st = torch.zeros(M, D, 8, dtype=torch.complex64, device=dev)
 
                 def call(fmt, w, rec):
+                    if M > 8 and not name.startswith("linear_residual"):     # (no fold at these rows: the dense launch of the class)
+                        if name.startswith("norm_gate"):
+                            return (lambda: ops.mlp_gate(x, w)) if fmt == "bf16" else (lambda: ops.mlp_gate_w8(x, rec))
+                        return (lambda: ops.linear(x, w, zb)) if fmt == "bf16" else (lambda: ops.linear_w8(x, rec, zb))
                     if name.startswith("hyena"):
                         if fmt == "bf16":
                             return lambda: ops.hyena_decode_fused(x, scale, 1e-6, w, zb, fs, st, fir_w, zb, poles, resd, zb[:D], H)
@@ -189,15 +197,18 @@ def main(argv=None):
     if "quality" in legs:
         from evo_amd.generation import Generator
         model = model_of("evo-1-8k-base", profile="contractive")
-        prompt = "".join(rng.choice(list("ACGT"), size=args.prompt_len))
+        QS = args.quality_streams
+        prompts = torch.tensor([list("".join(rng.choice(list("ACGT"), size=args.prompt_len)).encode()) for _ in range(QS)], device=dev)
         got = {}
         for f in ("bf16", "fp8"):
-            ids, logits, _ = Generator(model, tok, top_k=1, weight_dtype=f).generate(dev, input_string=prompt, num_tokens=96, print_generation=False)
-            got[f] = (ids[0].cpu(), logits[0].double().cpu())
+            ids, logits, _ = Generator(model, tok, top_k=1, weight_dtype=f).generate(dev, input_ids=prompts, num_tokens=96, print_generation=False,
+                                                                                     stop_at_eos=False)
+            got[f] = (ids[0].cpu(), logits[0].double().cpu(), logits[:, 1].double().cpu())
         same = (got["fp8"][0] == got["bf16"][0]).long().cumprod(0)
         n = min(int(same.sum()) + 1, 96)
         a, b = got["fp8"][1], got["bf16"][1]
         out["quality"] = {"weights": "toy, synthetic" if args.small else "synthetic, profile contractive", "prompt_len": args.prompt_len,
+                          "streams": QS, "second_step_rel_l2_all_rows": float((got["fp8"][2] - got["bf16"][2]).norm() / got["bf16"][2].norm()),
                           "greedy_tokens": 96, "second_step_rel_l2": float((a[1] - b[1]).norm() / b[1].norm()),
                           "common_prefix_steps": n, "common_prefix_rel_l2": float((a[:n] - b[:n]).norm() / b[:n].norm()),
                           "tokens_agreeing": int((got["fp8"][0] == got["bf16"][0]).sum())}
